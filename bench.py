@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the VQ-VAE forward on N MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--batch B] [--dump-outputs DIR] [--full]
 
 One process per GPU.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes this file under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (so the plain command
@@ -17,9 +17,16 @@ A "step" is one `VQVAE.forward(x)` over one synthetic batch already resident in 
   c5            BASELINE config 5: full HIP path, per-GPU shard of B=8192 over 8,   256x256x3, K=8192, D=128, B=1024/GPU
 There is no fallback between workloads: a missing kernel library or extension is an error.
 
-Timing: W warm-up steps, then R repeats of EXACTLY K steps, each repeat bracketed by barrier + synchronize on both
-sides and reduced with MAX over ranks; R is chosen so that the timed work is at least ~1 s (never fewer than 5
-repeats).  `value` / `ms_per_step` come from the MEDIAN repeat; min / max are reported beside it.
+Timing: W warm-up steps, then ONE region of exactly K timed steps, bracketed by barrier + synchronize on both sides and
+reduced with MAX over ranks.  `value` / `ms_per_step` come from that region.  `--dump-outputs DIR` then writes what the
+last timed step returned (VQVAE.forward: embedding_loss, x_hat, perplexity) as DIR/<name>.npy, float32, 64 MB at most
+(beyond that x_hat keeps a fixed, seeded sample of its images); weights and images are seeded, so two runs with the same
+arguments see the same inputs.
+
+A plain run does only that and prints the headline line.  Everything else below is measured with `--full` only: the box
+calibration before the warm-up, the repeat protocol behind the headline region (R repeats of EXACTLY K steps, R chosen
+so that they take at least --min-seconds, never fewer than 5; their median / min / max in `timing_repeats`), and the
+per-kernel, roofline, power, CPU-baseline and side-workload figures after it.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the fused VectorQuantizer kernel, timed live with HIP events on the
 launch stream (vqvae_profile_* hooks) in extra steps after the timed region -- the event pairs add a little
@@ -87,7 +94,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="lower bound on the timed work (sets the repeats)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the calibration, the repeat protocol and every figure beside the headline (the --no-* options "
+                         "below and --min-seconds / --cpu-seconds apply to these)")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--full: lower bound on the repeats' timed work (sets the repeats)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-power", action="store_true", help="skip the ~3.5 s power / clock sampling run behind the timed region")
@@ -890,6 +902,36 @@ def pixelcnn_leg(torch, dev, seconds=0.6):
     return res
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6 - 4096                  # 64 MB in all, the .npy headers included
+OUTPUT_NAMES = ("embedding_loss", "x_hat", "perplexity")     # VQVAE.forward's tuple (the reference's models/vqvae.py:44)
+
+
+def dump_outputs(path, out):
+    """Write the arrays one step returned as <path>/<name>.npy in float32.  While all of them fit DUMP_BUDGET_BYTES they are
+    written whole; beyond that every array with a batch axis keeps the same fixed, seeded sample of its leading rows (sorted,
+    numpy default_rng(0)), so that two builds dump the same images.  -> {name: {shape, full_shape}} for the result line."""
+    import numpy as np
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in zip(OUTPUT_NAMES, out) if t is not None}
+    batched = [n for n, a in arrays.items() if a.ndim >= 1]
+    fixed = sum(a.nbytes for n, a in arrays.items() if n not in batched)
+    rows = min((arrays[n].shape[0] for n in batched), default=0)
+    per_row = sum(arrays[n].nbytes // max(arrays[n].shape[0], 1) for n in batched)
+    keep = None
+    if fixed + rows * per_row > DUMP_BUDGET_BYTES and per_row:
+        n_keep = max(1, (DUMP_BUDGET_BYTES - fixed) // per_row)
+        keep = np.sort(np.random.default_rng(0).choice(rows, size=n_keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for n, a in arrays.items():
+        full_shape = list(a.shape)
+        if keep is not None and n in batched:
+            a = a[keep]
+        np.save(os.path.join(path, f"{n}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[n] = {"shape": list(a.shape), "full_shape": full_shape}
+    return {"dir": path, "dtype": "float32", "arrays": info,
+            "sample": None if keep is None else f"{len(keep)} of {rows} rows: sorted numpy default_rng(0).choice(rows, size, replace=False)"}
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -952,6 +994,7 @@ def main():
     H = W = HW
     if dry:
         B, H, W = 8, 32, 32
+        torch.manual_seed(0)
         conv = torch.nn.Conv2d(3, 8, 3, padding=1)
 
         def step():                                   # stub: control flow only
@@ -997,24 +1040,28 @@ def main():
         return el, out
 
     calib = None
-    if not dry:
+    if args.full and not dry:
         calib = calibrate(torch, dev)                  # every rank: the GPUs enter the timed region equally warm
     for _ in range(args.warmup):
         step()
-    first, out = timed_repeat()
-    # every rank must run the same number of repeats: derive it from the max-reduced first repeat
-    repeats = max(5, min(200, int(args.min_seconds / max(first, 1e-6)) + 1))
-    if dry:
-        repeats = 5
-    times = [first]
-    for _ in range(repeats - 1):
-        el, out = timed_repeat()
-        times.append(el)
+    # the headline: exactly --steps timed steps, one region
+    elapsed, out = timed_repeat()
     assert torch.isfinite(out[1]).all()
-    srt = sorted(times)
-    elapsed = srt[len(srt) // 2]                       # median repeat
-    # every rank's own median step time and calibration, gathered on all ranks (tiny): rank 0 prints them
-    own_ms = sorted(own_times)[len(own_times) // 2] / args.steps * 1e3
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
+    own_ms = own_times[0] / args.steps * 1e3
+    times = None
+    if args.full:
+        # the repeat protocol behind the headline region: every rank must run the same number of repeats, derived from the
+        # max-reduced first repeat
+        first, _ = timed_repeat()
+        repeats = max(5, min(200, int(args.min_seconds / max(first, 1e-6)) + 1))
+        if dry:
+            repeats = 5
+        times = [first]
+        for _ in range(repeats - 1):
+            el, _ = timed_repeat()
+            times.append(el)
+    # every rank's own step time and calibration, gathered on all ranks (tiny): rank 0 prints them
     per_rank = [{"rank": rank, "ms_per_step": round(own_ms, 4), "calibration_tflops": (calib or {}).get("mfma_fp16_random_tflops"),
                  "cpus": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None}]
     if dist:
@@ -1024,7 +1071,7 @@ def main():
 
     # ---- per-kernel time of the fused VQ kernel (and the conv groups), extra steps outside the timed region ----
     extra, vq_ms, vq_n, nprof = {}, 0.0, 0, min(args.steps, 50)
-    if not dry:
+    if args.full and not dry:
         _lib.profile_enable(True)
         for _ in range(nprof):
             step()
@@ -1072,12 +1119,19 @@ def main():
             "data": "synthetic",
             "config": {"workload": desc, "per_gpu_batch": B, "global_batch": B * n_gpus, "image": [3, H, W],
                        "K": K, "D": D, "parallelism": f"batch-sharded replicas x{n_gpus}, no collective"},
-            "timing": {"repeats": len(times), "steps_per_repeat": args.steps, "statistic": "median repeat",
-                       "ms_per_step_min": round(srt[0] / args.steps * 1e3, 4),
-                       "ms_per_step_max": round(srt[-1] / args.steps * 1e3, 4),
-                       "timed_seconds_total": round(sum(times), 3)},
+            "timing": {"timed_steps": args.steps, "statistic": "one region of exactly `steps` steps, max over ranks",
+                       "timed_seconds": round(elapsed, 4)},
         }
+        if times:
+            srt = sorted(times)
+            line["timing_repeats"] = {"repeats": len(times), "steps_per_repeat": args.steps, "statistic": "median repeat",
+                                      "ms_per_step": round(srt[len(srt) // 2] / args.steps * 1e3, 4),
+                                      "ms_per_step_min": round(srt[0] / args.steps * 1e3, 4),
+                                      "ms_per_step_max": round(srt[-1] / args.steps * 1e3, 4),
+                                      "timed_seconds_total": round(sum(times), 3)}
         line["per_rank"] = per_rank
+        if dumped:
+            line["outputs"] = dumped
         if calib:
             # next to `value`: the box's bare-MFMA rate and clock, and the value on the calibration's reference box
             line = {k: v for k, v in list(line.items())[:2]} | {
@@ -1092,6 +1146,8 @@ def main():
             line["dry_run"] = True
             line["data"] = "dry-run stub (no kernels ran; not a measurement)"
         else:
+            line["source_sha"] = source_sha()
+        if args.full and not dry:
             rows = B * (H // 4) * (W // 4)
             pmc, pmc_stale = pmc_traffic(args.workload, _lib.vq_kernel_name(K, D, 0x1))
             if vq_n:
@@ -1171,7 +1227,6 @@ def main():
             line["kernels"] = {slot_names.get(k, k): dict(v, timing="hip-event brackets (event_inflated: the brackets add "
                                                                    "~10 % to a step; profiles/ holds the rocprofv3 figures)")
                                for k, v in extra.items()}
-            line["source_sha"] = source_sha()
             if n_gpus == 1 and not args.no_power:
                 # package power / shader clock while the SAME step runs back to back (its own ~3 s run behind the timed region: the
                 # hwmon files of this GPU, 50 ms apart).  The step sits at the package limit -- that, not issue slots, is its ceiling

@@ -22,7 +22,7 @@ def _json_lines(stdout):
 
 
 def test_gpus_2_spawns_two_ranks_and_prints_one_line():
-    p = _run(["--gpus", "2"])
+    p = _run(["--gpus", "2", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = _json_lines(p.stdout)
     assert len(lines) == 1, p.stdout
@@ -30,7 +30,8 @@ def test_gpus_2_spawns_two_ranks_and_prints_one_line():
     assert line["n_gpus"] == 2 and line["dry_run"] is True
     assert line["config"]["global_batch"] == 2 * line["config"]["per_gpu_batch"]
     assert line["scaling"] == "weak" and line["higher_is_better"] is True and line["steps"] == 2
-    assert line["timing"]["repeats"] >= 5 and line["timing"]["statistic"] == "median repeat"
+    assert line["timing"]["timed_steps"] == 2
+    assert line["timing_repeats"]["repeats"] >= 5 and line["timing_repeats"]["statistic"] == "median repeat"
     for key in ("metric", "value", "unit", "warmup", "ms_per_step", "vs_baseline", "dtype", "data", "config"):
         assert key in line
 
@@ -60,6 +61,23 @@ def test_single_rank_line_and_world_size_mismatch():
     # a launcher that set WORLD_SIZE=1 while the command says --gpus 2 is an error, not a silent 1-GPU run
     p = _run(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)
+
+
+def test_plain_run_times_exactly_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain run times one region of exactly --steps steps (no repeat protocol: that is --full's) and --dump-outputs
+    writes what the last timed step returned as float32 .npy files, the same bits from run to run."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        p = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(_json_lines(p.stdout)[0])
+    line = lines[0]
+    assert line["steps"] == 2 and line["timing"]["timed_steps"] == 2 and "timing_repeats" not in line
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["outputs"]["arrays"]["x_hat"]["shape"] == [line["config"]["per_gpu_batch"], 8, 32, 32]
+    a, b = np.load(tmp_path / "a" / "x_hat.npy"), np.load(tmp_path / "b" / "x_hat.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
 
 
 def test_no_gpu_without_dry_run_is_a_loud_error():

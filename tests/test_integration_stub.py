@@ -1,6 +1,6 @@
 """INTEGRATION.md section B, executed: integration/vqvae_hip_stub.py is the binding a maintainer of the reference would add
-(ctypes + torch only).  On the build container it is applied to the REAL reference classes (structure / state_dict
-contract; no GPU there); on the GPU box it runs numerically on a module with the reference's state_dict keys."""
+(ctypes + torch only).  Without a GPU it is applied to a module of the reference's recorded layout (structure / state_dict
+contract); on the GPU box it runs numerically on a module with the reference's state_dict keys."""
 import importlib.util
 import os
 import sys
@@ -39,27 +39,30 @@ def C_sizeof(t):
     return ctypes.sizeof(t)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="the reference tree is only in the build container")
-def test_install_on_the_real_reference_class():
-    """The stub reads the reference's own VQVAE through state_dict(): every key it needs exists with the expected shape,
-    install() keeps the constructor / attributes untouched, and the patched forward refuses CPU tensors loudly."""
-    sys.path.insert(0, "/root/reference")
-    sys.dont_write_bytecode = True
-    try:
-        from models.vqvae import VQVAE
-    finally:
-        sys.path.remove("/root/reference")
+def test_install_on_the_real_reference_class(golden_models):
+    """The stub reads the reference's VQVAE through state_dict(): on a module of the reference's layout -- its state_dict keys, in
+    order, and its default-init bits are the ones the reference's own class recorded in tests/golden/model_cases.npz (kat1) --
+    every key the stub needs exists with the expected shape, install() keeps the attributes untouched, and the patched forward
+    refuses CPU tensors loudly."""
+    from tests.test_model_gpu import build
     stub = _stub()
-    torch.manual_seed(0)
-    m = VQVAE(128, 32, 2, 512, 64, 0.25).eval()
-    sd = m.state_dict()
+    m, _ = build("kat1")                                   # VQVAE(128, 32, 2, 512, 64, 0.25) after torch.manual_seed(0)
+    plain = torch.nn.Module.__new__(type("RefLike", (torch.nn.Module,), {}))      # a bare module carrying only the layers
+    torch.nn.Module.__init__(plain)
+    for attr in ("encoder", "pre_quantization_conv", "vector_quantization", "decoder"):
+        setattr(plain, attr, getattr(m, attr))
+    sd = plain.state_dict()
+    keys = list(golden_models["kat1/keys"])
+    assert list(sd.keys()) == keys, "state_dict keys / order differ from the reference's class"
+    for k, s in zip(keys, golden_models["kat1/sha"][5:]):
+        assert cases.sha(sd[k]) == s, f"default init of {k} differs from the reference's"
     for f, k in stub.RAW:
         assert k in sd, k
     assert sd["decoder.inverse_conv_stack.0.weight"].shape == (64, 128, 3, 3)          # ConvTranspose2d: (Cin, Cout, kh, kw)
-    stub.install(m)
-    assert hasattr(m, "hip_repack") and m.vector_quantization.beta == 0.25
+    stub.install(plain)
+    assert hasattr(plain, "hip_repack") and plain.vector_quantization.beta == 0.25
     with pytest.raises(RuntimeError, match="no CPU path"):
-        m(torch.randn(2, 3, 32, 32))
+        plain(torch.randn(2, 3, 32, 32))
 
 
 @pytest.mark.gpu

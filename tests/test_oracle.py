@@ -2,11 +2,10 @@
 
 1. C oracle vs the committed golden vectors produced by the real reference.
 2. C oracle's rounding order vs live torch CPU ops (the order probes of SURVEY.md A.1).
-3. torch_port (the CPU-baseline restatement) vs golden, and -- where /root/reference
-   exists -- bitwise vs the imported reference.
+3. torch_port (the CPU-baseline restatement) vs golden, and bitwise vs the reference's
+   one-thread forward recorded in the golden vectors.
 """
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -106,27 +105,29 @@ def test_c_oracle_model_matches_reference_golden(name, golden_models):
     np.testing.assert_allclose(x_hat, golden_models[f"{name}/x_hat"][:B], atol=1e-5, rtol=1e-4)
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference tree not present (GPU box)")
-def test_torch_port_bitwise_vs_imported_reference():
-    sys.dont_write_bytecode = True
-    ref = os.environ.get("VQVAE_REFERENCE", "/root/reference")
-    sys.path.insert(0, ref)
+def test_torch_port_bitwise_vs_imported_reference(golden_models):
+    """torch_port against the reference's own forward as oracle/gen_golden.py recorded it (tests/golden/model_cases.npz, kat1:
+    main.py's defaults, the reference's torch.manual_seed(0) init, one host thread): the same init bits and state_dict keys, and
+    x_hat, loss and perplexity bit for bit -- the same ATen ops in the same order on one thread."""
+    name = "kat1"
+    h, rh, nl, K, D, beta, B, H, W = cases.MODEL_CASES[name]
+    keys = list(golden_models[f"{name}/keys"])
+    sha = list(golden_models[f"{name}/sha"])
+    torch.manual_seed(0)
+    sd = torch_port.init_state_dict(h, rh, K, D, n_res_layers=nl)
+    assert set(sd.keys()) == set(keys)
+    for k, s in zip(keys, sha[5:]):
+        assert cases.sha(sd[k]) == s, f"weight init differs from the reference's: {k}"
+    x = cases.model_inputs(name)
+    assert cases.sha(x) == sha[0]
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
     try:
-        import models.quantizer as rq
-        from models.vqvae import VQVAE
-        rq.device = torch.device("cpu")
-        torch.manual_seed(0)
-        m = VQVAE(128, 32, 2, 512, 64, 0.25).eval()
-        x = torch.randn(8, 3, 32, 32)
-        with torch.no_grad():
-            loss, x_hat, ppl = m(x)
-        sd = {k: v.detach() for k, v in m.state_dict().items()}
-        l2, xh2, p2 = torch_port.forward(sd, x.clone(), 0.25, 2)
-        assert torch.equal(x_hat, xh2) and torch.equal(loss, l2) and torch.equal(ppl, p2)
+        loss, x_hat, ppl = torch_port.forward(sd, x.clone(), beta, nl)
     finally:
-        sys.path.remove(ref)
-        for k in [k for k in sys.modules if k == "models" or k.startswith("models.")]:
-            del sys.modules[k]
+        torch.set_num_threads(threads)
+    assert np.array_equal(x_hat.numpy().view(np.uint32), golden_models[f"{name}/x_hat"].view(np.uint32))
+    assert loss.item() == golden_models[f"{name}/loss"].item() and ppl.item() == golden_models[f"{name}/perplexity"].item()
 
 
 def test_residual_quirks():
@@ -203,20 +204,19 @@ def test_oracles_on_a_trained_checkpoint(name, golden_trained):
     np.testing.assert_allclose(ref["z_e"], g_ze, atol=2e-6 * cmax, rtol=0)
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("name", list(cases.TRAINED_CASES))
 def test_trained_goldens_reproduce_from_the_unmodified_reference(name, golden_trained):
-    from tests import synthdata
-    sys.path.insert(0, os.environ.get("VQVAE_REFERENCE", "/root/reference"))
-    sys.dont_write_bytecode = True
-    import models.quantizer as ref_q
-    from models.vqvae import VQVAE
-    ref_q.device = torch.device("cpu")
+    """The committed trained goldens are the unmodified reference's forward on the committed checkpoint and images
+    (oracle/gen_golden.py trained, one host thread): the reference's ATen ops (oracle/torch_port.py, bitwise the reference by
+    test_torch_port_bitwise_vs_imported_reference) reproduce their x_hat bit for bit and their loss exactly."""
     h, rh, nl, K, D, beta, B, seed = cases.TRAINED_CASES[name]
-    m = VQVAE(h, rh, nl, K, D, beta).eval()
-    m.load_state_dict(cases.trained_state(name), strict=True)
-    with torch.no_grad():
-        loss, x_hat, ppl = m(torch.from_numpy(golden_trained[f"{name}/x"]))
+    x = torch.from_numpy(golden_trained[f"{name}/x"])
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        loss, x_hat, ppl = torch_port.forward(cases.trained_state(name), x, beta, nl)
+    finally:
+        torch.set_num_threads(threads)
     assert cases.sha(x_hat) == golden_trained[f"{name}/sha"][3]
     assert loss.item() == golden_trained[f"{name}/loss"].item()
 

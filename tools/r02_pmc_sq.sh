@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/pmc_sq
 rm -rf $O; mkdir -p $O
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES \
-   --output-format csv -d $O/a -- python $R/bench.py --no-cpu-baseline --steps 4 --warmup 1 --min-seconds 0 > $O/a.log 2>&1
+   --output-format csv -d $O/a -- python $R/bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --min-seconds 0 > $O/a.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE \
-   --output-format csv -d $O/b -- python $R/bench.py --no-cpu-baseline --steps 4 --warmup 1 --min-seconds 0 > $O/b.log 2>&1
+   --output-format csv -d $O/b -- python $R/bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --min-seconds 0 > $O/b.log 2>&1
 python - <<PY
 import csv, glob, collections
 for d in ("a", "b"):

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r06c5; rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 B="--workload c5 --no-cpu-baseline --no-other-workloads --no-power --steps 2 --warmup 1 --min-seconds 0.01"
 for set in lds util; do
-  (cd $R && timeout 300 rocprofv3 -i tools/pmc_$set.txt --kernel-trace --output-format csv -d $O/pmc_$set -- python bench.py $B > $O/pmc_$set.log 2>&1)
+  (cd $R && timeout 300 rocprofv3 -i tools/pmc_$set.txt --kernel-trace --output-format csv -d $O/pmc_$set -- python bench.py --full $B > $O/pmc_$set.log 2>&1)
 done
 python - <<PY
 import csv, collections, glob

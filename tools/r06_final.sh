@@ -13,10 +13,10 @@ fi
 cd /tmp; export TMPDIR=/tmp
 B="--no-cpu-baseline --no-other-workloads --no-power --steps 2 --warmup 1 --min-seconds 0.01"
 for c in fetch write; do
-  (cd $R && timeout 200 rocprofv3 -i tools/pmc_$c.txt --kernel-trace --output-format csv -d $O/pmc_c3_$c -- python bench.py $B > $O/pmc_c3_$c.log 2>&1)
+  (cd $R && timeout 200 rocprofv3 -i tools/pmc_$c.txt --kernel-trace --output-format csv -d $O/pmc_c3_$c -- python bench.py --full $B > $O/pmc_c3_$c.log 2>&1)
   (cd $R && timeout 200 rocprofv3 -i tools/pmc_$c.txt --kernel-trace --output-format csv -d $O/vq_pmc_$c -- python tools/vq_traffic.py > $O/vq_pmc_$c.log 2>&1)
   for w in c4 c5; do
-    (cd $R && timeout 240 rocprofv3 -i tools/pmc_$c.txt --kernel-trace --output-format csv -d $O/pmc_${w}_$c -- python bench.py --workload $w $B > $O/pmc_${w}_$c.log 2>&1)
+    (cd $R && timeout 240 rocprofv3 -i tools/pmc_$c.txt --kernel-trace --output-format csv -d $O/pmc_${w}_$c -- python bench.py --full --workload $w $B > $O/pmc_${w}_$c.log 2>&1)
   done
 done
 (cd $R && python tools/pmc_traffic.py c3 4096 $O/pmc_c3_fetch $O/pmc_c3_write $O/vq_pmc_fetch $O/vq_pmc_write 4194304 $O/hbm_traffic_c3.json) > $O/traffic.txt 2>&1
@@ -24,10 +24,10 @@ done
 (cd $R && python tools/pmc_traffic.py c5 1024 $O/pmc_c5_fetch $O/pmc_c5_write $O/pmc_c5_fetch $O/pmc_c5_write 4194304 $O/hbm_traffic_c5.json) >> $O/traffic.txt 2>&1
 for w in c3 c4 c5; do [ -s $O/hbm_traffic_$w.json ] && cp $O/hbm_traffic_$w.json $R/profiles/hbm_traffic_$w.json; done
 # the bench lines are printed AFTER the traffic files of the same build exist
-(cd $R && timeout 600 python bench.py 2>$O/bench_c3.err | tail -1) > $O/bench_c3.json
-for w in c4 c5; do (cd $R && timeout 300 python bench.py --workload $w --no-cpu-baseline --no-other-workloads --no-power 2>/dev/null | tail -1) > $O/bench_$w.json; done
+(cd $R && timeout 600 python bench.py --full 2>$O/bench_c3.err | tail -1) > $O/bench_c3.json
+for w in c4 c5; do (cd $R && timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-other-workloads --no-power 2>/dev/null | tail -1) > $O/bench_$w.json; done
 for w in c3 c4 c5; do
-  (cd $R && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --workload $w --no-cpu-baseline --no-other-workloads --no-power --steps 10 --min-seconds 0.2 > $O/prof_$w.log 2>&1)
+  (cd $R && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --full --workload $w --no-cpu-baseline --no-other-workloads --no-power --steps 10 --min-seconds 0.2 > $O/prof_$w.log 2>&1)
   DB=$(find $O/prof_$w -name "*.db" | head -1)
   [ -n "$DB" ] && python $R/tools/rocprof_summary.py $DB 24 > $O/${w}_kernel_stats.txt
 done
