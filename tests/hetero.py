@@ -185,3 +185,18 @@ def per_channel_check(got, ref, what, atol_rel=1e-5, rtol=1e-4, per_image=True):
                              f"{rtol:g}; worst at {i}: got {got[i]:.9g} ref {ref[i]:.9g} (channel max {cmax[i[0] if per_image else 0, i[1], 0, 0]:.3g}); "
                              f"largest error = {worst:.3g} x its channel's maximum")
     return worst
+
+
+def explain_flips(got, want, z_ref_rows64, cb64, cmax):
+    """every index flip against the reference must be explained by the z_e tolerance: fp64 gap of the two codes
+    <= 8 eps32 (|z|^2 + |e|^2) + 2 sum_c tol_c |e_a,c - e_b,c|  with tol_c the per-channel z_e tolerance.  -> (flip rows, worst ratio)"""
+    import numpy as np
+    flips = np.nonzero(got != want)[0]
+    worst = 0.0
+    for r in flips:
+        z = z_ref_rows64[r]
+        d = ((z[None, :] - cb64) ** 2).sum(1)
+        tol_c = 1e-5 * cmax + 1e-4 * np.abs(z)
+        bound = 8 * 2.0 ** -24 * ((z ** 2).sum() + (cb64[want[r]] ** 2).sum()) + 2 * (tol_c * np.abs(cb64[got[r]] - cb64[want[r]])).sum()
+        worst = max(worst, abs(d[got[r]] - d[want[r]]) / bound)
+    return flips, worst

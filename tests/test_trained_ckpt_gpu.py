@@ -54,20 +54,6 @@ def _flags(scheme):
     return {"guard": None, "fp16x2": 0, "bf16x3": F.FWD_CONV_BF16_SPLIT, "fp32": F.FWD_CONV_EXACT_FP32}[scheme]
 
 
-def _explain_flips(got, want, z_ref_rows64, cb64, cmax):
-    """every index flip against the reference must be explained by the z_e tolerance: fp64 gap of the two codes
-    <= 8 eps32 (|z|^2 + |e|^2) + 2 sum_c tol_c |e_a,c - e_b,c|  with tol_c the per-channel z_e tolerance.  -> (flip rows, worst ratio)"""
-    flips = np.nonzero(got != want)[0]
-    worst = 0.0
-    for r in flips:
-        z = z_ref_rows64[r]
-        d = ((z[None, :] - cb64) ** 2).sum(1)
-        tol_c = 1e-5 * cmax + 1e-4 * np.abs(z)
-        bound = 8 * 2.0 ** -24 * ((z ** 2).sum() + (cb64[want[r]] ** 2).sum()) + 2 * (tol_c * np.abs(cb64[got[r]] - cb64[want[r]])).sum()
-        worst = max(worst, abs(d[got[r]] - d[want[r]]) / bound)
-    return flips, worst
-
-
 @pytest.mark.parametrize("name", NAMES)
 def test_quantizer_bit_exact_on_the_reference_ze_bits(name, golden_trained):
     h, rh, nl, K, D, beta, B, seed = cases.TRAINED_CASES[name]
@@ -120,7 +106,7 @@ def test_whole_forward_vs_reference_golden(name, scheme, golden_trained, capsys)
     cb64 = m.vector_quantization.embedding.weight.detach().cpu().double().numpy()
     zr = np.transpose(g_ze, (0, 2, 3, 1)).reshape(-1, D).astype(np.float64)
     cmax = np.abs(g_ze).max(axis=(0, 2, 3))
-    flips, worst = _explain_flips(got, want, zr, cb64, cmax)
+    flips, worst = hetero.explain_flips(got, want, zr, cb64, cmax)
     assert worst <= 1.0, f"an index flip is not explained by the z_e tolerance: gap = {worst:.3g} x the bound"
     assert len(flips) <= max(1, int(1e-3 * got.size)), f"{len(flips)} flips in {got.size} rows"
     clean = np.setdiff1d(np.arange(B), np.unique(flips // 64))
@@ -179,7 +165,7 @@ def test_config3_batch_every_row_vs_reference_port(name, scheme, capsys):
     got, want = idx.cpu().numpy().reshape(-1), idx_ref.numpy().reshape(-1)
     zr = z_e_ref.permute(0, 2, 3, 1).reshape(-1, D).double().numpy()
     cmax = z_e_ref.abs().amax(dim=(0, 2, 3)).double().numpy()
-    flips, worst = _explain_flips(got, want, zr, cbk.double().numpy(), cmax)
+    flips, worst = hetero.explain_flips(got, want, zr, cbk.double().numpy(), cmax)
     assert worst <= 1.0, f"an index flip is not explained by the z_e tolerance: gap = {worst:.3g} x the bound"
     assert len(flips) <= int(1e-4 * got.size), f"{len(flips)} flips in {got.size} rows (SURVEY 8c expects <= 1e-4)"
     clean = np.setdiff1d(np.arange(B), np.unique(flips // 64))

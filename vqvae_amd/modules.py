@@ -61,7 +61,8 @@ class LazyOneHot:
     or being passed to a torch function.  `VectorQuantizer.LAZY_MIN_ENCODINGS = False` returns the tensor itself as before."""
 
     def __init__(self, idx, n_e):
-        self._idx, self._n_e, self._t = idx, n_e, None
+        # its own copy: the caller also gets `idx` (the fifth output) and may edit it in place before the one-hot is first used
+        self._idx, self._n_e, self._t = idx.clone(), n_e, None
 
     def materialize(self):
         if self._t is None:
@@ -327,7 +328,7 @@ class VQVAE(nn.Module):
 
     def _c_weights(self):
         """-> (VqvaeWeights, keep-alive tensors): every layer packed once per weight version into ONE buffer by
-        vqvae_weights_pack_f32; rebuilt when any parameter's (data_ptr, _version) changes or invalidate_caches() ran."""
+        vqvae_weights_pack_f32; rebuilt when any parameter's (data_ptr, _version) or the quantizer's beta changes, or invalidate_caches() ran."""
         from . import _lib
         params = dict(self.named_parameters(remove_duplicate=False))
         n_res = self.encoder.conv_stack[5].n_res_layers
@@ -337,7 +338,9 @@ class VQVAE(nn.Module):
                 tensors[f] = params["encoder.conv_stack.4.weight"]
             else:
                 tensors[f] = params[k]
-        key = tuple((t.data_ptr(), t._version) for t in tensors.values()) + (str(tensors["enc0_w"].device),)
+        # beta is packed into VqvaeDims: a changed m.vector_quantization.beta must repack, as models/quantizer.py:63-64 reads it per call
+        key = tuple((t.data_ptr(), t._version) for t in tensors.values()) + (str(tensors["enc0_w"].device),
+                                                                              float(self.vector_quantization.beta))
         hit = _cache.side(self).get("c_weights")
         if hit is not None and hit[0] == key:
             _cache.wait_ready(hit[3], tensors["enc0_w"].device)          # packed on another stream a moment ago?
