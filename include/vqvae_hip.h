@@ -408,6 +408,59 @@ VQVAE_API int vqvae_gated_activation_f32(const float *t1, const float *t2, const
                                          int HW, int dim, float *out, vqvae_stream_t stream);
 VQVAE_API int vqvae_add_f32(const float *a, const float *b, int64_t n, float *out, vqvae_stream_t stream);
 
+/* ------------------------------------------------------- GatedPixelCNN prior: backward (csrc/pixelcnn_backward.hip)
+ * What loss.backward() of pixelcnn/gated_pixelcnn.py:78-111 needs beyond the conv path's entries.  Row-major activations, channel
+ * counts % 4 == 0 and 16-byte aligned tensors where noted.  No floating-point atomics: every result is bit-reproducible.
+ *
+ * vqvae_conv_taps_wgrad_f32 -- weight gradient of a tap-list convolution (vqvae_conv_taps_forward_f32's tap semantics):
+ *     grad_w[co][ci][t] = sum_{b,y,x} grad_y[b,y,x,co] * x[b, y+dy[t], x+dx[t], ci]      (0 outside the map)
+ *   grad_w is the weight's own (Cout, Cin, kh, kw) tensor for a list in (ky, kx) order.  ntaps <= 32, |dy|, |dx| <= 7 (HOST arrays),
+ *   Cin, Cout % 4 == 0, grad_y / x 16-byte aligned.  Exact fp32 products (fp32 MFMA, the pixel as the reduction index); maps of at
+ *   most 8 x 8 with 32-channel multiples stage both maps of an image in LDS once and serve every tap from there, other shapes run
+ *   per tap over 32-pixel blocks.  Partial sums per image / pixel range in the workspace, combined in a fixed order.  The workspace
+ *   size depends on (ntaps, Cin, Cout) only; 0 = unsupported.                                                                  */
+VQVAE_API size_t vqvae_conv_taps_wgrad_workspace_bytes(int ntaps, int Cin, int Cout);
+VQVAE_API int vqvae_conv_taps_wgrad_f32(const float *grad_y, const float *x, int64_t B, int H, int W, int Cin, int Cout, int ntaps,
+                                        const int8_t *dy, const int8_t *dx, float *grad_w, void *workspace, size_t workspace_bytes,
+                                        vqvae_stream_t stream);
+/* Data gradient of a tap-list convolution: grad_x = conv over the NEGATED taps of grad_y with the per-tap transposed weight, i.e.
+ * vqvae_conv_taps_forward_ep_f32(grad_y, packed, NULL, B, H, W, Cout, Cin, ntaps, -dy, -dx, 0, addend, NULL, grad_x) -- the
+ * forward's kernels and product scheme; the addend epilogue adds the other gradient terms of the same tensor.  This packs taps
+ * [t0, t0 + ntaps) of the forward weight w (Cout, Cin, wtaps) for that call (ntaps <= 16: longer lists run as slices, like the
+ * forward); dy / dx are the FORWARD offsets of the slice (HOST arrays).  The buffer holds the packed image and, behind it, the
+ * transposed weight the pack reads (no temporary allocation): vqvae_conv_taps_pack_dgrad_bytes.                               */
+VQVAE_API size_t vqvae_conv_taps_pack_dgrad_bytes(int ntaps, int Cin, int Cout);
+VQVAE_API int vqvae_conv_taps_pack_dgrad_f32(const float *w, int wtaps, int t0, int ntaps, const int8_t *dy, const int8_t *dx, int Cin,
+                                             int Cout, float *packed, vqvae_stream_t stream);
+/* Backward of vqvae_gated_activation_f32: (a|g) recomputed in the forward's order ((t1 + t2) + cond, same device functions),
+ *     grad_pre[.., c] = go sigma(g) (1 - tanh^2 a),   grad_pre[.., dim + c] = go tanh(a) sigma(g) (1 - sigma(g))
+ *   grad_out (B,HW,dim), grad_pre (B,HW,2*dim).  With cond: grad_cond[b] = [grad_cond_in[b] +] sum over HW of grad_pre[b] (fp64 in a
+ *   fixed order), (B, 2*dim) -- the class embedding's gradient per image; grad_cond_in may alias grad_cond, so that the two gates
+ *   of one layer share one buffer.  grad_cond / grad_cond_in may be NULL; they need cond.                                      */
+VQVAE_API int vqvae_gated_activation_backward_f32(const float *t1, const float *t2, const float *cond, const float *grad_out, int64_t B,
+                                                  int HW, int dim, float *grad_pre, const float *grad_cond_in, float *grad_cond,
+                                                  vqvae_stream_t stream);
+/* Backward of vqvae_gather_rows_f32 (nn.Embedding): grad_table[k] = sum_{i: idx_i = k} grad_out[i], (rows, C); rows nobody read are 0.
+ * Out-of-range indices: the forward clamps them into [0, rows), and so does this -- the gradient goes to the row the forward read.
+ * The stable-sort segmented sum of vqvae_vq_backward_f32: indices radix-sorted by row (ascending source order within a row),
+ * chunks of 512 sorted rows summed in fp64 by one workgroup, a row's chunks combined in order.  Any C.                       */
+VQVAE_API size_t vqvae_gather_rows_backward_workspace_bytes(int64_t n, int C, int rows);
+VQVAE_API int vqvae_gather_rows_backward_f32(const int64_t *idx, const float *grad_out, int64_t n, int C, int rows, float *grad_table,
+                                             void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+/* nn.CrossEntropyLoss() (mean) over N rows of K logits, row-major (B,H,W,K) as the prior's last conv writes them; int64 targets.
+ *   loss: one device float, the mean of (m + log sum exp(l - m)) - l[target] with m the row maximum, summed in fp64 in a fixed
+ *   order.  backward: grad_logits = g (softmax - onehot) / N, g = *grad_loss (device scalar; NULL = 1).  A target outside [0, K)
+ *   makes the loss and that row's gradient NaN (no host check: nothing synchronises).                                          */
+VQVAE_API size_t vqvae_cross_entropy_workspace_bytes(int64_t N);
+VQVAE_API int vqvae_cross_entropy_f32(const float *logits, const int64_t *targets, int64_t N, int K, float *loss, void *workspace,
+                                      size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_cross_entropy_backward_f32(const float *logits, const int64_t *targets, int64_t N, int K, const float *grad_loss,
+                                               float *grad_logits, vqvae_stream_t stream);
+/* grad_b[c] = sum over the P rows of grad_y (P, C) row-major, any C (vqvae_bias_grad_f32 stops at 256): fp64, fixed order.       */
+VQVAE_API size_t vqvae_bias_grad_wide_workspace_bytes(int C);
+VQVAE_API int vqvae_bias_grad_wide_f32(const float *grad_y, int64_t P, int C, float *grad_b, void *workspace, size_t workspace_bytes,
+                                       vqvae_stream_t stream);
+
 /* ------------------------------------------------------------------- whole path
  * models/vqvae.py:29-44 as ONE call: Encoder (models/encoder.py:28-43) -> pre_quantization_conv (models/vqvae.py:33)
  * -> VectorQuantizer (models/quantizer.py:45-76) -> Decoder (models/decoder.py:27-39).  The caller owns every buffer:

@@ -112,6 +112,18 @@ SIGNATURES = {
     "vqvae_im2col_rows_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vqvae_gated_activation_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "vqvae_add_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "vqvae_conv_taps_wgrad_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "vqvae_conv_taps_wgrad_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_conv_taps_pack_dgrad_bytes": (_sz, [_i32, _i32, _i32]),
+    "vqvae_conv_taps_pack_dgrad_f32": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "vqvae_gated_activation_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vqvae_gather_rows_backward_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vqvae_gather_rows_backward_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "vqvae_cross_entropy_workspace_bytes": (_sz, [_i64]),
+    "vqvae_cross_entropy_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "vqvae_cross_entropy_backward_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "vqvae_bias_grad_wide_workspace_bytes": (_sz, [_i32]),
+    "vqvae_bias_grad_wide_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -7,11 +7,22 @@ initialisation as the reference, so a PixelCNN checkpoint written by `pixelcnn/g
         .forward(x (B,H,W) int64, label (B,) int64) -> logits (B, input_dim, H, W)          (models.py:118-127)
         .generate(label, shape=(8, 8), batch_size=64) -> (B, *shape) int64                   (models.py:129-142)
 
-Forward-only.  Activations are row-major (B,H,W,C); a masked convolution is a stride-1 convolution over its causal tap list
+Activations are row-major (B,H,W,C); a masked convolution is a stride-1 convolution over its causal tap list
 (round 4: vqvae_conv_taps_forward_f32 -- the conv path's kernels with an explicit tap list, no im2col pass; lists of more than
 16 taps, i.e. the first layer's 4 x 7 vertical stack, run as a chain of launches over slices of the list); embeddings, the gated
 activation (+ class-conditional term) and the residual add are small HIP kernels (csrc/pixelcnn.hip).  The
 categorical sampling of `generate` uses torch's softmax + multinomial on the device, as the reference does.
+
+Training (pixelcnn/gated_pixelcnn.py:78-111).  When the module is in training mode, grad is enabled and some parameter requires
+grad, `GatedPixelCNN.forward` and `GatedMaskedConv2d.forward` build an autograd graph whose every layer runs forward AND backward on
+libvqvae_hip.so (csrc/pixelcnn_backward.hip): one autograd.Function per gated layer, the embeddings, the 1x1 head convs and the
+layout changes.  The forward is the same sequence of launches as the eval path, so the logits are the same bits.  Backward:
+tap-list weight gradients (vqvae_conv_taps_wgrad_f32, over the FULL tap list -- the mask-'A' taps get the nonzero gradient the
+reference's autograd gives them), tap-list data gradients through the forward's tap kernels with the taps negated and the weight
+transposed per tap (vqvae_conv_taps_pack_dgrad_f32), the 1x1 layers through the conv path's CONVT_1x1 kernels and
+vqvae_conv_wgrad_ex_f32, the gated activation's backward with the class-conditional per-image sums, and sort-based segmented sums
+for both embeddings.  No floating-point atomics: two backward passes give the same bits.  `cross_entropy` is the HIP form of the
+reference's criterion.  Every other case (eval mode, torch.no_grad(), generate, the hipGraph sampler) runs the forward-only path.
 No CPU path, no fallback.
 """
 from __future__ import annotations
@@ -23,6 +34,7 @@ import torch.nn as nn
 
 from . import _cache, _lib, conv_hip
 from ._lib import VqvaeHipError
+from .autograd_conv import CONVT_1x1, _holder, conv_wgrad, relu_backward
 from .conv_hip import CONV_1x1, RELU_OUT, _sp
 
 
@@ -81,6 +93,252 @@ def _add(a, b):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------ training
+
+def _autograd_wanted(mod):
+    """the autograd path runs in training mode, with grad enabled, when some parameter requires grad; everything else runs the
+    forward-only path (eval, torch.no_grad(), generate, the hipGraph sampler)"""
+    return mod.training and torch.is_grad_enabled() and any(p.requires_grad for p in mod.parameters())
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def _taps_arrays(taps, sign=1):
+    k = len(taps)
+    return (C.c_int8 * k)(*[sign * t[0] for t in taps]), (C.c_int8 * k)(*[sign * t[1] for t in taps])
+
+
+def bias_grad(g):
+    """per-channel sums over all pixels of a row-major gradient (vqvae_bias_grad_wide_f32: any width)"""
+    g = g.contiguous()
+    Cc = g.shape[-1]
+    L = _lib.load()
+    n = L.vqvae_bias_grad_wide_workspace_bytes(Cc)
+    ws = _ws(n, g.device)
+    out = torch.empty(Cc, dtype=torch.float32, device=g.device)
+    _lib.check(L.vqvae_bias_grad_wide_f32(g.data_ptr(), g.numel() // Cc, Cc, out.data_ptr(), ws.data_ptr(), n, _sp(g)))
+    return out
+
+
+def taps_wgrad(gy, x, taps):
+    """(Cout, Cin, ntaps): grad_w[co][ci][t] = sum gy[b,y,x,co] x[b, y+dy_t, x+dx_t, ci]  (vqvae_conv_taps_wgrad_f32)"""
+    gy, x = gy.contiguous(), x.contiguous()
+    B, H, W, Cin = x.shape
+    Cout, n = gy.shape[3], len(taps)
+    L = _lib.load()
+    nb = L.vqvae_conv_taps_wgrad_workspace_bytes(n, Cin, Cout)
+    if nb == 0:
+        raise VqvaeHipError(f"tap-list weight gradient: {n} taps, Cin={Cin}, Cout={Cout} not supported")
+    ws = _ws(nb, x.device)
+    gw = torch.empty((Cout, Cin, n), dtype=torch.float32, device=x.device)
+    dy, dx = _taps_arrays(taps)
+    _lib.check(L.vqvae_conv_taps_wgrad_f32(gy.data_ptr(), x.data_ptr(), B, H, W, Cin, Cout, n, C.cast(dy, C.c_void_p),
+                                           C.cast(dx, C.c_void_p), gw.data_ptr(), ws.data_ptr(), nb, _sp(x)))
+    return gw
+
+
+def taps_dgrad(gy, mod, weight, taps, addend=None):
+    """grad_x of conv_hip.conv_taps: the tap kernels over the negated taps with the per-tap transposed weight, packed per weight
+    version on a holder of `mod` (vqvae_conv_taps_pack_dgrad_f32); lists longer than 16 taps run as the forward's slices, each
+    launch adding to the previous one's result; `addend` rides in the first launch's epilogue."""
+    gy = gy.contiguous()
+    B, H, W, Cout = gy.shape
+    Cin, n = weight.shape[1], len(taps)
+    L = _lib.load()
+    hold = _holder(mod, ("taps_dgrad", tuple(taps)))
+    nsl = (n + 15) // 16
+    per = (n + nsl - 1) // nsl
+    y = addend.contiguous() if addend is not None else None
+    for s0 in range(0, n, per):
+        sl = taps[s0:s0 + per]
+        k = len(sl)
+        dy, dx = _taps_arrays(sl)
+        ndy, ndx = _taps_arrays(sl, -1)
+
+        def pack(w, buf, dy=dy, dx=dx, k=k, s0=s0):
+            return L.vqvae_conv_taps_pack_dgrad_f32(w.data_ptr(), n, s0, k, C.cast(dy, C.c_void_p), C.cast(dx, C.c_void_p), Cin,
+                                                    Cout, buf.data_ptr(), _sp(w))
+        packed = conv_hip._packed(hold, ("taps_dgrad", s0), weight, lambda k=k: L.vqvae_conv_taps_pack_dgrad_bytes(k, Cin, Cout), pack)
+        out = torch.empty((B, H, W, Cin), dtype=torch.float32, device=gy.device)
+        _lib.check(L.vqvae_conv_taps_forward_ep_f32(gy.data_ptr(), packed.data_ptr(), None, B, H, W, Cout, Cin, k,
+                                                    C.cast(ndy, C.c_void_p), C.cast(ndx, C.c_void_p), 0,
+                                                    y.data_ptr() if y is not None else None, None, out.data_ptr(), _sp(gy)))
+        y = out
+    return y
+
+
+def gate_backward(t1, cond, go, dim, gcond=None, accumulate=False):
+    """grad of (a|g) -> tanh(a) sigmoid(g) at (a|g) = t1 + cond[b]; with gcond (B, 2 dim): [+]= the per-image sums over HW"""
+    B, H, W, _ = t1.shape
+    gpre = torch.empty((B, H, W, 2 * dim), dtype=torch.float32, device=t1.device)
+    go = go.contiguous()
+    _lib.check(_lib.load().vqvae_gated_activation_backward_f32(
+        t1.data_ptr(), None, cond.data_ptr() if cond is not None else None, go.data_ptr(), B, H * W, dim, gpre.data_ptr(),
+        gcond.data_ptr() if (gcond is not None and accumulate) else None, gcond.data_ptr() if gcond is not None else None, _sp(go)))
+    return gpre
+
+
+def gather_rows_backward(idx, g, rows):
+    """grad_table (rows, C) of out = table[idx]: fixed-order segmented sums (vqvae_gather_rows_backward_f32)"""
+    idx, g = idx.contiguous().view(-1), g.contiguous()
+    n, Cc = idx.numel(), g.shape[-1]
+    L = _lib.load()
+    nb = L.vqvae_gather_rows_backward_workspace_bytes(n, Cc, rows)
+    if nb == 0:
+        raise VqvaeHipError(f"embedding backward: n={n}, C={Cc}, rows={rows} not supported")
+    ws = _ws(nb, g.device)
+    out = torch.empty((rows, Cc), dtype=torch.float32, device=g.device)
+    _lib.check(L.vqvae_gather_rows_backward_f32(idx.data_ptr(), g.data_ptr(), n, Cc, rows, out.data_ptr(), ws.data_ptr(), nb, _sp(g)))
+    return out
+
+
+class _GatherFn(torch.autograd.Function):
+    """nn.Embedding: out[i] = table[idx[i]] (vqvae_gather_rows_f32), backward the segmented sum over idx."""
+
+    @staticmethod
+    def forward(ctx, idx, table):
+        ctx.save_for_backward(idx)
+        ctx.rows = table.shape[0]
+        return _gather_rows(idx, table)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, = ctx.saved_tensors
+        return None, gather_rows_backward(idx, g, ctx.rows) if ctx.needs_input_grad[1] else None
+
+
+class _RowsToNchwFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return conv_hip.rows_to_nchw(t.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        return conv_hip.nchw_to_rows(g)
+
+
+class _NchwToRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return conv_hip.nchw_to_rows(t.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        return conv_hip.rows_to_nchw(g)
+
+
+class _Conv1x1Fn(torch.autograd.Function):
+    """One 1x1 conv of the output head (models.py:111-115) on row-major activations.  relu_out: the ReLU between the two convs,
+    whose backward the next conv's data gradient applies in its epilogue (mask_input=True there)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, relu_out, mask_input):
+        x = x.detach().contiguous()
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        y = conv_hip.conv(CONV_1x1, x, mod, weight.detach(), bias.detach(), Cin, Cout, RELU_OUT if relu_out else 0)
+        ctx.save_for_backward(x, weight.detach())
+        ctx.mod, ctx.mask_input = mod, mask_input
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        Cout, Cin = w.shape[0], w.shape[1]
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = conv_hip.conv(CONVT_1x1, gy, _holder(ctx.mod, ("dgrad", CONV_1x1)), w, None, Cout, Cin, 0,
+                               mask=x if ctx.mask_input else None)
+        if ctx.needs_input_grad[1]:
+            gw = conv_wgrad(gy, x, 1, 1, 0)
+        if ctx.needs_input_grad[2]:
+            gb = bias_grad(gy)
+        return gx, gw, gb, None, None, None
+
+
+class _GatedLayerFn(torch.autograd.Function):
+    """One GatedMaskedConv2d (models.py:64-84) after its class embedding's gather: (x_v, x_h, cond) -> (out_v, out_h), row-major.
+    Backward, given g_out_v and g_out_h:
+      horiz_resid    g_out = W_hr^T g_out_h;  its weight / bias gradients;  residual: g_out_h passes on to x_h
+      gate 2         g_pre2 = gate'(v2h + cond) g_out;  g_cond = per-image sums of g_pre2
+      gate 1         g_pre1 = gate'(h_vert + cond) g_out_v;  g_cond += its sums
+      vert_to_horiz  g_h_vert = W_vh^T g_pre2 + g_pre1 (the epilogue's addend);  gradients from (g_pre2, h_vert)
+      horiz_stack    g_x_h = taps^T g_pre2 (+ g_out_h);  gradients from (g_pre2, x_h)
+      vert_stack     g_x_v = taps^T g_h_vert (+ g_x_h where both stacks read one tensor);  gradients from (g_h_vert, x_v)"""
+
+    @staticmethod
+    def forward(ctx, x_v, x_h, cond, layer, same, *params):
+        x_v, x_h, cond = x_v.detach().contiguous(), x_h.detach().contiguous(), cond.detach()
+        out_v, out_h, h_vert, v2h, out = layer._forward_parts(x_v, x_h, cond)
+        ctx.save_for_backward(x_v, x_h, cond, h_vert, v2h, out)
+        ctx.layer, ctx.same = layer, same
+        ctx.set_materialize_grads(False)
+        return out_v, out_h
+
+    @staticmethod
+    def backward(ctx, g_ov, g_oh):
+        x_v, x_h, cond, h_vert, v2h, out = ctx.saved_tensors
+        L, dim = ctx.layer, ctx.layer.dim
+        vs, vh, hs, hr = L.vert_stack, L.vert_to_horiz, L.horiz_stack, L.horiz_resid
+        if g_oh is None:
+            g_oh = torch.zeros_like(out)
+        g_oh = g_oh.contiguous()
+        g_out = conv_hip.conv(CONVT_1x1, g_oh, _holder(L, ("dgrad", "horiz_resid")), hr.weight.detach(), None, dim, dim, 0)
+        gw_hr, gb_hr = conv_wgrad(g_oh, out, 1, 1, 0), bias_grad(g_oh)
+        B = x_v.shape[0]
+        g_cond = torch.empty((B, 2 * dim), dtype=torch.float32, device=x_v.device)
+        g_pre2 = gate_backward(v2h, cond, g_out, dim, g_cond)
+        g_pre1 = gate_backward(h_vert, cond, g_ov, dim, g_cond, accumulate=True) if g_ov is not None else None
+        g_h_vert = conv_hip.conv(CONVT_1x1, g_pre2, _holder(L, ("dgrad", "vert_to_horiz")), vh.weight.detach(), None, 2 * dim,
+                                 2 * dim, 0, addend=g_pre1)
+        gw_vh, gb_vh = conv_wgrad(g_pre2, h_vert, 1, 1, 0), bias_grad(g_pre2)
+        g_x_h = taps_dgrad(g_pre2, L, hs.weight.detach(), L._htaps, addend=g_oh if L.residual else None)
+        gw_hs, gb_hs = taps_wgrad(g_pre2, x_h, L._htaps).view_as(hs.weight), bias_grad(g_pre2)
+        g_x_v = taps_dgrad(g_h_vert, L, vs.weight.detach(), L._vtaps, addend=g_x_h if ctx.same else None)
+        gw_vs, gb_vs = taps_wgrad(g_h_vert, x_v, L._vtaps).view_as(vs.weight), bias_grad(g_h_vert)
+        return (g_x_v, None if ctx.same else g_x_h, g_cond, None, None,
+                gw_vs, gb_vs, gw_vh, gb_vh, gw_hs, gb_hs, gw_hr, gb_hr)
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, targets):
+        rows, targets = rows.detach().contiguous(), targets.contiguous().view(-1)
+        N, K = rows.shape
+        L = _lib.load()
+        nb = L.vqvae_cross_entropy_workspace_bytes(N)
+        ws = _ws(nb, rows.device)
+        loss = torch.empty((), dtype=torch.float32, device=rows.device)
+        _lib.check(L.vqvae_cross_entropy_f32(rows.data_ptr(), targets.data_ptr(), N, K, loss.data_ptr(), ws.data_ptr(), nb, _sp(rows)))
+        ctx.save_for_backward(rows, targets)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, targets = ctx.saved_tensors
+        N, K = rows.shape
+        g = g.detach().reshape(1).contiguous()
+        gx = torch.empty_like(rows)
+        _lib.check(_lib.load().vqvae_cross_entropy_backward_f32(rows.data_ptr(), targets.data_ptr(), N, K, g.data_ptr(), gx.data_ptr(),
+                                                                _sp(rows)))
+        return gx, None
+
+
+def cross_entropy(logits, x):
+    """nn.CrossEntropyLoss()(logits.permute(0, 2, 3, 1).contiguous().view(-1, K), x.view(-1)) of gated_pixelcnn.py:91-96 on the HIP
+    kernels: logits (B, K, H, W) as GatedPixelCNN.forward returns them, x (B, H, W) int64 -> 0-dim loss, differentiable.
+    Max-subtracted log-sum-exp per row, fixed-order mean; targets outside [0, K) give NaN."""
+    if not logits.is_cuda or logits.dtype != torch.float32 or x.dtype != torch.int64:
+        raise VqvaeHipError("cross_entropy needs CUDA(HIP) float32 logits and int64 targets: there is no CPU path")
+    B, K, H, W = logits.shape
+    if tuple(x.shape) != (B, H, W):
+        raise ValueError(f"targets of shape {tuple(x.shape)} do not match logits {tuple(logits.shape)}")
+    rows = _NchwToRowsFn.apply(logits.contiguous()).view(-1, K)
+    return _CrossEntropyFn.apply(rows, x)
+
+
 class GatedMaskedConv2d(nn.Module):
     """Mirrors pixelcnn/models.py:29-84."""
 
@@ -122,8 +380,12 @@ class GatedMaskedConv2d(nn.Module):
         """x_v, x_h row-major (B,H,W,dim); label (B,) int64 -> (out_v, out_h) row-major."""
         if self.mask_type == 'A':
             self.make_causal()
-        dim = self.dim
         cond = _gather_rows(label, self.class_cond_embedding.weight)                       # :68
+        return self._forward_parts(x_v, x_h, cond)[:2]
+
+    def _forward_parts(self, x_v, x_h, cond):
+        """The layer after the class embedding's gather -> (out_v, out_h, h_vert, v2h, out): the outputs and what backward reads."""
+        dim = self.dim
         h_vert = self._masked(x_v, self.vert_stack, self._vtaps, "vert")                   # :69-70
         out_v = _gate(h_vert, None, cond, dim)                                              # :71
         h_horiz = self._masked(x_h, self.horiz_stack, self._htaps, "horiz")                # :73-74
@@ -134,10 +396,23 @@ class GatedMaskedConv2d(nn.Module):
         # :78-79  the horizontal residual in the 1x1 conv's epilogue
         out_h = conv_hip.conv(CONV_1x1, out, self.horiz_resid, self.horiz_resid.weight, self.horiz_resid.bias, dim,
                               dim, 0, addend=x_h.contiguous() if self.residual else None)
-        return out_v, out_h
+        return out_v, out_h, h_vert, v2h, out
+
+    def train_rows(self, x_v, x_h, label):
+        """forward_rows under autograd: the same launches, with what backward needs kept (_GatedLayerFn)."""
+        if self.mask_type == 'A':
+            self.make_causal()                                   # before the weights are handed to the Function
+        cond = _GatherFn.apply(label.contiguous().view(-1), self.class_cond_embedding.weight)
+        same = x_v is x_h                                        # the first layer: both stacks read the embedded input
+        ps = (self.vert_stack.weight, self.vert_stack.bias, self.vert_to_horiz.weight, self.vert_to_horiz.bias,
+              self.horiz_stack.weight, self.horiz_stack.bias, self.horiz_resid.weight, self.horiz_resid.bias)
+        return _GatedLayerFn.apply(x_v, x_h, cond, self, same, *ps)
 
     def forward(self, x_v, x_h, h):
         """NCHW boundary of the reference (models.py:64-84)."""
+        if _autograd_wanted(self):
+            ov, oh = self.train_rows(_NchwToRowsFn.apply(x_v), _NchwToRowsFn.apply(x_h), h)
+            return _RowsToNchwFn.apply(ov), _RowsToNchwFn.apply(oh)
         ov, oh = self.forward_rows(conv_hip.nchw_to_rows(x_v), conv_hip.nchw_to_rows(x_h), h)
         return conv_hip.rows_to_nchw(ov), conv_hip.rows_to_nchw(oh)
 
@@ -158,12 +433,33 @@ class GatedPixelCNN(nn.Module):
         self.output_conv = nn.Sequential(nn.Conv2d(dim, 512, 1), nn.ReLU(True), nn.Conv2d(512, input_dim, 1))
         self.apply(weights_init)
 
-    @torch.no_grad()
     def forward(self, x, label):
+        if _autograd_wanted(self):
+            return self._forward_train(x, label)
+        with torch.no_grad():
+            return self._forward_eval(x, label)
+
+    def _check(self, x):
         if not x.is_cuda or x.dtype != torch.int64:
             raise VqvaeHipError("GatedPixelCNN.forward needs CUDA(HIP) int64 indices: there is no CPU path")
         if self.dim % 4:
             raise VqvaeHipError("dim must be a multiple of 4 for the HIP kernels")
+
+    def _forward_train(self, x, label):
+        """forward under autograd: the launches of _forward_eval, each layer an autograd.Function with a HIP backward."""
+        self._check(x)
+        B, H, W = x.shape
+        t = _GatherFn.apply(x.contiguous().view(-1), self.embedding.weight).view(B, H, W, self.dim)
+        x_v, x_h = t, t
+        for layer in self.layers:
+            x_v, x_h = layer.train_rows(x_v, x_h, label)
+        c0, c2 = self.output_conv[0], self.output_conv[2]
+        t = _Conv1x1Fn.apply(x_h, c0.weight, c0.bias, c0, True, False)
+        t = _Conv1x1Fn.apply(t, c2.weight, c2.bias, c2, False, True)
+        return _RowsToNchwFn.apply(t)
+
+    def _forward_eval(self, x, label):
+        self._check(x)
         B, H, W = x.shape
         t = _gather_rows(x, self.embedding.weight).view(B, H, W, self.dim)                  # :119-121
         x_v, x_h = t, t
