@@ -461,6 +461,38 @@ VQVAE_API size_t vqvae_bias_grad_wide_workspace_bytes(int C);
 VQVAE_API int vqvae_bias_grad_wide_f32(const float *grad_y, int64_t P, int C, float *grad_b, void *workspace, size_t workspace_bytes,
                                        vqvae_stream_t stream);
 
+/* ------------------------------------------------------- GatedPixelCNN prior: cached sampler (csrc/pixelcnn_sample.hip)
+ * GatedPixelCNN.generate (pixelcnn/models.py:129-142) without its H*W full forwards.  The prior is causal, so the sampler keeps each
+ * layer's state and computes only what the next pixel needs: per row, the vertical stacks (hv_L, out_v) and vert_to_horiz of every
+ * layer and column; per position, the horizontal stacks (out_h) of every layer, the output head, and one draw.  One workgroup per
+ * image loops over the whole map; nothing is shared between images, nothing synchronises across workgroups.  fp32 products with
+ * fp32 accumulation (fmaf chains); the gate is vqvae_gated_activation_f32's expression in the reference's order of sums.
+ *
+ * Supported (VQVAE_ERR_UNSUPPORTED otherwise): GatedPixelCNN's own structure (layer 0: k = 7, mask 'A', no residual; the others:
+ * k = 3, mask 'B'; output head 512 wide); dim % 4 == 0 and dim <= 256; 2 <= K <= 8192; any n_classes >= 1 and n_layers >= 1;
+ * square maps H = W from 1 to 128 (the reference's crops :70, :74 only make sense for square maps); packed image and workspace
+ * 16-byte aligned.
+ *
+ * vqvae_pixelcnn_sample_pack_f32 -- writes every parameter into the caller-owned sampler image (vqvae_pixelcnn_sample_packed_bytes;
+ *   0 = unsupported).  params: a HOST array of 9 n_layers + 5 device pointers in GatedPixelCNN.named_parameters() order:
+ *   embedding.weight; per layer class_cond_embedding.weight, vert_stack.{weight,bias}, vert_to_horiz.{weight,bias},
+ *   horiz_stack.{weight,bias}, horiz_resid.{weight,bias}; output_conv.0.{weight,bias}, output_conv.2.{weight,bias}.  The taps
+ *   make_causal zeroes are never read and not packed.
+ * vqvae_pixelcnn_sample_f32 -- label (B,) int64 (clamped into [0, n_classes) like vqvae_gather_rows_f32), uniforms (B, H, W) fp32
+ *   in [0, 1) -> samples (B, H, W) int64; logits (B, K, H, W), the NCHW logits each position was drawn from (may be NULL);
+ *   status (B,) int32, 0 or VQVAE_SAMPLE_* bits.  The draw: m = max l, e_k = exp(l_k - m), C_k the running sums of e_k in ascending
+ *   k (a fixed order), S = C_{K-1}; the code is the smallest k with u S < C_k, or, where rounding leaves none, the largest k with
+ *   e_k > 0.  A position whose logits are not all finite sets VQVAE_SAMPLE_NONFINITE and that image gets code 0 from there on.
+ *   workspace: vqvae_pixelcnn_sample_workspace_bytes (0 = unsupported), never read before the call writes it.                    */
+#define VQVAE_SAMPLE_NONFINITE 1
+VQVAE_API size_t vqvae_pixelcnn_sample_packed_bytes(int K, int dim, int n_layers, int n_classes);
+VQVAE_API int vqvae_pixelcnn_sample_pack_f32(const float *const *params, int n_params, int K, int dim, int n_layers, int n_classes,
+                                             void *packed, size_t packed_bytes, vqvae_stream_t stream);
+VQVAE_API size_t vqvae_pixelcnn_sample_workspace_bytes(int64_t B, int H, int W, int dim, int n_layers);
+VQVAE_API int vqvae_pixelcnn_sample_f32(const void *packed, size_t packed_bytes, const int64_t *label, const float *uniforms, int64_t B,
+                                        int H, int W, int K, int dim, int n_layers, int n_classes, int64_t *samples, float *logits,
+                                        int32_t *status, void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* ------------------------------------------------------------------- whole path
  * models/vqvae.py:29-44 as ONE call: Encoder (models/encoder.py:28-43) -> pre_quantization_conv (models/vqvae.py:33)
  * -> VectorQuantizer (models/quantizer.py:45-76) -> Decoder (models/decoder.py:27-39).  The caller owns every buffer:

@@ -124,6 +124,10 @@ SIGNATURES = {
     "vqvae_cross_entropy_backward_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "vqvae_bias_grad_wide_workspace_bytes": (_sz, [_i32]),
     "vqvae_bias_grad_wide_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "vqvae_pixelcnn_sample_packed_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "vqvae_pixelcnn_sample_pack_f32": (_i32, [C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "vqvae_pixelcnn_sample_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "vqvae_pixelcnn_sample_f32": (_i32, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@ initialisation as the reference, so a PixelCNN checkpoint written by `pixelcnn/g
     GatedPixelCNN(input_dim=256, dim=64, n_layers=15, n_classes=10)
         .forward(x (B,H,W) int64, label (B,) int64) -> logits (B, input_dim, H, W)          (models.py:118-127)
         .generate(label, shape=(8, 8), batch_size=64) -> (B, *shape) int64                   (models.py:129-142)
+        .generate_cached(label, shape, batch_size, *, uniforms, generator, return_logits)   the same draw, one cached kernel
 
 Activations are row-major (B,H,W,C); a masked convolution is a stride-1 convolution over its causal tap list
 (round 4: vqvae_conv_taps_forward_f32 -- the conv path's kernels with an explicit tap list, no im2col pass; lists of more than
@@ -24,6 +25,10 @@ vqvae_conv_wgrad_ex_f32, the gated activation's backward with the class-conditio
 for both embeddings.  No floating-point atomics: two backward passes give the same bits.  `cross_entropy` is the HIP form of the
 reference's criterion.  Every other case (eval mode, torch.no_grad(), generate, the hipGraph sampler) runs the forward-only path.
 No CPU path, no fallback.
+
+Sampling (csrc/pixelcnn_sample.hip).  `generate_cached` keeps each layer's state and computes only what the next pixel needs: per
+row the vertical stacks of every layer, per position the horizontal stacks, the head and one draw -- one kernel, one workgroup per
+image.  `sample_images` decodes its maps with VQVAE.decode_indices.
 """
 from __future__ import annotations
 
@@ -500,3 +505,95 @@ class GatedPixelCNN(nn.Module):
                 probs = torch.softmax(logits[:, :, i, j], -1)
                 x[:, i, j].copy_(probs.multinomial(1).squeeze(-1))
         return x
+
+    def _sampler_image(self):
+        """The cached sampler's packed image (vqvae_pixelcnn_sample_pack_f32), kept in the module's side table and keyed on every
+        parameter's (data_ptr, _version, device, shape).  make_causal runs first, as in the reference's generate; its in-place write
+        bumps the mask-A weights' versions on every call, so the key is taken BEFORE it and stored with the versions AFTER it: a
+        parameter changed between two calls (an optimizer step, load_state_dict, an in-place edit) misses, make_causal alone does
+        not.  The masked taps are never packed, so a `.data` write to them cannot make the image stale."""
+        params = list(self.parameters())
+
+        def key():
+            return tuple((p.data_ptr(), p._version, str(p.device), tuple(p.shape)) for p in params)
+
+        before = key()
+        self.layers[0].make_causal()
+        side = _cache.side(self)
+        hit = side.get("sampler_image")
+        L = _lib.load()
+        p0 = params[0]
+        if hit is not None and hit[0] == before:
+            img, mark = hit[1], hit[2]
+            _cache.wait_ready(mark, p0.device)
+        else:
+            K, dim, n_layers = self.embedding.num_embeddings, self.dim, len(self.layers)
+            n_classes = self.layers[0].class_cond_embedding.num_embeddings
+            nb = L.vqvae_pixelcnn_sample_packed_bytes(K, dim, n_layers, n_classes)
+            if nb == 0:
+                raise VqvaeHipError(f"cached sampler: K={K}, dim={dim}, n_layers={n_layers} not supported")
+            img = _ws(nb, p0.device)
+            keep = [p.detach().contiguous() for p in params]             # alive until the pack launches are queued
+            ptrs = (C.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+            _lib.check(L.vqvae_pixelcnn_sample_pack_f32(ptrs, len(params), K, dim, n_layers, n_classes, img.data_ptr(), nb,
+                                                        _sp(p0)))
+            mark = _cache.mark_ready(p0.device)
+        side["sampler_image"] = (key(), img, mark)
+        return img
+
+    @torch.no_grad()
+    def generate_cached(self, label, shape=(8, 8), batch_size=64, *, uniforms=None, generator=None, return_logits=False):
+        """models.py:129-142 on the cached sampler (csrc/pixelcnn_sample.hip): one kernel that keeps every layer's state and computes
+        only what each next pixel needs, instead of one full forward per position.
+
+        label (batch_size,) int64 on the module's device; shape = (H, W) with H == W.  uniforms (batch_size, H, W) fp32 in [0, 1)
+        drive the draws (drawn with torch.rand(generator=generator) when not given): position (y, x) takes the smallest code k
+        whose running sum of exp(l - max l) exceeds u times the total.  Returns the (batch_size, H, W) int64 codes and, with
+        return_logits, also the (batch_size, K, H, W) logits each position was drawn from.  Like generate, it leaves the mask-A
+        taps zeroed.  Raises VqvaeHipError for CPU tensors, non-square or unsupported shapes and non-finite logits."""
+        p0 = self.embedding.weight
+        if not p0.is_cuda or not torch.is_tensor(label) or not label.is_cuda:
+            raise VqvaeHipError("generate_cached needs the module and label on a CUDA(HIP) device: there is no CPU path")
+        H, W = (int(s) for s in shape)
+        if H != W:
+            raise VqvaeHipError(f"generate_cached samples square maps only, got {H} x {W}")
+        B = int(batch_size)
+        dev = p0.device
+        label = label.to(device=dev, dtype=torch.int64).contiguous()
+        if label.shape != (B,):
+            raise ValueError(f"label must have shape ({B},), got {tuple(label.shape)}")
+        if self.output_conv[0].weight.shape[0] != 512:
+            raise VqvaeHipError("cached sampler: the output head must be 512 wide, as GatedPixelCNN builds it")
+        K, dim, n_layers = self.embedding.num_embeddings, self.dim, len(self.layers)
+        n_classes = self.layers[0].class_cond_embedding.num_embeddings
+        L = _lib.load()
+        nws = L.vqvae_pixelcnn_sample_workspace_bytes(B, H, W, dim, n_layers)
+        if nws == 0 or L.vqvae_pixelcnn_sample_packed_bytes(K, dim, n_layers, n_classes) == 0:
+            raise VqvaeHipError(f"cached sampler: B={B}, {H} x {W}, K={K}, dim={dim}, n_layers={n_layers} not supported")
+        with torch.cuda.device(dev):
+            img = self._sampler_image()
+            if uniforms is None:
+                uniforms = torch.rand((B, H, W), generator=generator, device=dev)
+            elif not uniforms.is_cuda or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (B, H, W):
+                raise VqvaeHipError(f"uniforms must be a CUDA(HIP) float32 tensor of shape ({B}, {H}, {W})")
+            uniforms = uniforms.to(dev).contiguous()
+            out = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+            logits = torch.empty((B, K, H, W), dtype=torch.float32, device=dev) if return_logits else None
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            ws = _ws(nws, dev)
+            _lib.check(L.vqvae_pixelcnn_sample_f32(img.data_ptr(), img.numel(), label.data_ptr(), uniforms.data_ptr(), B, H, W, K, dim,
+                                                   n_layers, n_classes, out.data_ptr(),
+                                                   logits.data_ptr() if logits is not None else None, status.data_ptr(),
+                                                   ws.data_ptr(), nws, _sp(out)))
+            bad = int((status != 0).sum())
+        if bad:
+            raise VqvaeHipError(f"cached sampler: non-finite logits in {bad} of {B} images (status VQVAE_SAMPLE_NONFINITE)")
+        return (out, logits) if return_logits else out
+
+
+def sample_images(prior, vqvae, label, shape=(8, 8), batch_size=64, **kw):
+    """The reference pipeline's last step: latent maps sampled from the prior (GatedPixelCNN.generate_cached, keyword arguments
+    passed on) decoded by the VQ-VAE (VQVAE.decode_indices) -> (indices (B, H, W) int64, x_hat (B, C, 4 H, 4 W))."""
+    idx = prior.generate_cached(label, shape, batch_size, **kw)
+    H, W = idx.shape[1], idx.shape[2]
+    return idx, vqvae.decode_indices(idx, batch_size, H, W)
