@@ -177,6 +177,34 @@ def test_host_side_plans_without_gpu():
     assert L.vqvae_workspace_bytes(dims, 4096, 30, 32) == 0
 
 
+def test_dispatch_table_unchanged():
+    """Every kernel-selection query answer recorded in tests/golden/dispatch_table.json (tools/gen_golden_dispatch.py): which
+    quantizer kernel, sweep count, launch form and template instance; quantizer and whole-path workspace sizes; conv term products.
+    Launch forms assume 256 CUs without a device."""
+    import itertools
+    import json
+    from vqvae_amd import _lib
+    L = _lib.load()
+    t = json.load(open(os.path.join(ROOT, "tests", "golden", "dispatch_table.json")))
+    g = t["grid"]
+    for (K, D, f), (name, sweeps) in zip(itertools.product(g["K"], g["D"], g["vq_flags"]), t["vq"], strict=True):
+        assert (_lib.vq_kernel_name(K, D, f), _lib.vq_sweeps(K, D, f)) == (t["names"][name], sweeps), (K, D, hex(f))
+    forms = {e[0]: e[1:] for e in t["vq_forms"]}
+    for i, (n, K, D, HW, f) in enumerate(itertools.product(g["rows"], g["K"], g["D"], g["HW"], g["vq_flags"])):
+        want = forms.get(i)
+        assert _lib.vq_launch_form(n, K, D, HW, f) == (tuple(want[:3]) if want else None), (n, K, D, HW, hex(f))
+        if want:
+            assert _lib.vq_kernel_instance(n, K, D, HW, f) == t["instances"][want[3]], (n, K, D, HW, hex(f))
+    for (K, D), ws in zip(itertools.product(g["K"], g["D"]), t["vq_ws"], strict=True):
+        assert L.vqvae_vq_workspace_bytes(1000, K, D) == ws, (K, D)
+    for (k, hw, ch, f), p in zip(itertools.product(g["conv_kind"], g["conv_map"], g["conv_ch"], g["conv_flags"]), t["conv"],
+                                 strict=True):
+        assert L.vqvae_conv_term_products(k, hw[0], hw[1], ch[0], ch[1], f) == p, (k, hw, ch, hex(f))
+    for (dm, (B, H, W)), ws in zip(itertools.product(g["model_dims"], g["model_shape"]), t["model_ws"], strict=True):
+        d = _lib.VqvaeDims(*dm, 0.25)
+        assert [L.vqvae_workspace_bytes(d, B, H, W), L.vqvae_workspace_ze_offset(d, B, H, W)] == ws, (dm, B, H, W)
+
+
 def test_modules_pickle_and_deepcopy_like_the_reference(tmp_path):
     """The reference's VQVAE is a plain nn.Module: torch.save(model) and copy.deepcopy(model) (EMA copies,
     checkpoint-by-module) work.  Runtime caches live in a weak side table (vqvae_amd/_cache.py), never in __dict__."""

@@ -57,10 +57,8 @@ struct VqPlan {
     int K_pad;        // nchunks * KC
     size_t off_flags, off_ee, off_img, off_partials, off_img16, off_neh, off_imgh, off_seeds, off_imgf, off_chunk, total;
     size_t lds_bytes;
-    // filter-and-refine kernel (bf16 screening): usable when the whole bf16 image fits LDS
-    bool filter_ok;
     int K32;                 // K rounded up to 32
-    size_t filter_lds_bytes;
+    size_t filter_lds_bytes; // LDS of the filter-and-refine kernel (bf16 screening)
 };
 constexpr int kVqCandCap = 8;   // per lane half (16 per row), unsigned short entries   // candidate list capacity per row in the filter kernel
 constexpr int kVqTilesPerWave = 2;   // 32-row tiles a wave of the filter kernel walks per iteration
@@ -72,6 +70,19 @@ constexpr int kVqGroupSlabs = 16;    // slabs whose open / hard rows are resolve
 bool vq_track_ok(int K, int D);          // vq_track.hip: the codebook's fp16 image fits LDS next to four waves' 32-row tiles (D = 64, K <= 1024; row-major rows)
 bool vq_chunk_ok(int K, int D);
 size_t vq_chunk_scratch_bytes(int D);
+
+// LDS of the filter kernel: bf16 image + (-||e||^2/2) + histogram + per-wave candidate lists + scratch
+inline size_t vq_filter_lds_bytes(int K, int D) {
+    const size_t K32 = ((size_t)K + 31) / 32 * 32;
+    return K32 * D * 2 + K32 * 4 + (size_t)K * 4 + kVqTilesPerWave * (8 * 32 * 2 * kVqCandCap * 2 + 8 * 96 * 4) + 256 + 8;
+}
+
+// Which quantizer kernel runs for a problem (vq_exact.hip): the one place that decides it.  HW = pixels per image (NCHW rows only).
+// Track / TrackNchw: vq_track_kernel_d64 on row-major / NCHW rows (single-sweep fp16 screen, codebook image resident in LDS); Chunk:
+// vq_stream_sweep_kernel (the same screen, image streamed through LDS); Filter: vq_filter_kernel_d64 (two-sweep bf16); Exact:
+// vq_exact_kernel (exhaustive fp32 MFMA sweep); AnyD / GenericVector: other widths, vq_anyd_kernel / vq_generic_kernel (vq_generic.hip)
+enum class VqRoute { Track, TrackNchw, Chunk, Filter, Exact, AnyD, GenericVector, Unsupported };
+VqRoute vq_route(int K, int D, int HW, int flags);
 
 inline VqPlan vq_plan(int K, int D) {
     VqPlan p;
@@ -102,11 +113,8 @@ inline VqPlan vq_plan(int K, int D) {
     p.off_imgf = align_up(p.off_seeds + (size_t)p.K32 * 4 + 4096, 256);
     p.off_chunk = align_up(p.off_imgf + (size_t)(p.K32 + 512) * D * 2, 256);
     // row scratch of the streamed-codebook kernels: only where they are the default path
-    p.total = p.off_chunk + ((vq_chunk_ok(K, D) && !vq_track_ok(K, D)) ? vq_chunk_scratch_bytes(D) : 0);
-    // LDS of the filter kernel: bf16 image + (-||e||^2/2) + histogram + per-wave candidate lists + scratch
-    p.filter_lds_bytes = (size_t)p.K32 * D * 2 + (size_t)p.K32 * 4 + (size_t)K * 4 +
-                         kVqTilesPerWave * (8 * 32 * 2 * kVqCandCap * 2 + 8 * 96 * 4) + 256 + 8;
-    p.filter_ok = (D == 64) && p.filter_lds_bytes <= (size_t)kLdsBytes;
+    p.total = p.off_chunk + (vq_route(K, D, 0, VQVAE_VQ_ROWMAJOR) == VqRoute::Chunk ? vq_chunk_scratch_bytes(D) : 0);
+    p.filter_lds_bytes = vq_filter_lds_bytes(K, D);
     return p;
 }
 
@@ -139,6 +147,8 @@ int launch_vq_chunked(const float *z, const float *cb, long long N, int K, int D
 int conv_forward_impl(int kind, const float *x, const float *packed, const float *bias, int64_t B, int H, int W, int Cin,
                       int Cout, int flags, float *y, hipStream_t stream, const int *in_amax, int *out_amax,
                       const float *ep_add = nullptr, const float *ep_mask = nullptr);   // vqvae_conv_forward_ep_f32
+// does the layer's kernel, handed its images' maxima (the whole-path entry points), need them -- or does it measure each image itself
+bool conv_reads_amax(int kind, int H, int W, int Cin, int Cout, int flags);
 int res_layer_forward_impl(const float *x, const float *packed_w1, const float *packed_w2, int64_t B, int H, int W, int C,
                            int Rh, int flags, float *y, hipStream_t stream, const int *in_amax, int *out_amax,
                            float *hidden = nullptr, float *hid_scratch = nullptr);
@@ -180,7 +190,7 @@ size_t vq_generic_workspace_bytes(int K, int D);
 int launch_vq_generic(const float *z, const float *cb, long long N, int HW, int K, int D, float beta, bool rowmajor, float *zq,
                       long long *idx, int *hist, float *loss, float *ppl, char *ws, hipStream_t st, bool hist_zeroed,
                       bool vector_units = false, bool prepared = false);
-bool vq_fuse_ok(int K, int D, int64_t B, int flags);
+bool vq_fuse_ok(int K, int D, int flags);     // the quantizer inside the encoder's last kernel takes this codebook and these flags
 int vq_prepare_impl(const float *codebook, int K, int D, int flags, void *workspace, size_t workspace_bytes, hipStream_t st);
 VqFuse vq_fuse_args(const float *codebook, int K, void *workspace, float *z_q, int64_t *idx, int32_t *hist);
 int vq_finalize_impl(const double *partials, int grid, int32_t *hist, int K, int64_t n_rows, int D, float beta, float *loss,

@@ -1288,13 +1288,11 @@ int vqvae_conv_pack_f32(int kind, const float *w, int Cin, int Cout, float *pack
 int vqvae_conv_term_products(int kind, int H, int W, int Cin, int Cout, int flags) {
     ConvGeom g;
     if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || make_geom(kind, 1, H, W, Cin, Cout, flags, g) != VQVAE_OK) return 0;
-    if (flags & VQVAE_CONV_EXACT_FP32) return 1;
-    const bool tile8 = g.Hin == 8 && g.Win == 8 && g.istride == 1 && g.Hg == 8 && g.Wg == 8 && Cin % 32 == 0 && g.ntile % 2 == 0;
-    const bool s2d = !tile8 && kind == VQVAE_CONV_4x4_S2 && g.Hin == 16 && g.Win == 16 && Cin % 32 == 0 && g.ntile % 2 == 0;
     // VQVAE_CONV_QUERY_WHOLE_PATH: as launched by vqvae_forward_f32 / _encoder_f32 / _decoder_f32, which hand every layer its
     // images' maxima -- the generic kernels then run the two-term fp16 products on every map size (conv_forward_impl)
-    const bool handed = flags & VQVAE_CONV_QUERY_WHOLE_PATH;
-    return ((tile8 || s2d || handed) && !(flags & VQVAE_CONV_BF16_SPLIT)) ? 3 : 6;
+    const ConvRoute r = conv_route(kind, g, Cin, flags, flags & VQVAE_CONV_QUERY_WHOLE_PATH);
+    if (r == ConvRoute::Exact) return 1;
+    return (r == ConvRoute::IgemmBf3 || ((r == ConvRoute::Tile8 || r == ConvRoute::Tile8S2d) && (flags & VQVAE_CONV_BF16_SPLIT))) ? 6 : 3;
 }
 
 int vqvae_conv_forward_f32(int kind, const float *x, const float *packed, const float *bias, int64_t B,
@@ -1383,30 +1381,29 @@ int vqvae::conv_forward_impl(int kind, const float *x, const float *packed, cons
     g.ep_mask = ep_mask;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long M = (long long)B * g.Hg * g.Wg;
+    const ConvRoute route = conv_route(kind, g, Cin, flags, in_amax != nullptr);
+    // the weight images of the 16-bit product kernels: three-term bf16 (img3), the header {kw} and the two-term fp16 image behind it
+    const u32x4 *img3 = reinterpret_cast<const u32x4 *>(packed + packed_floats(g));
+    const char *h2base = reinterpret_cast<const char *>(packed) + packed_h2_offset(g, kind);
+    const int *whdr = reinterpret_cast<const int *>(h2base);
+    const u32x4 *img2 = reinterpret_cast<const u32x4 *>(h2base + h2_header_bytes(g.ntile));
     prof_begin(VQVAE_PROF_CONV_IGEMM, st);
-    if (!(flags & VQVAE_CONV_EXACT_FP32)) {
-        // default: split-bf16 products on the bf16 matrix cores (fp32-grade accuracy, ~2.7x the rate)
-        const u32x4 *img3 = reinterpret_cast<const u32x4 *>(packed + packed_floats(g));
-        const unsigned gx = (unsigned)((M + 127) / 128);
-        const bool tile8 = g.Hin == 8 && g.Win == 8 && g.istride == 1 && g.Hg == 8 && g.Wg == 8 && Cin % 32 == 0 && g.ntile % 2 == 0;
-        // 16x16 -> 8x8 (4x4 s2): the same kernel over 2x2 input blocks, weights in the s2d chunk order (third image)
-        const bool S2D_ = !tile8 && kind == VQVAE_CONV_4x4_S2 && g.Hin == 16 && g.Win == 16 && Cin % 32 == 0 && g.ntile % 2 == 0;
-        if (tile8 || S2D_)
-        {
+    switch (route) {
+        case ConvRoute::Tile8: case ConvRoute::Tile8S2d: {
             // whole 8x8 input images per wave: operands split once per chunk and kept in LDS for all taps.  With four
             // output tiles per wave (all 128 channels: the image is read and split once) the workgroup has eight
             // waves, so that its weight chunks (2 x 24 KiB) and eight operand tiles still fit one CU's LDS.
             // ... unless that leaves most of the chip without a workgroup (round 4: the prior's sampler runs these layers at
             // B = 64): below one eight-wave workgroup per CU the four-wave form, two channel halves per image, spreads the same
             // images over four times the workgroups
+            // (16x16 -> 8x8, 4x4 s2: the same kernel over 2x2 input blocks, weights in the s2d chunk order -- the third image)
+            const bool S2D_ = route == ConvRoute::Tile8S2d;
             const long long wg_wide = ((B + 7) / 8) * (S2D_ ? 1 : g.nphase) * (g.ntile / 4);
             const bool wide = g.ntile % 4 == 0 && wg_wide >= num_cus();
             const int ny = (S2D_ ? 1 : g.nphase) * (g.ntile / (wide ? 4 : 2));
             const unsigned gxt = (unsigned)((B + (wide ? 7 : 3)) / (wide ? 8 : 4)) * ny;
             const bool h2 = !(flags & VQVAE_CONV_BF16_SPLIT);
-            const char *h2base = reinterpret_cast<const char *>(packed) + packed_h2_offset(g, kind);
-            const int *whdr = reinterpret_cast<const int *>(h2base);
-            const u32x4 *wsel = h2 ? reinterpret_cast<const u32x4 *>(h2base + h2_header_bytes(g.ntile) + (S2D_ ? packed_h2_bytes(g) : 0))
+            const u32x4 *wsel = h2 ? (S2D_ ? img2 + packed_h2_bytes(g) / sizeof(u32x4) : img2)
                                    : (S2D_ ? img3 + packed_bf3_bytes(g) / sizeof(u32x4) : img3);
 #define TILE8_LAUNCH(NT_, S2D__, NW_, H2_, THREADS_)                                                                   \
     hipLaunchKernelGGL((conv_tile8_bf3_kernel<NT_, S2D__, NW_, 2, H2_>), dim3(gxt), dim3(THREADS_), 0, st, x, wsel, bias, y, \
@@ -1419,27 +1416,23 @@ int vqvae::conv_forward_impl(int kind, const float *x, const float *packed, cons
                 else      { if (h2) TILE8_LAUNCH(2, false, 4, true, 256); else TILE8_LAUNCH(2, false, 4, false, 256); }
             }
 #undef TILE8_LAUNCH
+            break;
         }
-        else if (in_amax && kind == VQVAE_CONV_4x4_S2 && !(flags & VQVAE_CONV_BF16_SPLIT) && g.Hg % 8 == 0 && g.Wg % 8 == 0 &&
-                 g.Hg * g.Wg > 64 && g.Hin == 2 * g.Hg && g.Win == 2 * g.Wg && Cin % 32 == 0 && g.ntile % 2 == 0 &&
-                 (long long)g.Hin * g.Win * Cin * 4 < 0x7FFFFFF0ll) {
+        case ConvRoute::HaloS2: {
             // the 4x4 stride-2 conv on larger maps: 8x8 output tiles over the grid of 2x2 input blocks, with a one-block halo
-            const char *h2base = reinterpret_cast<const char *>(packed) + packed_h2_offset(g, kind);
-            const int *whdr = reinterpret_cast<const int *>(h2base);
-            const u32x4 *wsel = reinterpret_cast<const u32x4 *>(h2base + h2_header_bytes(g.ntile) + packed_h2_bytes(g));      // space-to-depth chunk order
+            const u32x4 *wsel = img2 + packed_h2_bytes(g) / sizeof(u32x4);      // space-to-depth chunk order
             const bool wide = g.ntile % 4 == 0;
             const long long tiles = (long long)B * (g.Hg / 8) * (g.Wg / 8);
             const int ny = g.nphase * (wide ? g.ntile / 4 : g.ntile / 2);
             const unsigned gxt = (unsigned)((tiles + 3) / 4) * ny;
             if (wide) hipLaunchKernelGGL((conv_halo8_h2_kernel<4, 2, true>), dim3(gxt), dim3(256), 0, st, x, wsel, bias, y, g, ny, whdr, in_amax, out_amax);
             else hipLaunchKernelGGL((conv_halo8_h2_kernel<2, 4, true>), dim3(gxt), dim3(256), 0, st, x, wsel, bias, y, g, ny, whdr, in_amax, out_amax);
+            break;
         }
-        else if (conv_halo8_ok(g, Cin, flags) && in_amax) {
+        case ConvRoute::Halo: {
             // larger maps whose grid is a multiple of 8 both ways, inside the whole-path entry points (maxima handed over):
             // 8x8 tiles with a one-pixel halo, one per wave (conv_halo8_h2_kernel)
-            const char *h2base = reinterpret_cast<const char *>(packed) + packed_h2_offset(g, kind);
-            const int *whdr = reinterpret_cast<const int *>(h2base);
-            const u32x4 *wsel = reinterpret_cast<const u32x4 *>(h2base + h2_header_bytes(g.ntile));
+            const u32x4 *wsel = img2;
             const bool wide = g.ntile % 4 == 0;
             const long long tiles = (long long)B * (g.Hg / 8) * (g.Wg / 8);
             // 64-channel conv-transpose phases go in pairs (one patch load / split for two phases)
@@ -1456,14 +1449,14 @@ int vqvae::conv_forward_impl(int kind, const float *x, const float *packed, cons
             else if (pairs) HALO_LAUNCH(2, 2, 2);
             else { if (wide) HALO_LAUNCH(4, 2, 1); else HALO_LAUNCH(2, 4, 1); }
 #undef HALO_LAUNCH
+            break;
         }
-        else {
+        case ConvRoute::IgemmH2: case ConvRoute::IgemmBf3: {
             // generic maps: the two-term fp16 products need every image's maximum from the producing layer (in_amax); the
             // per-layer C entry points have none and use the three-term bf16 products
-            const bool h2 = in_amax && !(flags & VQVAE_CONV_BF16_SPLIT);
-            const char *h2base = reinterpret_cast<const char *>(packed) + packed_h2_offset(g, kind);
-            const int *whdr = reinterpret_cast<const int *>(h2base);
-            const u32x4 *wsel = h2 ? reinterpret_cast<const u32x4 *>(h2base + h2_header_bytes(g.ntile)) : img3;
+            const bool h2 = route == ConvRoute::IgemmH2;
+            const u32x4 *wsel = h2 ? img2 : img3;
+            const unsigned gx = (unsigned)((M + 127) / 128);
 #define IGEMM_LAUNCH(NT_, H2_, GY_)                                                                                     \
     hipLaunchKernelGGL((conv_igemm_bf3_kernel<NT_, H2_>), dim3(gx, GY_), dim3(256), 0, st, x, wsel, bias, y, g, whdr, in_amax, \
                        out_amax)
@@ -1471,23 +1464,29 @@ int vqvae::conv_forward_impl(int kind, const float *x, const float *packed, cons
             else if (g.ntile % 2 == 0) { if (h2) IGEMM_LAUNCH(2, true, g.nphase * (g.ntile / 2)); else IGEMM_LAUNCH(2, false, g.nphase * (g.ntile / 2)); }
             else { if (h2) IGEMM_LAUNCH(1, true, g.nphase * g.ntile); else IGEMM_LAUNCH(1, false, g.nphase * g.ntile); }
 #undef IGEMM_LAUNCH
+            break;
         }
-    } else if (g.ntile % 4 == 0) {
-        // exact-fp32 MFMA kernels: 32 pixels x 128 channels per wave when Cout fills it, else 64 x 64 / 32
-        const unsigned gx = (unsigned)((M + 127) / 128);
-        hipLaunchKernelGGL((conv_igemm_kernel<1, 4>), dim3(gx, g.nphase * (g.ntile / 4)), dim3(256), 0, st, x,
-                           packed, bias, y, g);
-    } else if (g.ntile % 2 == 0) {
-        const unsigned gx = (unsigned)((M + 255) / 256);
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2>), dim3(gx, g.nphase * (g.ntile / 2)), dim3(256), 0, st, x,
-                           packed, bias, y, g);
-    } else {
-        const unsigned gx = (unsigned)((M + 255) / 256);
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 1>), dim3(gx, g.nphase * g.ntile), dim3(256), 0, st, x, packed,
-                           bias, y, g);
+        case ConvRoute::Exact:
+            // exact-fp32 MFMA kernels: 32 pixels x 128 channels per wave when Cout fills it, else 64 x 64 / 32
+            if (g.ntile % 4 == 0)
+                hipLaunchKernelGGL((conv_igemm_kernel<1, 4>), dim3((unsigned)((M + 127) / 128), g.nphase * (g.ntile / 4)), dim3(256), 0, st, x,
+                                   packed, bias, y, g);
+            else if (g.ntile % 2 == 0)
+                hipLaunchKernelGGL((conv_igemm_kernel<2, 2>), dim3((unsigned)((M + 255) / 256), g.nphase * (g.ntile / 2)), dim3(256), 0, st, x,
+                                   packed, bias, y, g);
+            else
+                hipLaunchKernelGGL((conv_igemm_kernel<2, 1>), dim3((unsigned)((M + 255) / 256), g.nphase * g.ntile), dim3(256), 0, st, x,
+                                   packed, bias, y, g);
+            break;
     }
     prof_end(VQVAE_PROF_CONV_IGEMM, st);
     return (int)hipGetLastError();
+}
+
+bool vqvae::conv_reads_amax(int kind, int H, int W, int Cin, int Cout, int flags) {
+    ConvGeom g;
+    const ConvRoute r = make_geom(kind, 1, H, W, Cin, Cout, flags, g) == VQVAE_OK ? conv_route(kind, g, Cin, flags, true) : ConvRoute::Exact;
+    return r == ConvRoute::HaloS2 || r == ConvRoute::Halo || r == ConvRoute::IgemmH2;
 }
 
 void vqvae::act_absmax_impl(const float *x, int64_t B, long long elems_per_image, int *amax, hipStream_t st) {

@@ -99,11 +99,28 @@ inline size_t h2_header_bytes(int ntile) { return 256 + (size_t)ntile * 256; }
 inline size_t packed_h2_bytes(const ConvGeom &g) {
     return (size_t)g.nphase * g.ntaps * g.cpt * g.ntile * 2048 * sizeof(unsigned short);
 }
-// conv_halo8_h2_kernel: stride-1-sampled layers on pixel grids that are multiples of 8 both ways and larger than one tile
-inline bool conv_halo8_ok(const ConvGeom &g, int Cin, int flags) {
-    return !(flags & (VQVAE_CONV_BF16_SPLIT | VQVAE_CONV_EXACT_FP32)) && g.istride == 1 && g.Hg == g.Hin && g.Wg == g.Win &&
-           g.Hg % 8 == 0 && g.Wg % 8 == 0 && g.Hg * g.Wg > 64 && Cin % 32 == 0 && g.ntile % 2 == 0 && (g.ntaps == 1 || g.ntaps == 4 || g.ntaps == 9) &&
-           (long long)g.Hin * g.Win * Cin * 4 < 0x7FFFFFF0ll;
+// Which per-layer kernel conv_forward_impl launches: the one place that decides it.  maxima_handed: the producing layer hands over
+// every image's maximum (in_amax: the whole-path entry points, model.hip); the per-layer C entry points have none.
+// Tile8: conv_tile8_bf3_kernel, whole 8x8 input images per wave (two-term fp16, or three-term bf16 with VQVAE_CONV_BF16_SPLIT);
+// Tile8S2d: the same kernel for the 4x4 s2 conv on 16x16 maps, over 2x2 input blocks; HaloS2 / Halo: conv_halo8_h2_kernel on larger
+// maps (8x8 output tiles with a halo); IgemmH2 / IgemmBf3: conv_igemm_bf3_kernel with two-term fp16 / three-term bf16 products;
+// Exact: conv_igemm_kernel (VQVAE_CONV_EXACT_FP32)
+enum class ConvRoute { Tile8, Tile8S2d, HaloS2, Halo, IgemmH2, IgemmBf3, Exact };
+inline ConvRoute conv_route(int kind, const ConvGeom &g, int Cin, int flags, bool maxima_handed) {
+    if (flags & VQVAE_CONV_EXACT_FP32) return ConvRoute::Exact;
+    const bool split = flags & VQVAE_CONV_BF16_SPLIT;
+    const bool fits = (long long)g.Hin * g.Win * Cin * 4 < 0x7FFFFFF0ll;          // (32-bit offsets inside an image)
+    if (g.Hin == 8 && g.Win == 8 && g.istride == 1 && g.Hg == 8 && g.Wg == 8 && Cin % 32 == 0 && g.ntile % 2 == 0) return ConvRoute::Tile8;
+    if (kind == VQVAE_CONV_4x4_S2 && g.Hin == 16 && g.Win == 16 && Cin % 32 == 0 && g.ntile % 2 == 0) return ConvRoute::Tile8S2d;
+    // the halo kernels and the generic kernels' two-term fp16 products need every image's maximum from the producing layer
+    if (!maxima_handed || split) return ConvRoute::IgemmBf3;
+    if (kind == VQVAE_CONV_4x4_S2 && g.Hg % 8 == 0 && g.Wg % 8 == 0 && g.Hg * g.Wg > 64 && g.Hin == 2 * g.Hg && g.Win == 2 * g.Wg &&
+        Cin % 32 == 0 && g.ntile % 2 == 0 && fits)
+        return ConvRoute::HaloS2;
+    if (g.istride == 1 && g.Hg == g.Hin && g.Wg == g.Win && g.Hg % 8 == 0 && g.Wg % 8 == 0 && g.Hg * g.Wg > 64 && Cin % 32 == 0 &&
+        g.ntile % 2 == 0 && (g.ntaps == 1 || g.ntaps == 4 || g.ntaps == 9) && fits)
+        return ConvRoute::Halo;
+    return ConvRoute::IgemmH2;
 }
 // byte offset of the header from the start of a layer's packed weights
 inline size_t packed_h2_offset(const ConvGeom &g, int kind) {

@@ -107,6 +107,49 @@ size_t res_hidden_bytes(const VqvaeDims *d, int64_t B, int H, int W) {
 // z_q where the decoder's first layer is a generic kernel, dec2)
 size_t amax_bytes(const VqvaeDims *d, int64_t B) { return align_up((size_t)(4 + d->n_res_layers) * B * sizeof(int), 256); }
 
+// VQVAE_FWD_CONV_* -> the per-layer product-scheme flag; -1: both at once / unknown bits
+int conv_scheme(int flags) {
+    const int sel = flags & (VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32);
+    if (sel == (VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32)) return -1;
+    return sel == VQVAE_FWD_CONV_BF16_SPLIT ? VQVAE_CONV_BF16_SPLIT : (sel == VQVAE_FWD_CONV_EXACT_FP32 ? VQVAE_CONV_EXACT_FP32 : 0);
+}
+
+// What the whole-path entry points launch for a model and an image size: computed once per entry point (fwd_plan), read by
+// encoder_run / decoder_run.  The fused kernels exist for the default product scheme only (cf == 0).
+struct FwdPlan {
+    int cf;              // conv_scheme: 0 = default, VQVAE_CONV_BF16_SPLIT / _EXACT_FP32 = every layer's per-layer kernels of that scheme
+    bool enc_front;      // encoder.py:29-34 in ONE launch (32x32 RGB images)
+    bool enc_pair_post;  // encoder.py:35-38 + vqvae.py:33 in ONE launch (8x8 latent maps, h_dim 128, two residual layers)
+    bool dec_front;      // decoder.py:28-30 in ONE launch; it also gathers z_q from the indices (vqvae_decode_f32)
+    bool dec_tail;       // decoder.py:31-35 in ONE launch (8x8 latent maps)
+    bool fused;          // all four: every per-image maximum that is read has ONE producing wave that stores it plainly -- no fill
+    bool vq_fuse;        // and the quantizer can run inside the encoder's last kernel (vq_fuse_ok)
+    bool zq_amax;        // the decoder's first conv, handed z_q's maxima, reads them (the 8x8-map kernel measures its image itself)
+};
+FwdPlan fwd_plan(const VqvaeDims *d, int H, int W, int flags) {
+    FwdPlan p{};
+    p.cf = conv_scheme(flags);
+    if (!dims_ok(d)) return p;
+    const int h = d->h_dim, h4 = H / 4, w4 = W / 4;
+    p.zq_amax = conv_reads_amax(VQVAE_CONVT_3x3_S1, h4, w4, d->embedding_dim, h, 0);      // (asked for the default scheme under every scheme)
+    if (p.cf != 0) return p;
+    // (A/B builds, tools/build_variant.py: VQVAE_NO_* keep the layers as their own launches)
+#ifndef VQVAE_NO_ENC_FRONT_FUSION
+    p.enc_front = enc_front_supported(H, W, d->in_ch, h / 2, h);
+#endif
+#ifndef VQVAE_NO_FRONT_FUSION
+    p.enc_pair_post = d->n_res_layers == 2 && conv_res_pair_supported(VQVAE_CONV_3x3_S1, h4, w4, h, h, d->res_h_dim) &&
+                      res_pair_post_supported(h, d->embedding_dim);
+    p.dec_front = d->n_res_layers == 2 && conv_res_pair_supported(VQVAE_CONVT_3x3_S1, h4, w4, d->embedding_dim, h, d->res_h_dim);
+#endif
+#ifndef VQVAE_NO_DEC_TAIL_FUSION
+    p.dec_tail = dec_tail_supported(h4, w4, h, h / 2, d->in_ch);
+#endif
+    p.fused = p.enc_front && p.enc_pair_post && p.dec_front && p.dec_tail;
+    p.vq_fuse = p.fused && vq_fuse_ok(d->n_embeddings, d->embedding_dim, flags);
+    return p;
+}
+
 // vqvae_decode_f32 on shapes without the gathering decoder kernel: z_q[i][:] = codebook[idx[i]][:] for ANY row length, and -- the
 // contract of the fused gather, include/vqvae_hip.h -- an index outside [0, K) never reads the codebook: its latent pixel becomes NaN
 __global__ __launch_bounds__(256) void decode_gather_kernel(const long long *__restrict__ idx, const float *__restrict__ codebook,
@@ -258,16 +301,13 @@ int vqvae_resstack_f32(const float *packed_w1, const float *packed_w2, const flo
                      y, tmp, static_cast<hipStream_t>(stream), &res);
 }
 
-// am_given: a maxima region (amax_bytes) the caller has already set to -1, or NULL to carve and initialise one here
+// am_given: a maxima region (amax_bytes) the caller has already set to -1, or NULL to carve one here (filled unless p.fused)
 // zero_buf / zero_n / zeroed: ints the last encoder kernel should clear for the quantizer behind it (its histogram);
 // *zeroed tells the caller whether a kernel that can do so ran
 // vq: quantize inside the last kernel (fused 32x32 path only; z_e is then NOT written and zero_buf is cleared by the FIRST kernel)
 static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, int W, float *z_e, void *workspace,
-                       size_t workspace_bytes, hipStream_t st, int *am_given, int *zero_buf = nullptr, int zero_n = 0,
-                       bool *zeroed = nullptr, bool am_exclusive = false, const VqFuse *vq = nullptr, int cf = 0,
-                       float *hid_given = nullptr, bool debug_ze = false) {
-    // cf: 0 = the default product scheme (two-term fp16 where the kernels have it), VQVAE_CONV_BF16_SPLIT / VQVAE_CONV_EXACT_FP32 =
-    // every layer through the per-layer kernels of that scheme (no fused kernels: they exist for the fp16 products only)
+                       size_t workspace_bytes, hipStream_t st, const FwdPlan &p, int *am_given, int *zero_buf = nullptr, int zero_n = 0,
+                       bool *zeroed = nullptr, const VqFuse *vq = nullptr, float *hid_given = nullptr, bool debug_ze = false) {
     if (!w || !x || !z_e || !workspace) return VQVAE_ERR_NULL;
     const VqvaeDims *d = &w->dims;
     if (!dims_ok(d) || B < 1 || H < 4 || W < 4 || H % 4 || W % 4) return VQVAE_ERR_SHAPE;
@@ -287,35 +327,29 @@ static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, 
     int *am = am_given;
     if (!am) {
         am = static_cast<int *>(c.raw(amax_bytes(d, B)));
-        // (no fill where every array that is read has a one-wave-per-image producer with plain stores: fused_c3_path)
-        if (am && !am_exclusive && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
+        // (no fill where every array that is read has a one-wave-per-image producer with plain stores: p.fused)
+        if (am && !p.fused && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
     }
     int *am0 = am, *am1 = am ? am + B : nullptr, *am2 = am ? am + 2 * B : nullptr;     // conv_in, enc2, enc4 (+ residual layers)
-    const int h = d->h_dim;
+    const int h = d->h_dim, cf = p.cf;
     int rc;
     // encoder.py:29-31, :32-34, :35-36 (+ the residual stack's first in-place ReLU, residual.py:19)
-#ifndef VQVAE_NO_ENC_FRONT_FUSION    // A/B builds (tools/build_variant.py)
     // encoder.py:29-34 in ONE launch on 32x32 RGB images: the 16x16 x h/2 map between the two stride-2 convs is never written
-    if (!cf && enc_front_supported(H, W, d->in_ch, h / 2, h)) {
+    if (p.enc_front) {
         if ((rc = enc_front_forward_impl(x, w->enc0, w->enc0_b, w->enc2, w->enc2_b, B, H, W, d->in_ch, h / 2, h, b, st, am1,
                                          vq ? zero_buf : nullptr, vq ? zero_n : 0)) != 0) return rc;
-    } else
-#endif
-    {
+    } else {
         if ((rc = conv_in_forward_impl(x, w->enc0, w->enc0_b, B, H, W, d->in_ch, h / 2, VQVAE_CONV_RELU_OUT | cf, a, st, am0)) != 0) return rc;
         if ((rc = conv_forward_impl(VQVAE_CONV_4x4_S2, a, w->enc2, w->enc2_b, B, H / 2, W / 2, h / 2, h, VQVAE_CONV_RELU_OUT | cf, b, st, am0, am1)) != 0) return rc;
     }
-#ifndef VQVAE_NO_FRONT_FUSION    // A/B builds (tools/build_variant.py)
     // encoder.py:35-38 + vqvae.py:33 in ONE launch where the shapes allow (8x8 latent maps, h_dim 128, two residual layers):
     // 3x3 conv + ReLU, both residual layers and the pre-quantisation conv; none of the three intermediate maps is written
-    if (!cf && d->n_res_layers == 2 && conv_res_pair_supported(VQVAE_CONV_3x3_S1, H / 4, W / 4, h, h, d->res_h_dim) &&
-        res_pair_post_supported(h, d->embedding_dim)) {
+    if (p.enc_pair_post) {
         const ResPairPost post{w->pre, w->pre_b, d->embedding_dim, z_e, vq ? nullptr : zero_buf, vq ? 0 : zero_n, vq, vq && debug_ze};
         if (zeroed) *zeroed = zero_buf != nullptr;
         return conv_res_pair_forward_impl(VQVAE_CONV_3x3_S1, b, w->enc4, w->enc4_b, h, w->enc_res_w1, w->enc_res_w2, B, H / 4, W / 4, h,
                                           d->res_h_dim, VQVAE_CONV_RELU_OUT, nullptr, st, am1, nullptr, &post);
     }
-#endif
     if ((rc = conv_forward_impl(VQVAE_CONV_3x3_S1, b, w->enc4, w->enc4_b, B, H / 4, W / 4, h, h, VQVAE_CONV_RELU_OUT | cf, a, st, am1, am2)) != 0) return rc;
     const float *t = a;
     const int *amt = am2;
@@ -337,35 +371,11 @@ static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, 
     return conv_forward_impl(VQVAE_CONV_1x1, t, w->pre, w->pre_b, B, H / 4, W / 4, h, d->embedding_dim, cf, z_e, st, amt, nullptr);   // vqvae.py:33
 }
 
-// 32x32 RGB images, h_dim 128, two residual layers: the step is four fused conv kernels (+ the quantizer), every per-image
-// maximum that is read has ONE producing wave that stores it plainly -- the maxima arrays need no fill
-static bool fused_c3_path(const VqvaeDims *d, int H, int W, int cf = 0) {
-    if (cf) return false;
-#if defined(VQVAE_NO_FRONT_FUSION) || defined(VQVAE_NO_ENC_FRONT_FUSION) || defined(VQVAE_NO_DEC_TAIL_FUSION)
-    (void)d; (void)H; (void)W;
-    return false;
-#else
-    const int h = d->h_dim;
-    return d->n_res_layers == 2 && enc_front_supported(H, W, d->in_ch, h / 2, h) &&
-           conv_res_pair_supported(VQVAE_CONV_3x3_S1, H / 4, W / 4, h, h, d->res_h_dim) && res_pair_post_supported(h, d->embedding_dim) &&
-           conv_res_pair_supported(VQVAE_CONVT_3x3_S1, H / 4, W / 4, d->embedding_dim, h, d->res_h_dim) &&
-           dec_tail_supported(H / 4, W / 4, h, h / 2, d->in_ch);
-#endif
-}
-
-// VQVAE_FWD_CONV_* -> the per-layer product-scheme flag; -1: both at once / unknown bits
-static int conv_scheme(int flags) {
-    const int sel = flags & (VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32);
-    if (sel == (VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32)) return -1;
-    return sel == VQVAE_FWD_CONV_BF16_SPLIT ? VQVAE_CONV_BF16_SPLIT : (sel == VQVAE_FWD_CONV_EXACT_FP32 ? VQVAE_CONV_EXACT_FP32 : 0);
-}
-
 int vqvae_encoder_ex_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, int W, int flags, float *z_e, void *workspace,
                          size_t workspace_bytes, vqvae_stream_t stream) {
-    const int cf = conv_scheme(flags);
-    if (cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
-    return encoder_run(w, x, B, H, W, z_e, workspace, workspace_bytes, static_cast<hipStream_t>(stream), nullptr, nullptr, 0, nullptr,
-                       w && dims_ok(&w->dims) && fused_c3_path(&w->dims, H, W, cf), nullptr, cf);
+    const FwdPlan p = fwd_plan(w ? &w->dims : nullptr, H, W, flags);
+    if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
+    return encoder_run(w, x, B, H, W, z_e, workspace, workspace_bytes, static_cast<hipStream_t>(stream), p, nullptr);
 }
 
 int vqvae_encoder_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, int W, float *z_e, void *workspace,
@@ -375,24 +385,11 @@ int vqvae_encoder_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
 
 // where z_q's per-image maxima go inside a maxima region (amax_bytes) for the decoder's first layer
 static int *zq_amax_slot(const VqvaeDims *d, int64_t B, int *am) { return am + (size_t)(2 + d->n_res_layers) * B; }
-// does the decoder's first layer want them (the generic / halo kernels do; the 8x8-map kernel measures its image itself)
-static bool zq_amax_wanted(const VqvaeDims *d, int h4, int w4) {
-    return vqvae_conv_term_products(VQVAE_CONVT_3x3_S1, h4, w4, d->embedding_dim, d->h_dim, 0) != 3;
-}
-
 // zq_amax_given: the quantizer has already published z_q's maxima into the region's slot
-// gather_idx: z_q = the codebook and the first kernel takes pixel p's row from code gather_idx[p] (decoder_gather_ok shapes only)
-static bool decoder_gather_ok(const VqvaeDims *d, int h4, int w4, int cf) {
-#ifndef VQVAE_NO_FRONT_FUSION
-    return !cf && d->n_res_layers == 2 && conv_res_pair_supported(VQVAE_CONVT_3x3_S1, h4, w4, d->embedding_dim, d->h_dim, d->res_h_dim);
-#else
-    (void)d; (void)h4; (void)w4; (void)cf;
-    return false;
-#endif
-}
+// gather_idx: z_q = the codebook and the first kernel takes pixel p's row from code gather_idx[p] (p.dec_front only)
 static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h4, int w4, float *x_hat, void *workspace,
-                       size_t workspace_bytes, hipStream_t st, int *am_given, bool am_exclusive = false, bool zq_amax_given = false,
-                       int cf = 0, float *hid_given = nullptr, const int64_t *gather_idx = nullptr) {
+                       size_t workspace_bytes, hipStream_t st, const FwdPlan &p, int *am_given, bool zq_amax_given = false,
+                       float *hid_given = nullptr, const int64_t *gather_idx = nullptr) {
     if (!w || !z_q || !x_hat || !workspace) return VQVAE_ERR_NULL;
     const VqvaeDims *d = &w->dims;
     if (!dims_ok(d) || B < 1 || h4 < 1 || w4 < 1) return VQVAE_ERR_SHAPE;
@@ -408,46 +405,39 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
     int *am = am_given;                                                       // optional, see encoder_run
     if (!am) {
         am = static_cast<int *>(c.raw(amax_bytes(d, B)));
-        if (am && !am_exclusive && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
+        if (am && !p.fused && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
     }
-    const int h = d->h_dim;
+    const int h = d->h_dim, cf = p.cf;
     int rc;
     // decoder.py:28-29 (+ the stack's first in-place ReLU), :30, :31-33, :34-35
     // z_q has no producer that publishes maxima: the 8x8-map kernel measures its image itself, the generic one gets them
     // from one more pass over z_q (array [2 + n_res_layers] of the region)
-    if (gather_idx && !decoder_gather_ok(d, h4, w4, cf)) return VQVAE_ERR_UNSUPPORTED;
+    if (gather_idx && !p.dec_front) return VQVAE_ERR_UNSUPPORTED;
     int *amz = nullptr;
-    if (am && !gather_idx && zq_amax_wanted(d, h4, w4)) {
+    if (am && !gather_idx && p.zq_amax) {
         amz = zq_amax_slot(d, B, am);
         if (!zq_amax_given) act_absmax_impl(z_q, B, (long long)h4 * w4 * d->embedding_dim, amz, st);
     }
     const float *t = a;
     const int *amt = am;
-#ifndef VQVAE_NO_FRONT_FUSION
     // decoder.py:28-30 in one launch where the shapes allow: conv-transpose 3x3 (+ the stack's first ReLU) and both residual layers
-    const bool front = !cf && d->n_res_layers == 2 && conv_res_pair_supported(VQVAE_CONVT_3x3_S1, h4, w4, d->embedding_dim, h, d->res_h_dim);
-#else
-    const bool front = false;
-#endif
-    if (front) {
+    if (p.dec_front) {
         int *aout = am ? am + (size_t)2 * B : nullptr;
         if ((rc = conv_res_pair_forward_impl(VQVAE_CONVT_3x3_S1, z_q, w->dec0, w->dec0_b, d->embedding_dim, w->dec_res_w1, w->dec_res_w2, B, h4,
                                              w4, h, d->res_h_dim, VQVAE_CONV_RELU_OUT, a, st, amz, aout, nullptr, gather_idx,
                                              d->n_embeddings)) != 0) return rc;
         amt = aout;
     } else if ((rc = conv_forward_impl(VQVAE_CONVT_3x3_S1, z_q, w->dec0, w->dec0_b, B, h4, w4, d->embedding_dim, h, VQVAE_CONV_RELU_OUT | cf, a, st, amz, am)) != 0) return rc;
-    if (!front && d->n_res_layers > 0) {
+    if (!p.dec_front && d->n_res_layers > 0) {
         float *y = (d->n_res_layers & 1) ? b : a, *tmp = (d->n_res_layers & 1) ? a : b;
         if ((rc = res_stack(w->dec_res_w1, w->dec_res_w2, a, B, h4, w4, h, d->res_h_dim, d->n_res_layers, false, true, y, tmp, st, &t, am,
                             nullptr, nullptr, cf, hid)) != 0) return rc;
         if (am) amt = am + (size_t)d->n_res_layers * B;
         if (!res_layer_fused_ok(h, d->res_h_dim)) amt = nullptr;
     }
-#ifndef VQVAE_NO_DEC_TAIL_FUSION    // A/B builds (tools/build_variant.py)
     // decoder.py:31-35 in ONE launch on 8x8 latent maps: the 16x16 x h/2 map between the two stride-2 transposed convs is never written
-    if (!cf && dec_tail_supported(h4, w4, h, h / 2, d->in_ch))
+    if (p.dec_tail)
         return dec_tail_forward_impl(t, w->dec2, w->dec2_b, w->dec4, w->dec4_b, B, h4, w4, h, h / 2, d->in_ch, x_hat, st, amt);
-#endif
     float *u = (t == a) ? b : a;
     int *am_u = am ? am + (size_t)(3 + d->n_res_layers) * B : nullptr;       // dec2's output maxima for the last layer
     if ((rc = conv_forward_impl(VQVAE_CONVT_4x4_S2, t, w->dec2, w->dec2_b, B, h4, w4, h, h / 2, VQVAE_CONV_RELU_OUT | cf, u, st, amt, am_u)) != 0) return rc;
@@ -456,10 +446,9 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
 
 int vqvae_decoder_ex_f32(const VqvaeWeights *w, const float *z_q, int64_t B, int h4, int w4, int flags, float *x_hat, void *workspace,
                          size_t workspace_bytes, vqvae_stream_t stream) {
-    const int cf = conv_scheme(flags);
-    if (cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
-    return decoder_run(w, z_q, B, h4, w4, x_hat, workspace, workspace_bytes, static_cast<hipStream_t>(stream), nullptr,
-                       w && dims_ok(&w->dims) && fused_c3_path(&w->dims, 4 * h4, 4 * w4, cf), false, cf);
+    const FwdPlan p = fwd_plan(w ? &w->dims : nullptr, 4 * h4, 4 * w4, flags);
+    if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
+    return decoder_run(w, z_q, B, h4, w4, x_hat, workspace, workspace_bytes, static_cast<hipStream_t>(stream), p, nullptr);
 }
 
 int vqvae_decoder_f32(const VqvaeWeights *w, const float *z_q, int64_t B, int h4, int w4, float *x_hat, void *workspace,
@@ -528,15 +517,14 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
     hipStream_t st = static_cast<hipStream_t>(stream);
     // two fill launches per step saved on the fused 32x32 path: the maxima need none there, and the quantizer's histogram
     // is cleared by the encoder's last kernel
-    const int cf = conv_scheme(vq_flags);
-    if (cf < 0) return VQVAE_ERR_UNSUPPORTED;
-    const bool fused = fused_c3_path(d, H, W, cf);
-    if (!fused && hipMemsetAsync(am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    const FwdPlan p = fwd_plan(d, H, W, vq_flags);
+    if (p.cf < 0) return VQVAE_ERR_UNSUPPORTED;
+    if (!p.fused && hipMemsetAsync(am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
     int *am_dec = reinterpret_cast<int *>(reinterpret_cast<char *>(am2) + amax_bytes(d, B));
     int rc;
     bool hist_zeroed = false;
     // (a forced launch form of the stand-alone quantizer -- VQVAE_VQ_UNITS* -- means the stand-alone quantizer: ADVICE r4)
-    if (fused && !(vq_flags & kVqFormFlags) && vq_fuse_ok(d->n_embeddings, d->embedding_dim, B, vq_flags)) {
+    if (p.vq_fuse && !(vq_flags & kVqFormFlags)) {
         // vqvae.py:31-34 in TWO launches: the encoder's last kernel quantizes its own z_e (never written); the codebook's
         // images are prepared first, the histogram is cleared by the encoder's first kernel, loss / perplexity by the finalize
         if ((rc = vq_prepare_impl(w->codebook, d->n_embeddings, d->embedding_dim, vq_flags, vqws, vqws_bytes, st)) != 0) return rc;
@@ -548,22 +536,22 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
         const bool debug_ze = vq_flags & VQVAE_FWD_DEBUG_ZE;
         if (debug_ze && !idx) return VQVAE_ERR_NULL;
         if (debug_ze) vf.partials = reinterpret_cast<double *>(idx_ws);
-        if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, am2, hist, d->n_embeddings, &hist_zeroed, false, &vf, 0, nullptr,
+        if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, p, am2, hist, d->n_embeddings, &hist_zeroed, &vf, nullptr,
                               debug_ze)) != 0) return rc;
         if ((rc = vq_finalize_impl(vf.partials, (int)((B + 3) / 4), hist, d->n_embeddings, (int64_t)rows, d->embedding_dim, d->beta, loss,
                                    perplexity, st)) != 0) return rc;
-        return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, am_dec);                         // :36
+        return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, p, am_dec);                      // :36
     }
     bool zq_amax_done = false;
-    if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, am2, fused ? hist : nullptr, d->n_embeddings, &hist_zeroed, false,
-                          nullptr, cf, f.hid)) != 0)
+    if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, p, am2, p.fused ? hist : nullptr, d->n_embeddings, &hist_zeroed,
+                          nullptr, f.hid)) != 0)
         return rc;                                                                                              // vqvae.py:31-33
     if ((rc = vq_forward_impl(z_e, w->codebook, B, d->embedding_dim, H / 4, W / 4, d->n_embeddings, d->beta,
                               (vq_flags & (VQVAE_VQ_CODEBOOK_PREPARED | VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER |
                                            VQVAE_VQ_REMOVED_FLAGS | kVqFormFlags)) | VQVAE_VQ_ROWMAJOR,
                               z_q, idx ? idx : idx_ws, hist, loss, perplexity, vqws, vqws_bytes, stream, hist_zeroed,
-                              zq_amax_wanted(d, H / 4, W / 4) ? zq_amax_slot(d, B, am_dec) : nullptr, &zq_amax_done)) != 0) return rc;   // :34
-    return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, am_dec, false, zq_amax_done, cf, f.hid);    // :36
+                              p.zq_amax ? zq_amax_slot(d, B, am_dec) : nullptr, &zq_amax_done)) != 0) return rc;   // :34
+    return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, p, am_dec, zq_amax_done, f.hid);    // :36
 }
 
 
@@ -582,22 +570,21 @@ int vqvae_encode_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, in
         if (crc != VQVAE_OK) return crc;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int cf = conv_scheme(vq_flags);
-    if (cf < 0) return VQVAE_ERR_UNSUPPORTED;
+    const FwdPlan p = fwd_plan(d, H, W, vq_flags);
+    if (p.cf < 0) return VQVAE_ERR_UNSUPPORTED;
     const size_t acts_bytes = 2 * align_up(f.act * sizeof(float), 256);
-    const bool fused = fused_c3_path(d, H, W, cf);
-    if (!fused && hipMemsetAsync(f.am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (!p.fused && hipMemsetAsync(f.am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
     int rc;
     bool hist_zeroed = false;
-    if (fused && !(vq_flags & kVqFormFlags) && vq_fuse_ok(d->n_embeddings, d->embedding_dim, B, vq_flags)) {
+    if (p.vq_fuse && !(vq_flags & kVqFormFlags)) {
         if ((rc = vq_prepare_impl(w->codebook, d->n_embeddings, d->embedding_dim, vq_flags, f.vqws, f.vqws_bytes, st)) != 0) return rc;
         VqFuse vf = vq_fuse_args(w->codebook, d->n_embeddings, f.vqws, nullptr, idx, f.hist);      // no z_q: its stores are dropped
         vf.partials = reinterpret_cast<double *>(f.z_e);                // (the loss partials and the histogram are by-products nobody reads)
-        return encoder_run(w, x, B, H, W, f.z_e, f.acts, acts_bytes, st, f.am2, f.hist, d->n_embeddings, &hist_zeroed, false, &vf);
+        return encoder_run(w, x, B, H, W, f.z_e, f.acts, acts_bytes, st, p, f.am2, f.hist, d->n_embeddings, &hist_zeroed, &vf);
     }
     // other shapes: encoder -> z_e (workspace) -> the stand-alone quantizer (z_q, loss and perplexity land in the workspace, unread)
-    if ((rc = encoder_run(w, x, B, H, W, f.z_e, f.acts, acts_bytes, st, f.am2, fused ? f.hist : nullptr, d->n_embeddings, &hist_zeroed, false,
-                          nullptr, cf, f.hid)) != 0) return rc;
+    if ((rc = encoder_run(w, x, B, H, W, f.z_e, f.acts, acts_bytes, st, p, f.am2, p.fused ? f.hist : nullptr, d->n_embeddings, &hist_zeroed,
+                          nullptr, f.hid)) != 0) return rc;
     float *scal = reinterpret_cast<float *>(f.idx_ws);                  // (the workspace's index region is free: idx is the caller's)
     return vq_forward_impl(f.z_e, w->codebook, B, d->embedding_dim, H / 4, W / 4, d->n_embeddings, d->beta,
                            (vq_flags & (VQVAE_VQ_CODEBOOK_PREPARED | VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER | VQVAE_VQ_REMOVED_FLAGS |
@@ -609,8 +596,8 @@ int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h
                      size_t workspace_bytes, vqvae_stream_t stream) {
     if (!w || !idx || !x_hat || !workspace) return VQVAE_ERR_NULL;
     const VqvaeDims *d = &w->dims;
-    const int cf = conv_scheme(flags);
-    if (cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
+    const FwdPlan p = fwd_plan(d, 4 * h4, 4 * w4, flags);
+    if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
     if (!dims_ok(d) || B < 1 || h4 < 1 || w4 < 1) return VQVAE_ERR_SHAPE;
     FwdWs f;
     int vq_flags = VQVAE_VQ_CODEBOOK_PREPARED;                          // (no quantizer workspace is touched here)
@@ -621,10 +608,9 @@ int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t acts_bytes = 2 * align_up(f.act * sizeof(float), 256);
     int *am_dec = reinterpret_cast<int *>(reinterpret_cast<char *>(f.am2) + amax_bytes(d, B));
-    const bool fused = fused_c3_path(d, 4 * h4, 4 * w4, cf);
-    if (!fused && hipMemsetAsync(am_dec, 0xFF, amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
-    if (decoder_gather_ok(d, h4, w4, cf))
-        return decoder_run(w, w->codebook, B, h4, w4, x_hat, f.acts, acts_bytes, st, am_dec, false, false, cf, f.hid, idx);
+    if (!p.fused && hipMemsetAsync(am_dec, 0xFF, amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (p.dec_front)
+        return decoder_run(w, w->codebook, B, h4, w4, x_hat, f.acts, acts_bytes, st, p, am_dec, false, f.hid, idx);
     // other shapes: the codebook rows of every position into the workspace's z_q (row-major), then the decoder
     {
         const long long total = (long long)f.rows * d->embedding_dim;
@@ -635,7 +621,7 @@ int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h
         const int lrc = (int)hipGetLastError();
         if (lrc != 0) return lrc;
     }
-    return decoder_run(w, f.z_q, B, h4, w4, x_hat, f.acts, acts_bytes, st, am_dec, false, false, cf, f.hid);
+    return decoder_run(w, f.z_q, B, h4, w4, x_hat, f.acts, acts_bytes, st, p, am_dec, false, f.hid);
 }
 
 // ---- the same step in PARTS (the default shapes' fused path only) -----------------------------------------------------------
@@ -652,7 +638,7 @@ int vqvae_forward_begin_f32(const VqvaeWeights *w, int64_t B, int H, int W, int 
     FwdWs f;
     int rc = carve_forward(d, B, H, W, workspace, workspace_bytes, vq_workspace, vq_workspace_bytes, vq_flags, f);
     if (rc != VQVAE_OK) return rc;
-    if (!fused_c3_path(d, H, W, conv_scheme(vq_flags)) || !vq_fuse_ok(d->n_embeddings, d->embedding_dim, B, vq_flags)) return VQVAE_ERR_UNSUPPORTED;
+    if (!fwd_plan(d, H, W, vq_flags).vq_fuse) return VQVAE_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = vq_prepare_impl(w->codebook, d->n_embeddings, d->embedding_dim, vq_flags, f.vqws, f.vqws_bytes, st)) != 0) return rc;
     if (hipMemsetAsync(f.hist, 0, (size_t)d->n_embeddings * sizeof(int32_t), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
@@ -673,7 +659,8 @@ int vqvae_forward_part_f32(const VqvaeWeights *w, const float *x, int64_t B, int
     FwdWs f;
     int rc = carve_forward(d, B, H, W, workspace, workspace_bytes, vq_workspace, vq_workspace_bytes, vq_flags, f);
     if (rc != VQVAE_OK) return rc;
-    if (!fused_c3_path(d, H, W, conv_scheme(vq_flags)) || !vq_fuse_ok(d->n_embeddings, d->embedding_dim, B, vq_flags)) return VQVAE_ERR_UNSUPPORTED;
+    const FwdPlan p = fwd_plan(d, H, W, vq_flags);
+    if (!p.vq_fuse) return VQVAE_ERR_UNSUPPORTED;
     {
         // this part against the step's record: same shapes / flags / quantizer workspace as begin, images nobody has claimed
         std::lock_guard<std::mutex> lk(g_parts_mu);
@@ -698,8 +685,8 @@ int vqvae_forward_part_f32(const VqvaeWeights *w, const float *x, int64_t B, int
     VqFuse vf = vq_fuse_args(w->codebook, d->n_embeddings, f.vqws, z_q_p, idx_p, f.hist);
     vf.partials = reinterpret_cast<double *>(f.z_e) + b0 / 4;
     const float *x_p = x + (size_t)b0 * d->in_ch * H * W;
-    rc = encoder_run(w, x_p, Bc, H, W, f.z_e, acts_p, acts_p_bytes, st, am_p, nullptr, 0, nullptr, false, &vf);
-    if (rc == 0) rc = decoder_run(w, z_q_p, Bc, H / 4, W / 4, x_hat + (size_t)b0 * d->in_ch * H * W, acts_p, acts_p_bytes, st, am_dec_p);
+    rc = encoder_run(w, x_p, Bc, H, W, f.z_e, acts_p, acts_p_bytes, st, p, am_p, nullptr, 0, nullptr, &vf);
+    if (rc == 0) rc = decoder_run(w, z_q_p, Bc, H / 4, W / 4, x_hat + (size_t)b0 * d->in_ch * H * W, acts_p, acts_p_bytes, st, p, am_dec_p);
     if (rc != 0) {
         // a part whose launches failed gives its claim back: the caller may retry [b0, b0 + Bc)
         std::lock_guard<std::mutex> lk(g_parts_mu);

@@ -444,12 +444,15 @@ static int launch_vq_prepare(const float *cb, int K, char *ws, hipStream_t st) {
     hipLaunchKernelGGL(vq_prepare_kernel<D>, dim3((kmax + 63) / 64), dim3(64), 0, st, cb, K, p.KC, p.K_pad,
                        reinterpret_cast<float *>(ws + p.off_ee), reinterpret_cast<float *>(ws + p.off_img), wflags, p.K32,
                        reinterpret_cast<unsigned short *>(ws + p.off_img16), reinterpret_cast<float *>(ws + p.off_neh));
-    if (vq_track_ok(K, D) || vq_chunk_ok(K, D)) launch_vq_prepare16(cb, K, D, ws, st);
+    // the fp16 image of the single-sweep screens (the NCHW stream tracker takes a subset of the row-major one's codebooks)
+    const VqRoute r = vq_route(K, D, 0, VQVAE_VQ_ROWMAJOR);
+    if (r == VqRoute::Track || r == VqRoute::Chunk) launch_vq_prepare16(cb, K, D, ws, st);
     return (int)hipGetLastError();
 }
 
+// route: vq_route of this problem -- Track, TrackNchw, Chunk, Filter or Exact
 template <int D>
-static int launch_vq(const float *z, const float *cb, long long N, int HW, int K, float beta,
+static int launch_vq(VqRoute route, const float *z, const float *cb, long long N, int HW, int K, float beta,
                      int flags, float *zq, long long *idx, int *hist, float *loss, float *ppl,
                      char *ws, hipStream_t st, bool hist_zeroed, int *zq_amax, bool *zq_amax_done) {
     const VqPlan p = vq_plan(K, D);
@@ -466,55 +469,31 @@ static int launch_vq(const float *z, const float *cb, long long N, int HW, int K
         if (rc != 0) return rc;
     }
     const bool rowmajor = flags & VQVAE_VQ_ROWMAJOR;
-    if constexpr (D == 64) {
-        // NCHW maps whose pixel count is a multiple of 32 (a unit = 64 or 32 positions of one image): the stream-tracker kernel reads
-        // and writes the reference's own layout (round 4); other NCHW maps stay on the two-sweep kernel below
-        const bool track_nchw = !rowmajor && vq_track_nchw_ok(K, D, HW) && !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER));
-        if (track_nchw || (rowmajor && vq_track_ok(K, D) && !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER)))) {
-            int fgrid = 0;
-            const int rc = launch_vq_track_d64(z, cb, N, K, zq, idx, hist, ws, st, &fgrid, HW, track_nchw,
-                                               vq_form_of_flags(flags));
-            if (rc != 0) return rc;
-            hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, st, partials, fgrid, hist, K, N, D,
-                               beta, loss, ppl);
-            return (int)hipGetLastError();
-        }
-    }
-    if constexpr (D == 64 || D == 128) {
-        // larger codebooks / D = 128: the same fp16 screen with the codebook image streamed through LDS (vq_chunk.hip)
-        if (rowmajor && vq_chunk_ok(K, D) && !vq_track_ok(K, D) && !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER))) {
-            int fgrid = 0;
-            prof_begin(VQVAE_PROF_VQ_MAIN, st);
-            const int rc = launch_vq_chunked(z, cb, N, K, D, zq, idx, hist, ws, st, &fgrid, zq_amax, HW);
+    // the stream tracker times its own dispatch (prof_dispatch); the others are timed around their launches
+    const bool timed = route != VqRoute::Track && route != VqRoute::TrackNchw;
+    if (timed) prof_begin(VQVAE_PROF_VQ_MAIN, st);
+    int fgrid = 0, rc = 0;
+    switch (route) {
+        case VqRoute::Track:
+        case VqRoute::TrackNchw:
+            rc = launch_vq_track_d64(z, cb, N, K, zq, idx, hist, ws, st, &fgrid, HW, route == VqRoute::TrackNchw, vq_form_of_flags(flags));
+            break;
+        case VqRoute::Chunk:
+            rc = launch_vq_chunked(z, cb, N, K, D, zq, idx, hist, ws, st, &fgrid, zq_amax, HW);
             if (zq_amax_done) *zq_amax_done = zq_amax != nullptr && zq != nullptr;
-            prof_end(VQVAE_PROF_VQ_MAIN, st);
-            if (rc != 0) return rc;
-            hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, st, partials, fgrid, hist, K, N, D,
-                               beta, loss, ppl);
-            return (int)hipGetLastError();
-        }
-    }
-    if constexpr (D == 64) {
-        if (p.filter_ok && !(flags & VQVAE_VQ_EXACT_SWEEP)) {
-            int fgrid = 0;
-            prof_begin(VQVAE_PROF_VQ_MAIN, st);
-            const int rc = launch_vq_filter_d64(z, cb, N, HW, K, rowmajor, zq, idx, hist, ws, st, &fgrid);
-            prof_end(VQVAE_PROF_VQ_MAIN, st);
-            if (rc != 0) return rc;
-            hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, st, partials, fgrid, hist, K, N, D,
-                               beta, loss, ppl);
-            return (int)hipGetLastError();
-        }
-    }
-    const int cus = num_cus();
-    // two row tiles per wave when that still leaves every CU at least two row blocks
-    int rt = (D <= 64 && (N + 511) / 512 >= 2LL * cus) ? 2 : 1;
-    const long long rows_wg = 256LL * rt;
-    const long long nblocks = (N + rows_wg - 1) / rows_wg;
-    long long grid = nblocks < cus ? nblocks : cus;
-    if (grid > kVqMaxGrid) grid = kVqMaxGrid;
-
-    prof_begin(VQVAE_PROF_VQ_MAIN, st);
+            break;
+        case VqRoute::Filter:
+            rc = launch_vq_filter_d64(z, cb, N, HW, K, rowmajor, zq, idx, hist, ws, st, &fgrid);
+            break;
+        default: {                                   // Exact
+            const int cus = num_cus();
+            // two row tiles per wave when that still leaves every CU at least two row blocks
+            int rt = (D <= 64 && (N + 511) / 512 >= 2LL * cus) ? 2 : 1;
+            const long long rows_wg = 256LL * rt;
+            const long long nblocks = (N + rows_wg - 1) / rows_wg;
+            long long grid = nblocks < cus ? nblocks : cus;
+            if (grid > kVqMaxGrid) grid = kVqMaxGrid;
+            fgrid = (int)grid;
 #define VQ_LAUNCH(RT_, RM_)                                                                        \
     do {                                                                                           \
         auto kfn = vq_exact_kernel<D, RT_, RM_>;                                                   \
@@ -524,19 +503,40 @@ static int launch_vq(const float *z, const float *cb, long long N, int HW, int K
         hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), p.lds_bytes, st, z, cb, img, ee,  \
                            wflags, N, HW, K, p.KC, p.nchunks, nblocks, zq, idx, hist, partials);   \
     } while (0)
-
-    if (rt == 2) {
-        if constexpr (D <= 64) {
-            if (rowmajor) VQ_LAUNCH(2, true); else VQ_LAUNCH(2, false);
-        }
-    } else {
-        if (rowmajor) VQ_LAUNCH(1, true); else VQ_LAUNCH(1, false);
-    }
+            if (rt == 2) {
+                if constexpr (D <= 64) {
+                    if (rowmajor) VQ_LAUNCH(2, true); else VQ_LAUNCH(2, false);
+                }
+            } else {
+                if (rowmajor) VQ_LAUNCH(1, true); else VQ_LAUNCH(1, false);
+            }
 #undef VQ_LAUNCH
-    prof_end(VQVAE_PROF_VQ_MAIN, st);
-    hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, st, partials, (int)grid, hist, K, N,
-                       D, beta, loss, ppl);
+        }
+    }
+    if (timed) prof_end(VQVAE_PROF_VQ_MAIN, st);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, st, partials, fgrid, hist, K, N, D, beta, loss, ppl);
     return (int)hipGetLastError();
+}
+
+static bool vq_mfma_dim(int D) { return D == 32 || D == 64 || D == 128 || D == 256; }
+
+VqRoute vq_route(int K, int D, int HW, int flags) {
+    if (K < 1 || K > 16384 || (flags & VQVAE_VQ_REMOVED_FLAGS)) return VqRoute::Unsupported;
+    // any other width: exact fp32 -- on the matrix cores since round 6 (zero-padded to a multiple of eight channels), round 5's
+    // vector-unit kernel behind VQVAE_VQ_BF16_FILTER for A/B runs
+    if (!vq_mfma_dim(D)) return !vq_generic_ok(K, D) ? VqRoute::Unsupported
+                                                      : ((flags & VQVAE_VQ_BF16_FILTER) ? VqRoute::GenericVector : VqRoute::AnyD);
+    const bool rowmajor = flags & VQVAE_VQ_ROWMAJOR;
+    const bool screen = !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER));      // the default single-sweep fp16 screen
+    if (screen && rowmajor && vq_track_ok(K, D)) return VqRoute::Track;
+    // NCHW maps whose pixel count is a multiple of 32 (a unit = 64 or 32 positions of one image): the stream-tracker kernel reads
+    // and writes the reference's own layout (round 4); other NCHW maps take the two-sweep filter kernel
+    if (screen && !rowmajor && vq_track_nchw_ok(K, D, HW)) return VqRoute::TrackNchw;
+    // larger codebooks / D = 128: the same fp16 screen with the codebook image streamed through LDS (vq_chunk.hip)
+    if (screen && rowmajor && vq_chunk_ok(K, D)) return VqRoute::Chunk;
+    if (D == 64 && !(flags & VQVAE_VQ_EXACT_SWEEP) && vq_filter_lds_bytes(K, D) <= (size_t)kLdsBytes) return VqRoute::Filter;
+    return VqRoute::Exact;
 }
 
 }  // namespace vqvae
@@ -545,34 +545,19 @@ using namespace vqvae;
 
 extern "C" {
 
-static bool vq_mfma_dim(int D) { return D == 32 || D == 64 || D == 128 || D == 256; }
-
+// (NCHW: the answer for 8x8 maps -- HW = 64)
 const char *vqvae_vq_kernel_name(int K, int D, int flags) {
-    if (K < 1 || K > 16384 || (flags & VQVAE_VQ_REMOVED_FLAGS)) return "unsupported";
-    // any other width: exact fp32 -- on the matrix cores since round 6 (zero-padded to a multiple of eight channels), round 5's
-    // vector-unit kernel behind VQVAE_VQ_BF16_FILTER for A/B runs
-    if (!vq_mfma_dim(D)) return vq_generic_ok(K, D) ? ((flags & VQVAE_VQ_BF16_FILTER) ? "vq_generic_kernel" : "vq_anyd_kernel") : "unsupported";
-    if (D == 64 && !(flags & VQVAE_VQ_EXACT_SWEEP)) {
-        if ((flags & VQVAE_VQ_ROWMAJOR) && vq_track_ok(K, D) && !(flags & VQVAE_VQ_BF16_FILTER)) return "vq_track_kernel_d64";
-        if ((flags & VQVAE_VQ_ROWMAJOR) && vq_chunk_ok(K, D) && !(flags & VQVAE_VQ_BF16_FILTER)) return "vq_stream_sweep_kernel";
-        // NCHW (the module boundary): the stream-tracker kernel on maps whose pixel count is a multiple of 32 (8x8, 56x56, 64x64
-        // ...: what this function answers for); other NCHW maps run vq_filter_kernel_d64
-        if (!(flags & (VQVAE_VQ_ROWMAJOR | VQVAE_VQ_BF16_FILTER)) && vq_track_nchw_ok(K, D, 64))
-            return "vq_track_kernel_d64";
-        if (vq_plan(K, D).filter_ok) return "vq_filter_kernel_d64";
-    }
-    if (D == 128 && (flags & VQVAE_VQ_ROWMAJOR) && !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER)) && vq_chunk_ok(K, D))
-        return "vq_stream_sweep_kernel";
-    return "vq_exact_kernel";
+    static const char *const names[] = {"vq_track_kernel_d64", "vq_track_kernel_d64", "vq_stream_sweep_kernel", "vq_filter_kernel_d64",
+                                        "vq_exact_kernel", "vq_anyd_kernel", "vq_generic_kernel", "unsupported"};
+    return names[(int)vq_route(K, D, 64, flags)];
 }
 
 int vqvae_vq_launch_form(int64_t n_rows, int K, int D, int HW, int flags, int *waves, int *unit_rows, int *pool_pct) {
     if (n_rows < 1 || K < 1 || HW < 1) return VQVAE_ERR_SHAPE;
-    const char *n = vqvae_vq_kernel_name(K, D, flags);
+    const VqRoute r = vq_route(K, D, HW, flags);
     VqTrackForm f;
-    const bool nchw = !(flags & VQVAE_VQ_ROWMAJOR);
-    if (D != 64 || n[3] != 't' || !vq_track_form(n_rows, K, HW, nchw, vq_form_of_flags(flags),
-                                                  num_cus(), f))
+    if ((r != VqRoute::Track && r != VqRoute::TrackNchw) ||
+        !vq_track_form(n_rows, K, HW, r == VqRoute::TrackNchw, vq_form_of_flags(flags), num_cus(), f))
         return VQVAE_ERR_UNSUPPORTED;
     if (waves) *waves = f.waves;
     if (unit_rows) *unit_rows = f.unit_rows;
@@ -581,15 +566,14 @@ int vqvae_vq_launch_form(int64_t n_rows, int K, int D, int HW, int flags, int *w
 }
 
 int vqvae_vq_screen_sweeps(int K, int D, int flags) {
-    const char *n = vqvae_vq_kernel_name(K, D, flags);
-    return (n[3] == 's' || n[3] == 't') ? 1 : (n[3] == 'f' ? 2 : 0);
+    const VqRoute r = vq_route(K, D, 64, flags);
+    return (r == VqRoute::Track || r == VqRoute::TrackNchw || r == VqRoute::Chunk) ? 1 : (r == VqRoute::Filter ? 2 : 0);
 }
 
 size_t vqvae_vq_workspace_bytes(int64_t n_rows, int K, int D) {
-    if (K < 1 || K > 16384) return 0;
     (void)n_rows;
-    if (!vq_mfma_dim(D)) return vq_generic_ok(K, D) ? vq_generic_workspace_bytes(K, D) : 0;
-    return vq_plan(K, D).total;
+    const VqRoute r = vq_route(K, D, 0, VQVAE_VQ_ROWMAJOR);
+    return r == VqRoute::Unsupported ? 0 : (r == VqRoute::AnyD ? vq_generic_workspace_bytes(K, D) : vq_plan(K, D).total);
 }
 
 int vqvae_vq_forward_f32(const float *z_e, const float *codebook, int64_t B, int D, int H, int W,
@@ -602,11 +586,10 @@ int vqvae_vq_forward_f32(const float *z_e, const float *codebook, int64_t B, int
 }  // extern "C"
 
 // ---- the quantizer inside the encoder's last kernel (conv_fused.hip): what vqvae_forward_f32 does around that launch ---------
-bool vqvae::vq_fuse_ok(int K, int D, int64_t B, int flags) {
-    const VqPlan p = vq_plan(K > 0 ? K : 1, 64);
-    (void)B;
-    return D == 64 && K >= 1 && K <= 1024 && p.K32 % 128 == 0 && vq_track_ok(K, D) &&
-           !(flags & (VQVAE_VQ_EXACT_SWEEP | VQVAE_VQ_BF16_FILTER | VQVAE_VQ_UNFUSED));
+// the codebooks of the row-major stream tracker whose 32-code tiles come in fours (K32 % 128 == 0); the removed flags are not looked at
+bool vqvae::vq_fuse_ok(int K, int D, int flags) {
+    return vq_route(K, D, 0, (flags & ~VQVAE_VQ_REMOVED_FLAGS) | VQVAE_VQ_ROWMAJOR) == VqRoute::Track && (K + 31) / 32 % 4 == 0 &&
+           !(flags & VQVAE_VQ_UNFUSED);
 }
 
 int vqvae::vq_prepare_impl(const float *codebook, int K, int D, int flags, void *workspace, size_t workspace_bytes, hipStream_t st) {
@@ -648,28 +631,29 @@ int vqvae::vq_forward_impl(const float *z_e, const float *codebook, int64_t B, i
     if (zq_amax_done) *zq_amax_done = false;
     if (!z_e || !codebook || !idx || !hist || !loss || !perplexity) return VQVAE_ERR_NULL;
     if (B < 1 || D < 1 || H < 1 || W < 1 || K < 1) return VQVAE_ERR_SHAPE;
-    const bool generic = !(D == 32 || D == 64 || D == 128 || D == 256);
-    if (K > 16384 || (generic && !vq_generic_ok(K, D))) return VQVAE_ERR_UNSUPPORTED;
+    // (round 2's tracker kernel and its A/B flags are gone since round 4: refused behind the overflow checks)
+    if (vq_route(K, D, 0, flags & ~VQVAE_VQ_REMOVED_FLAGS) == VqRoute::Unsupported) return VQVAE_ERR_UNSUPPORTED;
     if ((int64_t)H * W > (int64_t)1 << 30) return VQVAE_ERR_OVERFLOW;
     const int64_t N = B * (int64_t)H * W;
     if (N / ((int64_t)H * W) != B || N > ((int64_t)1 << 40)) return VQVAE_ERR_OVERFLOW;
-    if (flags & VQVAE_VQ_REMOVED_FLAGS) return VQVAE_ERR_UNSUPPORTED;     // round 2's tracker kernel and its A/B flags are gone (round 4)
+    const int HW = H * W;
+    const VqRoute route = vq_route(K, D, HW, flags);
+    if (route == VqRoute::Unsupported) return VQVAE_ERR_UNSUPPORTED;
     const size_t need = vqvae_vq_workspace_bytes(N, K, D);
     if (!workspace || workspace_bytes < need) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);
-    const int HW = H * W;
     long long *idx_ll = reinterpret_cast<long long *>(idx);
-    // any other embedding width (main.py:21 leaves it free): exact fp32 on the vector units, the same bits (vq_generic.hip); the
-    // kernel-selection flags have nothing to select there
-    if (generic)
+    // any other embedding width (main.py:21 leaves it free): exact fp32, the same bits (vq_generic.hip); the kernel-selection flags
+    // have nothing to select there
+    if (route == VqRoute::AnyD || route == VqRoute::GenericVector)
         return launch_vq_generic(z_e, codebook, N, HW, K, D, beta, (flags & VQVAE_VQ_ROWMAJOR) != 0, z_q, idx_ll, hist, loss, perplexity, ws, st,
-                                 hist_zeroed, (flags & VQVAE_VQ_BF16_FILTER) != 0, (flags & VQVAE_VQ_CODEBOOK_PREPARED) != 0);
+                                 hist_zeroed, route == VqRoute::GenericVector, (flags & VQVAE_VQ_CODEBOOK_PREPARED) != 0);
     switch (D) {
-        case 32:  return launch_vq<32>(z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
-        case 64:  return launch_vq<64>(z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
-        case 128: return launch_vq<128>(z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
-        case 256: return launch_vq<256>(z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
+        case 32:  return launch_vq<32>(route, z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
+        case 64:  return launch_vq<64>(route, z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
+        case 128: return launch_vq<128>(route, z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
+        case 256: return launch_vq<256>(route, z_e, codebook, N, HW, K, beta, flags, z_q, idx_ll, hist, loss, perplexity, ws, st, hist_zeroed, zq_amax, zq_amax_done);
     }
     return VQVAE_ERR_UNSUPPORTED;
 }
