@@ -111,6 +111,9 @@ VQVAE_API int vqvae_calibration_mfma_f16(int iters, void *scratch, size_t scratc
 
 #define VQVAE_VQ_UNITS32_8WAVES  0x400 /* 32-row units on eight waves per CU, forced (the rule takes this form up to 8 units per CU) */
 
+#define VQVAE_VQ_BWD_COMMITMENT 0x800 /* vqvae_vq_backward_f32 only: the gradient of VectorQuantizerEMA's loss beta * mean((z_q - z)^2)
+                                        (grad_z only, scale 2 beta / (N D); grad_codebook must be NULL) */
+
 #define VQVAE_VQ_UNFUSED        0x40 /* vqvae_forward_f32 only: run the quantizer as its own launch even where the encoder's last
                                         kernel would quantize its z_e in place (32x32 images, h_dim 128, K = 128 k <= 1024, D = 64: z_e is
                                         then never written); identical outputs, A/B timing and tests */
@@ -301,13 +304,31 @@ VQVAE_API int vqvae_transpose_f32(const float *x, int64_t batch, int R, int C, f
  *   g = *grad_loss (device scalar; NULL = 1), grad_zq = upstream gradient of the returned z_q (NULL = 0).
  *   z_e / grad_zq / grad_z share the layout selected by VQVAE_VQ_ROWMAJOR.  Either output may be NULL.
  *   The codebook gradient uses no floating-point atomics: rows are stably sorted by code and summed in a
- *   fixed order in fp64, so it is bit-reproducible run to run.  Parity with torch autograd: rtol 1e-5.   */
+ *   fixed order in fp64, so it is bit-reproducible run to run.  Parity with torch autograd: rtol 1e-5.
+ *   flags | VQVAE_VQ_BWD_COMMITMENT: grad_z = grad_zq + g * 2 beta (z - e_idx) / (N D) only (VectorQuantizerEMA's loss).   */
 VQVAE_API size_t vqvae_vq_backward_workspace_bytes(int64_t N, int K, int D);
 VQVAE_API int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t *idx,
                                     const float *grad_zq, const float *grad_loss,
                                     int64_t B, int D, int H, int W, int K, float beta, int flags,
                                     float *grad_z, float *grad_codebook,
                                     void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
+/* EMA codebook update (arXiv 1711.00937 Appendix A.1; Sonnet's VectorQuantizerEMA): the codebook follows exponential moving
+ * averages of the encoder outputs assigned to each code instead of a gradient.  With c_k = #{i : idx_i = k}, s_k = sum of those z_i:
+ *     N_k <- decay N_k + (1 - decay) c_k                       ema_cluster_size (K) fp32, in/out
+ *     m_k <- decay m_k + (1 - decay) s_k                       ema_w (K, D) fp32, in/out
+ *     n = sum_k N_k;  e_k = m_k / ((N_k + eps) / (n + K eps) n)   codebook (K, D) fp32, out (Laplace-smoothed counts)
+ * Restart: with threshold >= 0 and uniforms (K fp32 in [0, 1)) given, a code with N_k < threshold takes row
+ * r_k = min(floor(u_k N), N - 1) of z_e instead (N_k and m_k stay as updated); threshold < 0 or uniforms == NULL: no restart.
+ *   idx: the forward's indices (against the codebook before this update).  z_e layout by VQVAE_VQ_ROWMAJOR (no other flag).
+ *   Sums s_k in fp64 in a fixed order (the backward's sort and segmented sum), update and normalisation in fp64, one rounding per
+ *   store; no floating-point atomics, no host sync: bit-reproducible.  codebook must not alias ema_w or z_e.
+ *   Envelope: K <= 16384, D <= 256, N <= INT32_MAX (VQVAE_ERR_UNSUPPORTED outside it; the sizing call then returns 0).  */
+VQVAE_API size_t vqvae_vq_ema_workspace_bytes(int64_t N, int K, int D);
+VQVAE_API int vqvae_vq_ema_update_f32(const float *z_e, const int64_t *idx, int64_t B, int D, int H, int W, int K,
+                                      double decay, double eps, double threshold, const float *uniforms, int flags,
+                                      float *ema_cluster_size, float *ema_w, float *codebook,
+                                      void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
 /* recon_loss = mean((x_hat - x)^2) / x_train_var; loss = recon_loss + embedding_loss (main.py:75-76).
  * out3 = {recon_loss, loss, perplexity}: the three values main.py:81-83 copies to the host one by one,

@@ -5,6 +5,7 @@ no dataset can be fetched here).  Every forward and backward runs on libvqvae_hi
 training.VQStraightThrough, training.step_losses); the optimizer is torch's, as in the reference.
 
     python tools/train_checkpoint.py [--n_updates 5000] [--batch_size 32] [--out gpurun_out/trained]
+                                     [--ema_decay 0.99 [--restart_threshold 1]]     (the EMA codebook; off by default)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -44,7 +45,15 @@ def main():
     p.add_argument("--data_seed", type=int, default=2026)
     p.add_argument("--out", default="gpurun_out/trained")
     p.add_argument("--tag", default="vqvae_trained")
+    # opt-in EMA codebook (VectorQuantizerEMA); absent from the namespace unless given, so a default run writes what it always did
+    p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS)
+    p.add_argument("--restart_threshold", type=float, default=argparse.SUPPRESS)
     args = p.parse_args()
+    ema_kw = {}
+    if hasattr(args, "ema_decay"):
+        ema_kw["ema_decay"] = args.ema_decay
+    if hasattr(args, "restart_threshold"):
+        ema_kw["restart_threshold"] = args.restart_threshold
 
     dev = torch.device("cuda:0")
     conv.set_conv_backend("hip")
@@ -67,7 +76,7 @@ def main():
 
     torch.manual_seed(0)
     model = VQVAE(args.n_hiddens, args.n_residual_hiddens, args.n_residual_layers, args.n_embeddings, args.embedding_dim,
-                  args.beta).to(dev)
+                  args.beta, **ema_kw).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)       # main.py:59
     model.train()
     results = {"n_updates": 0, "recon_errors": [], "loss_vals": [], "perplexities": []}

@@ -10,6 +10,10 @@
 //                              added in a fixed order in fp64 by one workgroup, and a code's chunks are combined in a
 //                              fixed order -- the result is bit-reproducible from run to run, and the work is
 //                              proportional to the rows however skewed the code histogram is.
+//   vqvae_vq_ema_update_f32    the codebook update of VectorQuantizerEMA (arXiv 1711.00937 Appendix A.1): the same sorted,
+//                              fixed-order fp64 per-code sums, then exponential moving averages of counts and sums and the
+//                              Laplace-smoothed normalisation (optionally restarting codes whose average count is below a
+//                              threshold on rows of the batch).  Bit-reproducible, no host sync.
 //   vqvae_recon_loss_f32       main.py:75-76 and the three scalars of :81-83 packed into one 3-float buffer
 //                              (one D2H copy per step instead of three).
 //   vqvae_recon_loss_backward_f32   d/dx_hat of mean((x_hat - x)^2) / var.
@@ -275,6 +279,117 @@ __global__ __launch_bounds__(256) void recon_backward_kernel(const float *__rest
         grad[i] = s * (a[i] - b[i]);
 }
 
+// The per-code segmented sum shared by the codebook gradient and the EMA update: keys, stable radix sort of the rows by code,
+// per-code offsets, unit starts, fp64 partial sums per unit (workspace laid out by bwd_plan).  Fixed order throughout.
+static hipError_t launch_code_segsum(const BwdPlan &p, const float *z_e, const long long *idx, long long N, int K, int D, int HW,
+                                     int rowmajor, char *ws, hipStream_t st) {
+    unsigned *keys = reinterpret_cast<unsigned *>(ws + p.off_keys);
+    unsigned *keys_out = reinterpret_cast<unsigned *>(ws + p.off_keys_out);
+    int *vals = reinterpret_cast<int *>(ws + p.off_vals);
+    int *vals_out = reinterpret_cast<int *>(ws + p.off_vals_out);
+    int *offsets = reinterpret_cast<int *>(ws + p.off_offsets);
+    int *unit_start = reinterpret_cast<int *>(ws + p.off_units);
+    double *partial = reinterpret_cast<double *>(ws + p.off_partials);
+    long long grid = (N + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(vqb_keys_kernel, dim3((unsigned)grid), dim3(256), 0, st, idx, N, K, keys, vals);
+    size_t sb = p.sort_bytes;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + p.off_sort, sb, keys, keys_out, vals, vals_out, (int)N, 0,
+                                                      p.key_bits, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vqb_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st, keys_out, N, K,
+                       offsets);
+    hipLaunchKernelGGL(vqb_units_kernel, dim3(1), dim3(1024), 0, st, offsets, K, unit_start);
+    hipLaunchKernelGGL(vqb_segsum_kernel, dim3((unsigned)p.max_units), dim3(256), 0, st, z_e, vals_out, offsets,
+                       unit_start, K, D, HW, rowmajor, partial);
+    return hipSuccess;
+}
+
+// ---- EMA codebook update (arXiv 1711.00937 Appendix A.1; include/vqvae_hip.h, vqvae_vq_ema_update_f32) ----
+
+struct EmaPlan {
+    BwdPlan seg;                 // the segmented sum's workspace, first
+    size_t off_nk, off_n, total;
+};
+
+static EmaPlan ema_plan(long long N, int K, int D) {
+    EmaPlan p;
+    p.seg = bwd_plan(N, K, D);
+    p.off_nk = align_up(p.seg.total, 256);
+    p.off_n = align_up(p.off_nk + (size_t)K * sizeof(double), 256);
+    p.total = align_up(p.off_n + sizeof(double), 256);
+    return p;
+}
+
+// N_k <- decay N_k + (1 - decay) c_k in fp64 (c_k from the sorted offsets), kept unrounded in nk[]; n = sum_k N_k in a fixed
+// order (contiguous codes per thread, then a fixed tree).  One block: K <= 16384.
+__global__ __launch_bounds__(1024) void vqe_counts_kernel(const int *__restrict__ offsets, const float *__restrict__ cluster_size,
+                                                          int K, double decay, double *__restrict__ nk,
+                                                          double *__restrict__ n_total) {
+    __shared__ double part[1024];
+    const int tid = threadIdx.x;
+    const int per = (K + 1023) / 1024;
+    double local = 0.0;
+    for (int j = 0; j < per; ++j) {
+        const int k = tid * per + j;
+        if (k < K) {
+            const double v = decay * (double)cluster_size[k] + (1.0 - decay) * (double)(offsets[k + 1] - offsets[k]);
+            nk[k] = v;
+            local += v;
+        }
+    }
+    part[tid] = local;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (tid < o) part[tid] += part[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) *n_total = part[0];
+}
+
+// One thread per (k, c): s_k[c] from the code's unit partials (the codebook gradient's fixed order), m <- decay m + (1 - decay) s,
+// then e_k = m / ((N_k + eps) / (n + K eps) * n), or, with restart on and N_k < threshold, row r_k = min(floor(u_k N), N - 1) of z.
+// Everything in fp64, rounded once on the store.  Reads only ws / ema_w / z, so codebook may be any buffer of K x D floats.
+__global__ __launch_bounds__(256) void vqe_update_kernel(const float *__restrict__ z, const int *__restrict__ unit_start,
+                                                         const double *__restrict__ partial, const double *__restrict__ nk,
+                                                         const double *__restrict__ n_total, const float *__restrict__ uniforms,
+                                                         long long N, int K, int D, int HW, int rowmajor, double decay,
+                                                         double eps, double threshold, float *__restrict__ cluster_size,
+                                                         float *__restrict__ ema_w, float *__restrict__ codebook) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)K * D) return;
+    const int k = (int)(e / D), c = (int)(e - (long long)k * D);
+    double z4[4] = {0.0, 0.0, 0.0, 0.0};
+    int u = unit_start[k];
+    const int u1 = unit_start[k + 1];
+    for (; u + 4 <= u1; u += 4)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z4[j] += partial[(size_t)(u + j) * D + c];
+    for (int j = 0; u < u1; ++u, ++j) z4[j] += partial[(size_t)u * D + c];
+    const double s = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+    const double m = decay * (double)ema_w[e] + (1.0 - decay) * s;
+    const double Nk = nk[k];
+    double ek;
+    if (uniforms && Nk < threshold) {
+        long long r = (long long)floor((double)uniforms[k] * (double)N);
+        r = r < 0 ? 0 : (r > N - 1 ? N - 1 : r);
+        if (rowmajor) {
+            ek = (double)z[(size_t)r * D + c];
+        } else {
+            const long long bb = r / HW;
+            const int hw = (int)(r - bb * HW);
+            ek = (double)z[((size_t)bb * D + c) * HW + hw];
+        }
+    } else {
+        const double n = *n_total;
+        const double smoothed = (Nk + eps) / (n + (double)K * eps) * n;
+        ek = m / smoothed;
+    }
+    ema_w[e] = (float)m;
+    codebook[e] = (float)ek;
+    if (c == 0) cluster_size[k] = (float)Nk;
+}
+
 }  // namespace vqvae
 
 using namespace vqvae;
@@ -290,14 +405,17 @@ int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t
                           const float *grad_loss, int64_t B, int D, int H, int W, int K, float beta, int flags,
                           float *grad_z, float *grad_codebook, void *workspace, size_t workspace_bytes,
                           vqvae_stream_t stream) {
-    if (!z_e || !codebook || !idx || (!grad_z && !grad_codebook)) return VQVAE_ERR_NULL;
+    const bool commitment = (flags & VQVAE_VQ_BWD_COMMITMENT) != 0;
+    if (!z_e || !codebook || !idx || (!grad_z && !grad_codebook) || (commitment && !grad_z)) return VQVAE_ERR_NULL;
     if (B < 1 || D < 1 || H < 1 || W < 1 || K < 1) return VQVAE_ERR_SHAPE;
-    if (D > 256 || K > 16384) return VQVAE_ERR_UNSUPPORTED;
+    if (D > 256 || K > 16384 || (commitment && grad_codebook)) return VQVAE_ERR_UNSUPPORTED;
     const long long HW = (long long)H * W, N = (long long)B * HW;
     if (N > INT32_MAX || N * D > ((long long)1 << 40)) return VQVAE_ERR_OVERFLOW;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rowmajor = (flags & VQVAE_VQ_ROWMAJOR) ? 1 : 0;
     const double nd = (double)N * (double)D;
+    // the reference's z term is 2/(ND) (its commitment term carries no beta); the EMA quantizer's loss is beta * mse only
+    const float gz_scale = commitment ? (float)(2.0 * (double)beta / nd) : (float)(2.0 / nd);
     if (grad_z) {
         const long long total = N * D;
         const bool vec4 = rowmajor && (D & 3) == 0 &&
@@ -307,36 +425,54 @@ int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t
         if (grid > 65536) grid = 65536;
         hipLaunchKernelGGL(vqb_gradz_kernel, dim3((unsigned)grid), dim3(256), 0, st, z_e, codebook,
                            reinterpret_cast<const long long *>(idx), grad_zq, grad_loss, total, D, (int)HW, vec4 ? -1 : rowmajor,
-                           (float)(2.0 / nd), grad_z);
+                           gz_scale, grad_z);
     }
     if (grad_codebook) {
         const BwdPlan p = bwd_plan(N, K, D);
         if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
         char *ws = static_cast<char *>(workspace);
-        unsigned *keys = reinterpret_cast<unsigned *>(ws + p.off_keys);
-        unsigned *keys_out = reinterpret_cast<unsigned *>(ws + p.off_keys_out);
-        int *vals = reinterpret_cast<int *>(ws + p.off_vals);
-        int *vals_out = reinterpret_cast<int *>(ws + p.off_vals_out);
-        int *offsets = reinterpret_cast<int *>(ws + p.off_offsets);
-        double *partial = reinterpret_cast<double *>(ws + p.off_partials);
-        long long grid = (N + 255) / 256;
-        if (grid > 4096) grid = 4096;
-        hipLaunchKernelGGL(vqb_keys_kernel, dim3((unsigned)grid), dim3(256), 0, st,
-                           reinterpret_cast<const long long *>(idx), N, K, keys, vals);
-        size_t sb = p.sort_bytes;
-        hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + p.off_sort, sb, keys, keys_out, vals, vals_out, (int)N, 0,
-                                                          p.key_bits, st);
+        const hipError_t e = launch_code_segsum(p, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(vqb_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st, keys_out, N, K,
-                           offsets);
-        int *unit_start = reinterpret_cast<int *>(ws + p.off_units);
-        hipLaunchKernelGGL(vqb_units_kernel, dim3(1), dim3(1024), 0, st, offsets, K, unit_start);
-        hipLaunchKernelGGL(vqb_segsum_kernel, dim3((unsigned)p.max_units), dim3(256), 0, st, z_e, vals_out, offsets,
-                           unit_start, K, D, (int)HW, rowmajor, partial);
+        const int *offsets = reinterpret_cast<const int *>(ws + p.off_offsets);
+        const int *unit_start = reinterpret_cast<const int *>(ws + p.off_units);
+        const double *partial = reinterpret_cast<const double *>(ws + p.off_partials);
         hipLaunchKernelGGL(vqb_codebook_grad_kernel, dim3((unsigned)(((long long)K * D + 255) / 256)), dim3(256), 0,
                            st, codebook, offsets, unit_start, partial, grad_loss, K, D, 2.0 * (double)beta / nd,
                            grad_codebook);
     }
+    return (int)hipGetLastError();
+}
+
+size_t vqvae_vq_ema_workspace_bytes(int64_t N, int K, int D) {
+    if (N < 1 || N > INT32_MAX || K < 1 || K > 16384 || D < 1 || D > 256) return 0;
+    return ema_plan(N, K, D).total;
+}
+
+int vqvae_vq_ema_update_f32(const float *z_e, const int64_t *idx, int64_t B, int D, int H, int W, int K, double decay,
+                            double eps, double threshold, const float *uniforms, int flags, float *ema_cluster_size,
+                            float *ema_w, float *codebook, void *workspace, size_t workspace_bytes, vqvae_stream_t stream) {
+    if (!z_e || !idx || !ema_cluster_size || !ema_w || !codebook) return VQVAE_ERR_NULL;
+    if (B < 1 || D < 1 || H < 1 || W < 1 || K < 1) return VQVAE_ERR_SHAPE;
+    const long long HW = (long long)H * W, N = (long long)B * HW;
+    if (D > 256 || K > 16384 || N > INT32_MAX || (flags & ~VQVAE_VQ_ROWMAJOR)) return VQVAE_ERR_UNSUPPORTED;
+    if (!(decay >= 0.0 && decay <= 1.0) || !(eps > 0.0)) return VQVAE_ERR_UNSUPPORTED;
+    const EmaPlan p = ema_plan(N, K, D);
+    if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rowmajor = (flags & VQVAE_VQ_ROWMAJOR) ? 1 : 0;
+    char *ws = static_cast<char *>(workspace);
+    const hipError_t e = launch_code_segsum(p.seg, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
+    if (e != hipSuccess) return (int)e;
+    const int *offsets = reinterpret_cast<const int *>(ws + p.seg.off_offsets);
+    const int *unit_start = reinterpret_cast<const int *>(ws + p.seg.off_units);
+    const double *partial = reinterpret_cast<const double *>(ws + p.seg.off_partials);
+    double *nk = reinterpret_cast<double *>(ws + p.off_nk);
+    double *n_total = reinterpret_cast<double *>(ws + p.off_n);
+    hipLaunchKernelGGL(vqe_counts_kernel, dim3(1), dim3(1024), 0, st, offsets, ema_cluster_size, K, decay, nk, n_total);
+    const bool restart = uniforms && threshold >= 0.0;
+    hipLaunchKernelGGL(vqe_update_kernel, dim3((unsigned)(((long long)K * D + 255) / 256)), dim3(256), 0, st, z_e, unit_start,
+                       partial, nk, n_total, restart ? uniforms : nullptr, N, K, D, (int)HW, rowmajor, decay, eps,
+                       restart ? threshold : 0.0, ema_cluster_size, ema_w, codebook);
     return (int)hipGetLastError();
 }
 

@@ -21,6 +21,7 @@ FWD_CONV_BF16_SPLIT = 0x1000
 FWD_CONV_EXACT_FP32 = 0x2000
 FWD_DEBUG_ZE = 0x4000            # tests: the fused encoder+quantizer kernel also writes its z_e (include/vqvae_hip.h)
 VQ_UNITS32_8WAVES = 0x400
+VQ_BWD_COMMITMENT = 0x800        # vqvae_vq_backward_f32: grad_z of beta * mse only (VectorQuantizerEMA)
 
 
 def _stream_ptr(t: torch.Tensor) -> int:
@@ -121,3 +122,50 @@ def vq_decode_indices(idx: torch.Tensor, codebook: torch.Tensor, B: int, H: int,
         _lib.check(_lib.load().vqvae_vq_decode_indices_f32(idx.data_ptr(), codebook.data_ptr(), B, D, H, W, K,
                                                            out.data_ptr(), _stream_ptr(idx)))
     return out
+
+
+def vq_ema_workspace(N: int, K: int, D: int, device) -> torch.Tensor:
+    n = _lib.load().vqvae_vq_ema_workspace_bytes(N, K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"EMA codebook update: N={N}, K={K}, D={D} not supported (K <= 16384, D <= 256, N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_ema_update(z_e: torch.Tensor, idx: torch.Tensor, ema_cluster_size: torch.Tensor, ema_w: torch.Tensor,
+                  codebook: torch.Tensor, decay: float, eps: float = 1e-5, *, threshold: float | None = None,
+                  uniforms: torch.Tensor | None = None, rowmajor: bool = False, workspace: torch.Tensor | None = None):
+    """One EMA codebook update (arXiv 1711.00937 Appendix A.1; vqvae_vq_ema_update_f32) from the rows z_e and the indices the
+    forward assigned them.  Writes ema_cluster_size (K,), ema_w (K, D) and codebook (K, D) in place through their data pointers
+    (no autograd version bump: the caller owns that).  threshold / uniforms: restart codes whose averaged count is below
+    threshold on the rows floor(u_k N) of z_e; both or neither.  z_e: (B,D,H,W), or (B,H,W,D) when rowmajor."""
+    _check_dev("z_e", z_e)
+    _check_dev("idx", idx, torch.int64)
+    for name, t in (("ema_cluster_size", ema_cluster_size), ("ema_w", ema_w), ("codebook", codebook)):
+        _check_dev(name, t)
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous (it is written in place)")
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K = codebook.shape[0]
+    if codebook.shape != (K, D) or ema_w.shape != (K, D) or ema_cluster_size.shape != (K,) or idx.numel() != B * H * W:
+        raise ValueError("shape mismatch between z_e, idx, ema_cluster_size, ema_w and codebook")
+    if (threshold is None) != (uniforms is None):
+        raise ValueError("restart needs both threshold and uniforms")
+    if uniforms is not None:
+        _check_dev("uniforms", uniforms)
+        uniforms = uniforms.contiguous()
+        if uniforms.numel() != K:
+            raise ValueError("uniforms must hold K values")
+    z_e = z_e.contiguous()
+    idx = idx.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_ema_workspace(B * H * W, K, D, dev)
+        _lib.check(_lib.load().vqvae_vq_ema_update_f32(
+            z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, float(decay), float(eps),
+            float(threshold) if threshold is not None else -1.0, uniforms.data_ptr() if uniforms is not None else None,
+            VQ_ROWMAJOR if rowmajor else 0, ema_cluster_size.data_ptr(), ema_w.data_ptr(), codebook.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
+    return codebook

@@ -185,6 +185,70 @@ class VectorQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
+class VectorQuantizerEMA(VectorQuantizer):
+    """VectorQuantizer whose codebook follows exponential moving averages of the encoder outputs assigned to each code
+    (arXiv 1711.00937 Appendix A.1; Sonnet's VectorQuantizerEMA) instead of a gradient.
+
+    State: `embedding.weight` (a Parameter with requires_grad=False: the codebook, same state_dict key and whole-path packing as
+    VectorQuantizer), and the buffers `ema_cluster_size` (K,) = N_k (initially 0) and `ema_w` (K, D) = m_k (initially the initial
+    codebook).  Every forward in training mode -- with or without grad -- runs one update (vqvae_vq_ema_update_f32) from that
+    forward's z and indices, then copies the new codebook into `embedding.weight` in place (its `_version` moves, so every cache
+    keyed on it re-keys).  Eval mode never updates.  The forward's outputs are those of the codebook BEFORE the update; the loss
+    is the commitment term only, beta * mean((z_q - z)^2), and the codebook gets no gradient.
+
+    restart_threshold: codes whose N_k falls below it take a row of the batch instead (row floor(u_k N), u drawn on the device from
+    `generator`, or the default CUDA generator, on every update).  None: no restart.  Under data parallelism each replica updates
+    from its own shard; the statistics are not merged across ranks."""
+
+    def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None):
+        super().__init__(n_e, e_dim, beta)
+        self.decay = float(decay)
+        self.eps = float(eps)
+        self.restart_threshold = None if restart_threshold is None else float(restart_threshold)
+        self.generator = generator
+        self.embedding.weight.requires_grad_(False)
+        self.register_buffer("ema_cluster_size", torch.zeros(n_e))
+        self.register_buffer("ema_w", self.embedding.weight.detach().clone())
+
+    def _ema_update(self, z, idx, rowmajor):
+        w = self.embedding.weight
+        side = _cache.side(self)
+        N = idx.numel()
+        wkey = (str(w.device), torch.cuda.current_stream(w.device).cuda_stream, N)
+        table = side.setdefault("ema_ws", {})
+        ws = _cache.lru_get(table, wkey)
+        if ws is None:
+            ws = F_hip.vq_ema_workspace(N, self.n_e, self.e_dim, w.device)
+            _cache.lru_put(table, wkey, ws, 4)
+        uniforms = None
+        if self.restart_threshold is not None:
+            uniforms = torch.rand(self.n_e, device=w.device, generator=self.generator)
+        new = torch.empty_like(w, memory_format=torch.contiguous_format)
+        F_hip.vq_ema_update(z, idx, self.ema_cluster_size, self.ema_w, new, self.decay, self.eps,
+                            threshold=self.restart_threshold, uniforms=uniforms, rowmajor=rowmajor, workspace=ws)
+        with torch.no_grad():
+            w.copy_(new)
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (beta * mse, z_q, perplexity, min_encoding_indices, hist) against the codebook as it was on entry; then, in training
+        mode, one EMA update of the codebook."""
+        w = self.embedding.weight
+        ws, prepared, key, slot = self._workspace()
+        if not prepared:
+            slot[1] = None
+        if torch.is_grad_enabled() and z.requires_grad:
+            from .training import VQEMAStraightThrough      # HIP forward + HIP commitment-only backward
+            out = VQEMAStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared)
+        else:
+            mse, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w.detach(), 0.0, rowmajor=rowmajor, workspace=ws,
+                                                               prepared=prepared, want_zq=want_zq)
+            out = (mse * self.beta, z_q, perplexity, idx, hist)
+        slot[1] = key
+        if self.training:
+            self._ema_update(z.detach(), out[3], rowmajor)
+        return out
+
+
 class ResidualLayer(nn.Module):
     """Parameter holder mirroring models/residual.py:8-29."""
 
@@ -285,11 +349,18 @@ class VQVAE(nn.Module):
     """Mirrors models/vqvae.py:10-44."""
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
-                 save_img_embedding_map=False):
+                 save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None):
         super().__init__()
         self.encoder = Encoder(3, h_dim, n_res_layers, res_h_dim)
         self.pre_quantization_conv = nn.Conv2d(h_dim, embedding_dim, kernel_size=1, stride=1)
-        self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta)
+        if ema_decay is None:
+            if restart_threshold is not None:
+                raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
+            self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta)
+        else:
+            # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
+            self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,
+                                                          restart_threshold=restart_threshold)
         self.decoder = Decoder(embedding_dim, h_dim, n_res_layers, res_h_dim)
         if save_img_embedding_map:
             self.img_to_embedding_map = {i: [] for i in range(n_embeddings)}
@@ -340,7 +411,7 @@ class VQVAE(nn.Module):
                 tensors[f] = params[k]
         # beta is packed into VqvaeDims: a changed m.vector_quantization.beta must repack, as models/quantizer.py:63-64 reads it per call
         key = tuple((t.data_ptr(), t._version) for t in tensors.values()) + (str(tensors["enc0_w"].device),
-                                                                              float(self.vector_quantization.beta))
+                                                                              self._packed_beta())
         hit = _cache.side(self).get("c_weights")
         if hit is not None and hit[0] == key:
             _cache.wait_ready(hit[3], tensors["enc0_w"].device)          # packed on another stream a moment ago?
@@ -349,7 +420,7 @@ class VQVAE(nn.Module):
         w0 = tensors["enc0_w"]
         dims = _lib.VqvaeDims(self.encoder.conv_stack[4].weight.shape[0], tensors["enc_res_w1"].shape[0] if n_res else 1,
                               n_res, self.vector_quantization.n_e, self.vector_quantization.e_dim, w0.shape[1],
-                              float(self.vector_quantization.beta))
+                              self._packed_beta())
         nbytes = L.vqvae_weights_packed_bytes(dims)
         if nbytes == 0:
             raise VqvaeHipError("model dimensions not supported by the gfx950 whole-path entry points")
@@ -391,6 +462,11 @@ class VQVAE(nn.Module):
         _cache.side(self)["c_weights"] = (key, cw, (keep, packed), ready)
         _cache.side(self)["c_scheme_hint"] = hint
         return cw, (keep, packed)
+
+    def _packed_beta(self):
+        """beta as the whole path's loss reads it: the reference's (1 + beta) mse for VectorQuantizer; for VectorQuantizerEMA 0, so
+        that the path returns mse itself and forward() scales it to the commitment loss beta * mse"""
+        return 0.0 if isinstance(self.vector_quantization, VectorQuantizerEMA) else float(self.vector_quantization.beta)
 
     def scheme_hint(self):
         """-> (flags, per-layer input-channel spread in binades): FWD_CONV_BF16_SPLIT when this checkpoint's weights put the default
@@ -507,7 +583,14 @@ class VQVAE(nn.Module):
             x_hat = A_hip.decoder_forward_train(self.decoder, z_q)
             return embedding_loss, x_hat, perplexity
         _require_forward_only(x, *self.parameters())
-        if C_hip.get_conv_backend() == "hip" and not verbose and x.is_cuda and x.dtype == torch.float32:
+        vq = self.vector_quantization
+        ema = isinstance(vq, VectorQuantizerEMA)
+        # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it)
+        if (C_hip.get_conv_backend() == "hip" and not verbose and x.is_cuda and x.dtype == torch.float32
+                and not (ema and vq.training)):
+            if ema:
+                mse, x_hat, perplexity = self._forward_c(x)
+                return mse * vq.beta, x_hat, perplexity
             return self._forward_c(x)                 # one ctypes call: vqvae_forward_f32
         # encoder + 1x1 pre-quantisation conv, activations kept row-major (B,H,W,C)
         z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
@@ -542,7 +625,8 @@ class VQVAE(nn.Module):
         from . import _lib, conv as C_hip
         if C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32:
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
-            _, _, _, idx, _ = self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)
+            # (VectorQuantizer's quantize: an EMA quantizer in training mode must not update from encode())
+            _, _, _, idx, _ = VectorQuantizer.quantize(self.vector_quantization, z_e, rowmajor=True, want_zq=False)
             return idx
         L = _lib.load()
         x = x.contiguous()
