@@ -223,10 +223,12 @@ def test_map_resident_weight_gradient_vs_fp64_sum(k, s, CA, CB, exact, monkeypat
 
 @pytest.mark.parametrize("k,s,CA,CB", [(3, 1, 128, 128), (4, 2, 128, 64), (3, 1, 32, 128), (1, 1, 128, 32)])
 def test_two_term_weight_gradient_across_image_scales(k, s, CA, CB):
-    """conv_wgrad_map8_h2_kernel carries one power-of-two scale per image and operand tile and rescales its accumulators between
-    images: images whose magnitudes differ by up to 10^12 in one range (both directions, both operands), an all-zero image, an
-    image below the 2^-60 cut and one channel 10^4 above the rest -- against the defining sum in fp64, relative to each
-    (ca, cb) filter's own maximum (2e-5) -- and the same bits from the second call."""
+    """conv_wgrad_map8_h2_kernel carries one power-of-two scale per image and operand tile: images whose magnitudes differ by up to
+    10^12 (both directions, both operands), an all-zero image, an image 10^-18 and one channel 10^4 above the rest -- against the
+    defining sum in fp64, relative to each (ca, cb) filter's own maximum (2e-5) -- and the same bits from the second call.  At
+    B = 37 the host plans min(ceil(512 / tiles), B) = B image ranges: every range holds ONE image, so what this checks is each
+    image's own scales, the way out of the range (v_ldexp) and the fixed-order sum over ranges.  The rescaling between the images
+    of a range and the 2^-60 rule are exercised at eight images per range by tests/test_train_reductions_gpu.py."""
     from vqvae_amd import autograd_conv as A
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(k * 7 + CA)
@@ -252,8 +254,9 @@ def test_two_term_weight_gradient_across_image_scales(k, s, CA, CB):
     tile = ref.abs().amax(dim=(2, 3)).amax(dim=0 if False else 1, keepdim=True)
     assert bool(((err <= lim) | (err <= 2e-7 * tile)).all()), float((err / lim).max())
     assert torch.equal(got, A.conv_wgrad(a.to(dev), bt.to(dev), k, s, pad))
-    # a run of EVER SMALLER images (a factor of 10 per image and operand, 10^6 ... 10^-30): the accumulators must not climb after
-    # them binade by binade (the first version's rule, relative to the previous image, overflowed here: tests/test_wgrad_scheme_cpu.py)
+    # a run of EVER SMALLER images (a factor of 10 per image and operand, 10^6 ... 10^-30), one per range here: every image on its
+    # own scale, summed over ranges (the run inside one range, where the first version's rule relative to the previous image
+    # overflowed: tests/test_wgrad_scheme_cpu.py and the "falling" pattern of tests/test_train_reductions_gpu.py)
     a2 = torch.randn(B, 8, 8, CA, generator=g) * (10.0 ** (6 - torch.arange(B, dtype=torch.float32)))[:, None, None, None]
     b2 = torch.randn(B, 8 * s, 8 * s, CB, generator=g) * (10.0 ** (6 - torch.arange(B, dtype=torch.float32)))[:, None, None, None]
     ref2 = torch.nn.grad.conv2d_weight(b2.permute(0, 3, 1, 2).double(), (CA, CB, k, k), a2.permute(0, 3, 1, 2).double(), stride=s, padding=pad)

@@ -5,8 +5,11 @@ found the first version's rule -- relative to the PREVIOUS image -- overflowing 
 SCHEME (the statements of the kernel's header), on a 1x1 layer so that the sum is a plain matrix product:
   * well-scaled operands: error at the fp32 GEMM's own level;
   * images 10^12 apart in both directions, an all-zero image, one below the 2^-60 cut, the first image small: still there;
+  * an all-zero operand tile in front of images near 1e-22: it takes no part in the 2^-60 rule (it used to count as a maximum near
+    2^14 and hold the images after it to fp16's subnormals);
   * the accumulator never overflows and the rescaling is exact (powers of two only).
-The GPU counterpart is tests/test_training_gpu.py::test_two_term_weight_gradient_across_image_scales."""
+The GPU counterparts are tests/test_training_gpu.py::test_two_term_weight_gradient_across_image_scales and the scale patterns of
+tests/test_train_reductions_gpu.py."""
 import numpy as np
 
 
@@ -32,15 +35,17 @@ def _emulate(a, b):
     e_acc, e_min, first = 0, 0, True
     for i in range(B):
         ka, kb = _scale_exp(np.abs(a[i]).max()), _scale_exp(np.abs(b[i]).max())
-        e_min = ka + kb if first else min(e_min, ka + kb)
-        if ka + kb > e_min + 60:                                       # (relative to the LARGEST image so far, not to the previous one)
-            kb = e_min + 60 - ka
+        zero = np.abs(a[i]).max() == 0 or np.abs(b[i]).max() == 0      # exact zeros: in neither rule
+        if not zero:
+            e_min = ka + kb if first else min(e_min, ka + kb)
+            if ka + kb > e_min + 60:                                   # (relative to the LARGEST image so far, not to the previous one)
+                kb = e_min + 60 - ka
         a1, a2 = _split(a[i], ka)
         b1, b2 = _split(b[i], kb)
         e_img = ka + kb
-        if first:
+        if not zero and first:
             e_acc, first = e_img, False
-        elif e_img != e_acc:
+        elif not zero and e_img != e_acc:
             d = e_img - e_acc
             f = np.float32(0.0) if d < -120 else np.float32(2.0 ** d)
             before = acc.copy()
@@ -88,4 +93,21 @@ def test_images_decades_apart_zero_images_and_the_cut():
     assert e < 2e-6 and e < 8 * f + 1e-7, (e, f)
     # and the other order: the largest image first, then ever smaller ones
     e, f = _case(np.sort(fa)[::-1], np.sort(fb)[::-1], seed=2)
+    assert e < 2e-6 and e < 8 * f + 1e-7, (e, f)
+
+
+def test_zero_tile_takes_no_part_in_the_scale_rules():
+    """an all-zero A (or Bt) tile first, then images with A ~ 1e-22: the error stays at the fp32 GEMM's level, as without the zero tile"""
+    for which in ("a", "b"):
+        fa, fb = np.full(8, 1e-22), np.ones(8)
+        (fa if which == "a" else fb)[0] = 0.0
+        e, f = _case(fa, fb, seed=3, B=8)
+        assert e < 2e-6 and e < 8 * f + 1e-7, (which, e, f)
+        fa[0], fb[0] = 1e-22, 1.0                                      # the same images without the zero tile
+        e0, _ = _case(fa, fb, seed=3, B=8)
+        assert e < 2e-6 and e0 < 2e-6, (e, e0)
+    # in the middle, between tiny images and after a large one: the sums before it are neither flushed nor rescaled
+    fa = np.array([1e-20, 1e-20, 0.0, 1e-20, 1e-20, 1e-20])
+    fb = np.array([1e-20, 1e-20, 1e6, 1e-20, 1e-20, 1e-20])
+    e, f = _case(fa, fb, seed=4, B=6)
     assert e < 2e-6 and e < 8 * f + 1e-7, (e, f)

@@ -290,7 +290,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_map8_kernel(const float *__
 //     sits in its registers (no pass over the tensors, no maxima handed in).  Images of one range carry different scales, so the
 //     fp32 accumulators live on the CURRENT image's scale 2^(ka + kb) and are multiplied by the exact power of two between two
 //     images; the partial sums leave through v_ldexp.  An image more than 2^60 below the LARGEST one of the range so far keeps a
-//     coarser scale, so that the accumulators cannot overflow however the magnitudes are ordered.  Relative error per product
+//     coarser scale, so that the accumulators cannot overflow however the magnitudes are ordered; an image with an all-zero A or Bt
+//     tile adds exact zeros and takes no part in either rule (it used to count as a maximum near 2^14: images near 1e-22 after it
+//     were held to fp16's subnormals, and a zero A tile beside a large Bt one flushed the sums of tiny images before it).  Relative error per product
 //     <= 2^-21 as in the forward kernels (representation 2^-23 per operand + the dropped h2 h2 term); elements 2^17 below their image tile's maximum keep fewer bits
 //     -- absolute error <= 2^-39 of the tile maxima's product -- which is the forward scheme's statement for activations.
 //   * Fixed summation order as before (image order inside a range, ranges by conv_wgrad_reduce_kernel): bit-reproducible.
@@ -372,7 +374,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_map8_h2_kernel(const float 
     };
 
     int e_acc = 0, e_min = 0;                                                   // the accumulators hold sum * 2^e_acc; e_min: the largest image's scale
-    bool first = true;
+    bool first = true;                                                          // no image with both tiles nonzero yet
     if (b_lo < b_hi) load_image(b_lo);
     for (long long b = b_lo; b < b_hi; ++b) {
         // ---- this image's two scales: maxima of the A tile and of the Bt tile over the workgroup ----
@@ -402,9 +404,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_map8_h2_kernel(const float 
         // its scale (sums at the largest image's own scale stay below 2^48: 2^30 per product, 64 pixels, <= 2^12 images): such
         // an image keeps a coarser scale, at most 2^60 finer than the LARGEST image's -- not than the previous image's, or a run
         // of ever smaller images would climb 60 binades at a time (tests/test_wgrad_scheme_cpu.py found that) -- and its whole
-        // contribution is below 2^-60 of that image's
-        e_min = first ? ka + kb : (ka + kb < e_min ? ka + kb : e_min);
-        if (ka + kb > e_min + 60) kb = e_min + 60 - ka;
+        // contribution is below 2^-60 of that image's.  An image with an all-zero A or Bt tile adds exact zeros: scale_exp(0) = 0 is
+        // no measure of it, so it neither enters e_min (a phantom maximum near 2^14 would pin the tiny images after it to 2^60 of
+        // that) nor moves the accumulators (a step below 2^-120 would flush the sums of the images before it)
+        const bool zero_img = ma == 0.0f || mb == 0.0f;
+        if (!zero_img) {
+            e_min = first ? ka + kb : (ka + kb < e_min ? ka + kb : e_min);
+            if (ka + kb > e_min + 60) kb = e_min + 60 - ka;
+        }
         const int e_img = __builtin_amdgcn_readfirstlane(ka + kb);
         const float sa = __builtin_ldexpf(1.0f, ka), sb = __builtin_ldexpf(1.0f, kb);
         // ---- convert and park: [term][tile][pixel][32 ch], 8 bytes per lane and term ----
@@ -433,9 +440,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_map8_h2_kernel(const float 
         }
         __syncthreads();
         if (b + 1 < b_hi) load_image(b + 1);                // in flight under this image's matrix work
-        // ---- the accumulators follow the image's scale ----
-        if (first) { e_acc = e_img; first = false; }
-        else if (e_img != e_acc) {
+        // ---- the accumulators follow the image's scale (the products of a zero image are zeros at any scale) ----
+        if (!zero_img && first) { e_acc = e_img; first = false; }
+        else if (!zero_img && e_img != e_acc) {
             const int d = e_img - e_acc;
             const float f = d < -120 ? 0.0f : __builtin_ldexpf(1.0f, d);
 #pragma unroll
