@@ -53,8 +53,12 @@ def _gate(t):
     return torch.tanh(a) * torch.sigmoid(g)
 
 
-def forward(p, x, label, n_layers):
-    """logits (B, K, H, W) of GatedPixelCNN.forward; p: name -> tensor (the state_dict's names)"""
+def forward(p, x, label, n_layers, head_mask=None, keep=None):
+    """logits (B, K, H, W) of GatedPixelCNN.forward; p: name -> tensor (the state_dict's names).
+    head_mask ((B, 512, H, W) of 0 / 1): the head's ReLU becomes `pre * head_mask`, i.e. the ReLU decisions are given instead of
+    taken from this run's own pre-activations (tests/pixelcnn_envelope.py: a pre-activation within rounding of zero may fall on
+    either side in two correct implementations, and one such decision moves a gradient summed over many pixels by more than the
+    tolerance).  keep: a dict that receives the head's pre-activation under "pre" (detached)."""
     B, H, W = x.shape
     t = F.embedding(x.reshape(-1), p["embedding.weight"]).view(B, H, W, -1).permute(0, 3, 1, 2)
     x_v = x_h = t
@@ -69,17 +73,23 @@ def forward(p, x, label, n_layers):
         out = _gate(v2h + h_horiz + h)
         out_h = F.conv2d(out, p[q + "horiz_resid.weight"], p[q + "horiz_resid.bias"])
         x_v, x_h = out_v, (out_h + x_h if i > 0 else out_h)
-    t = F.relu(F.conv2d(x_h, p["output_conv.0.weight"], p["output_conv.0.bias"]))
+    pre = F.conv2d(x_h, p["output_conv.0.weight"], p["output_conv.0.bias"])
+    if keep is not None:
+        keep["pre"] = pre.detach()
+    t = F.relu(pre) if head_mask is None else pre * head_mask.to(pre.dtype)
     return F.conv2d(t, p["output_conv.2.weight"], p["output_conv.2.bias"])
 
 
-def loss_and_grads(state, x, label, n_layers, dtype=torch.float64):
-    """-> (loss, grad_logits (B,K,H,W), {name: grad}) of the reference criterion (gated_pixelcnn.py:91-96), on the CPU"""
+def loss_and_grads(state, x, label, n_layers, dtype=torch.float64, head_mask=None, keep=None):
+    """-> (loss, grad_logits (B,K,H,W), {name: grad}) of the reference criterion (gated_pixelcnn.py:91-96), on the CPU.
+    head_mask, keep: as in `forward`; keep also receives the logits under "logits"."""
     p = {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in state.items()}
     make_causal(p)
     x, label = x.cpu(), label.cpu()
-    logits = forward(p, x, label, n_layers)
+    logits = forward(p, x, label, n_layers, head_mask, keep)
     logits.retain_grad()
+    if keep is not None:
+        keep["logits"] = logits.detach()
     K = logits.shape[1]
     loss = F.cross_entropy(logits.permute(0, 2, 3, 1).contiguous().view(-1, K), x.view(-1))
     loss.backward()
