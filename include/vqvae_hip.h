@@ -482,6 +482,37 @@ VQVAE_API size_t vqvae_bias_grad_wide_workspace_bytes(int C);
 VQVAE_API int vqvae_bias_grad_wide_f32(const float *grad_y, int64_t P, int C, float *grad_b, void *workspace, size_t workspace_bytes,
                                        vqvae_stream_t stream);
 
+/* ------------------------------------------------------- what a training reduction would launch (csrc/train_reduce.hip)
+ * Host logic only (no GPU needed; without a device it assumes 256 CUs): the plan the entry point itself launches from, for tests and
+ * tools that must know how a batch is split.  `what` selects the reduction and the meaning of dims[0 .. ndims):
+ *   VQVAE_TRAIN_PLAN_CONV_WGRAD       B, HA, WA, CA, HB, WB, CB, k, stride, pad, bt_nchw, flags      (vqvae_conv_wgrad_ex_f32)
+ *   VQVAE_TRAIN_PLAN_CONV_TAPS_WGRAD  B, H, W, Cin, Cout, ntaps, dy[0 .. ntaps), dx[0 .. ntaps)      (vqvae_conv_taps_wgrad_f32)
+ *   VQVAE_TRAIN_PLAN_BIAS_GRAD        P = B * HW, C                                                  (vqvae_bias_grad_f32)
+ *   VQVAE_TRAIN_PLAN_BIAS_GRAD_WIDE   P, C                                                           (vqvae_bias_grad_wide_f32)
+ *   VQVAE_TRAIN_PLAN_SEGSUM           n, keys, C      (the sorted segmented sum of vqvae_vq_backward_f32: N, K, D; of
+ *                                                      vqvae_vq_ema_update_f32: N, K, D; of vqvae_gather_rows_backward_f32: n, rows, C)
+ * out[0 .. 8): the kernel (VQVAE_TRAIN_KERNEL_*); the items that are split (images for the map-resident and image-operand kernels,
+ * 32-pixel blocks for the per-tap kernels, rows); splits; items per split; items in the last split (0: it is empty); the split count
+ * the rule asks for before it is clamped to its cap and to the items; and two kernel-specific values: waves along ca and cb
+ * (CONV_WGRAD_MAP8*), tap groups and taps per group (CONV_TAPS_WGRAD_MAP), rows per unit and the unit bound (SEGSUM: its splits are
+ * the unit bound too -- how many units hold rows depends on the data, ceil(count_k / rows per unit) per key), else 0.
+ * Returns VQVAE_OK, or the error the entry point gives for these dimensions (VQVAE_ERR_SHAPE also for a wrong ndims).             */
+#define VQVAE_TRAIN_PLAN_CONV_WGRAD      0
+#define VQVAE_TRAIN_PLAN_CONV_TAPS_WGRAD 1
+#define VQVAE_TRAIN_PLAN_BIAS_GRAD       2
+#define VQVAE_TRAIN_PLAN_BIAS_GRAD_WIDE  3
+#define VQVAE_TRAIN_PLAN_SEGSUM          4
+#define VQVAE_TRAIN_KERNEL_CONV_WGRAD_IMG      1   /* conv_wgrad_img_kernel                                  */
+#define VQVAE_TRAIN_KERNEL_CONV_WGRAD_MAP8_H2  2   /* conv_wgrad_map8_h2_kernel (two-term fp16 products)      */
+#define VQVAE_TRAIN_KERNEL_CONV_WGRAD_MAP8     3   /* conv_wgrad_map8_kernel (fp32 products)                  */
+#define VQVAE_TRAIN_KERNEL_CONV_WGRAD          4   /* conv_wgrad_kernel: any map, per tap                     */
+#define VQVAE_TRAIN_KERNEL_CONV_TAPS_WGRAD_MAP 5   /* taps_wgrad_map_kernel                                   */
+#define VQVAE_TRAIN_KERNEL_CONV_TAPS_WGRAD_BLK 6   /* taps_wgrad_blk_kernel                                   */
+#define VQVAE_TRAIN_KERNEL_BIAS_GRAD           7   /* bias_grad_partial_kernel                                */
+#define VQVAE_TRAIN_KERNEL_BIAS_GRAD_WIDE      8   /* bias_wide_partial_kernel                                */
+#define VQVAE_TRAIN_KERNEL_SEGSUM              9   /* segsum_kernel                                           */
+VQVAE_API int vqvae_train_reduction_plan(int what, const int64_t *dims, int ndims, int64_t *out);
+
 /* ------------------------------------------------------- GatedPixelCNN prior: cached sampler (csrc/pixelcnn_sample.hip)
  * GatedPixelCNN.generate (pixelcnn/models.py:129-142) without its H*W full forwards.  The prior is causal, so the sampler keeps each
  * layer's state and computes only what the next pixel needs: per row, the vertical stacks (hv_L, out_v) and vert_to_horiz of every

@@ -3,10 +3,10 @@ INFRASTRUCTURE ONLY; nothing under vqvae_amd/ imports it.
 
 The tables name the shapes at which the prior's kernels change form: the batch decides between the four-wave and the eight-wave
 ("wide") tile-8 conv kernel and how many images a weight-gradient split sums; the channel counts decide between the tile-8 and the
-generic conv kernels and between the map-resident and the per-tap weight-gradient kernels.  The planner mirrors below restate the
-host code's arithmetic (csrc/conv.hip conv_forward_impl, csrc/conv_host.h conv_route, csrc/pixelcnn_backward.hip) in plain
-Python, so that the CPU test can say which case reaches which branch: if a planner is retuned, that test names the case that lost
-its purpose.
+generic conv kernels and between the map-resident and the per-tap weight-gradient kernels.  The forward planner mirrors below
+restate the host code's arithmetic (csrc/conv.hip conv_forward_impl, csrc/conv_host.h conv_route) in plain Python; the training
+reductions are asked of the library itself (vqvae_train_reduction_plan: the plan the entry point launches from).  So the CPU test can
+say which case reaches which branch: if a planner is retuned, that test names the case that lost its purpose.
 
 The ReLU-decision rule.  The head's ReLU sits on B H W 512 pre-activations; a few of them lie within rounding of zero, two correct
 implementations decide them differently, and one such decision moves a gradient summed over all pixels by more than the house
@@ -109,44 +109,17 @@ def model_convs(dim, K):
     return fwd + [("d_" + n, co, ci) for n, ci, co in fwd]
 
 
-def taps_frame(taps, H, W):
-    """the zero frame of the map-resident kernel's x map: (PH, PW)"""
-    ys, xs = [t[0] for t in taps], [t[1] for t in taps]
-    return H + max(0, max(ys)) - min(0, min(ys)), W + max(0, max(xs)) - min(0, min(xs))
+def taps_wgrad_plan(B, H, W, Cin, Cout, taps):
+    """what vqvae_conv_taps_wgrad_f32 would launch, from the library: .kernel is 'taps_wgrad_map' (items = images: per_split images
+    per split, splits, last) or 'taps_wgrad_blk' (items = 32-pixel blocks; want = the split count before the 64-split clamp)"""
+    from vqvae_amd import _lib
+    return _lib.train_reduction_plan("conv_taps_wgrad", B, H, W, Cin, Cout, len(taps), *[t[0] for t in taps], *[t[1] for t in taps])
 
 
-def wgrad_is_map(H, W, Cin, Cout, taps):
-    """taps_map_ok: maps of at most 8 x 8, 32-channel multiples, both maps within 96 KiB of LDS"""
-    PH, PW = taps_frame(taps, H, W)
-    return H <= 8 and W <= 8 and Cin % 32 == 0 and Cout % 32 == 0 and (64 + PH * PW) * 68 * 4 <= 96 * 1024
-
-
-def wgrad_map_plan(B, Cin, Cout, ntaps):
-    """-> (images per split, splits, images in the last split) of taps_wgrad_map_kernel"""
-    groups = cdiv(ntaps, 8)
-    tiles = cdiv(Cout, 64) * cdiv(Cin, 64) * groups
-    ns = min(cdiv(256, tiles), B)
-    ips = cdiv(B, ns)
-    ns = cdiv(B, ips)
-    return ips, ns, B - (ns - 1) * ips
-
-
-def wgrad_blk_plan(B, H, W, Cin, Cout, ntaps):
-    """-> (32-pixel blocks, the split count before the 64-split clamp, blocks per split, splits) of taps_wgrad_blk_kernel"""
-    nblk = cdiv(B * H * W, 32)
-    tiles = cdiv(Cout, 64) * cdiv(Cin, 64)
-    want = min(cdiv(8 * 256, tiles * ntaps), cdiv(nblk, 8))
-    ns = max(1, min(want, 64))
-    per = cdiv(nblk, ns)
-    return nblk, want, per, cdiv(nblk, per)
-
-
-def bias_plan(P):
-    """-> (blocks before the 512-block clamp, rows per block, blocks) of vqvae_bias_grad_wide_f32"""
-    want = cdiv(P, 64)
-    nb = min(want, 512)
-    rpb = cdiv(P, nb)
-    return want, rpb, cdiv(P, rpb)
+def bias_wide_plan(P, C):
+    """what vqvae_bias_grad_wide_f32 would launch: want = blocks before the 512-block clamp, per_split = rows per block, splits"""
+    from vqvae_amd import _lib
+    return _lib.train_reduction_plan("bias_grad_wide", P, C)
 
 
 def sampler_packed_floats(K, dim, nl, ncls):

@@ -179,8 +179,10 @@ def test_host_side_plans_without_gpu():
 
 def test_dispatch_table_unchanged():
     """Every kernel-selection query answer recorded in tests/golden/dispatch_table.json (tools/gen_golden_dispatch.py): which
-    quantizer kernel, sweep count, launch form and template instance; quantizer and whole-path workspace sizes; conv term products.
-    Launch forms assume 256 CUs without a device."""
+    quantizer kernel, sweep count, launch form and template instance; quantizer and whole-path workspace sizes; conv term products;
+    the training entry points' workspace sizes and what each training reduction would launch (the generator's own query lists).
+    Launch forms and plans assume 256 CUs without a device."""
+    import importlib.util
     import itertools
     import json
     from vqvae_amd import _lib
@@ -203,6 +205,40 @@ def test_dispatch_table_unchanged():
     for (dm, (B, H, W)), ws in zip(itertools.product(g["model_dims"], g["model_shape"]), t["model_ws"], strict=True):
         d = _lib.VqvaeDims(*dm, 0.25)
         assert [L.vqvae_workspace_bytes(d, B, H, W), L.vqvae_workspace_ze_offset(d, B, H, W)] == ws, (dm, B, H, W)
+    spec = importlib.util.spec_from_file_location("gen_golden_dispatch", os.path.join(ROOT, "tools", "gen_golden_dispatch.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    got = gen.train_ws_without_device(g)         # the goldens' sizes are those of a machine without a GPU (rocPRIM's sort scratch)
+    assert sorted(got) == sorted(t["train_ws"])
+    for name, table in t["train_ws"].items():
+        assert got[name] == table, name
+    for (what, dims), i in zip(gen.train_plan_queries(g), t["train_plans"], strict=True):
+        p = _lib.train_reduction_plan(what, *dims)
+        assert (None if p is None else list(p)) == t["train_plan_values"][i], (what, dims)
+
+
+def test_train_reduction_plan_answers_without_gpu():
+    """vqvae_train_reduction_plan is host logic: the plans of the default model's step at B = 4096 (256 CUs without a device), and the
+    entry points' own refusals for dimensions they do not take"""
+    from vqvae_amd import _lib
+    q = _lib.train_reduction_plan
+    p = q("conv_wgrad", 4096, 8, 8, 128, 8, 8, 128, 3, 1, 1, 0, 0)
+    assert (p.kernel, p.items, p.splits, p.per_split, p.last, p.want, p.aux0, p.aux1) == ("conv_wgrad_map8_h2", 4096, 128, 32, 32, 128, 2, 2)
+    assert q("conv_wgrad", 4096, 8, 8, 128, 8, 8, 128, 3, 1, 1, 0, 0x4).kernel == "conv_wgrad_map8"
+    p = q("conv_wgrad", 4096, 16, 16, 64, 32, 32, 3, 4, 2, 1, 1, 0)
+    assert (p.kernel, p.splits, p.per_split, p.want) == ("conv_wgrad_img", 512, 8, 1024)
+    p = q("conv_wgrad", 4096, 8, 8, 96, 8, 8, 32, 3, 1, 1, 0, 0)            # 32-channel multiples without a wave layout
+    assert (p.kernel, p.items, p.splits) == ("conv_wgrad", 8192, 64)
+    p = q("segsum", 262144, 512, 64)
+    assert (p.kernel, p.aux0, p.aux1, p.splits) == ("segsum", 512, 1024, 1024)
+    assert q("bias_grad", 1 << 20, 257) is None and q("bias_grad_wide", 1 << 20, 257).splits == 512
+    assert q("conv_wgrad", 4096, 8, 8, 128, 8, 8, 128, 5, 1, 1, 0, 0) is None     # k > 4
+    assert q("conv_wgrad", 4096, 8, 8, 128) is None                              # too few dimensions
+    assert q("conv_taps_wgrad", 8, 8, 8, 64, 128, 2, 0, 0, -1, 9) is None        # a tap 9 columns away
+    assert q("conv_taps_wgrad", 8, 8, 8, 6, 128, 1, 0, 0) is None                # Cin % 4
+    L = _lib.load()
+    assert L.vqvae_train_reduction_plan(99, (ctypes.c_int64 * 2)(1, 1), 2, (ctypes.c_int64 * 8)()) == -3
+    assert L.vqvae_train_reduction_plan(0, None, 0, None) == -1
 
 
 def test_modules_pickle_and_deepcopy_like_the_reference(tmp_path):

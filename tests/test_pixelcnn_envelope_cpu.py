@@ -126,26 +126,26 @@ def test_model_cases_reach_the_weight_gradient_kernels_they_name():
         K, dim, nl, ncls, B, side = E.MODEL_CASES[case]
         out = {}
         for name, taps in (("v0", E.T28), ("h0", [(0, kx - 3) for kx in range(4)]), ("v", E.T6), ("h", E.T2)):
-            if E.wgrad_is_map(side, side, dim, 2 * dim, taps):
-                out[name] = ("map",) + E.wgrad_map_plan(B, dim, 2 * dim, len(taps))
-            else:
-                out[name] = ("blk",) + E.wgrad_blk_plan(B, side, side, dim, 2 * dim, len(taps))
+            out[name] = E.taps_wgrad_plan(B, side, side, dim, 2 * dim, taps)
         return out
+
+    def form(q):                                             # (kernel, images per split)
+        return {"taps_wgrad_map": "map", "taps_wgrad_blk": "blk"}[q.kernel], q.per_split
     p = plans("k512_d64_l15_c10_b1024_s8")
-    assert [p[k][:2] for k in ("v0", "h0", "v", "h")] == [("map", 32), ("map", 8), ("map", 8), ("map", 8)]
+    assert [form(p[k]) for k in ("v0", "h0", "v", "h")] == [("map", 32), ("map", 8), ("map", 8), ("map", 8)]
     p = plans("k512_d64_l15_c10_b32_s8")
-    assert all(v[:2] == ("map", 1) for v in p.values())
+    assert all(form(v) == ("map", 1) for v in p.values())
     p = plans("k512_d64_l2_c10_b2048_s8")
-    assert [p[k][:2] for k in ("v0", "v")] == [("map", 64), ("map", 16)]
+    assert [form(p[k]) for k in ("v0", "v")] == [("map", 64), ("map", 16)]
     p = plans("k256_d128_l2_c10_b1024_s8")
-    assert p["v"][:2] == ("map", 32) and p["v0"][:2] == ("map", 128)    # 8 tiles: 32 splits; 32 tiles: 8 splits
+    assert form(p["v"]) == ("map", 32) and form(p["v0"]) == ("map", 128)    # 8 tiles: 32 splits; 32 tiles: 8 splits
     p = plans("k100_d96_l3_c4_b3_s8")                        # 96 = one and a half 64-wide tiles
-    assert p["v"][0] == "map" and 96 % 64 == 32
+    assert form(p["v"])[0] == "map" and 96 % 64 == 32
     for case in ("k100_d96_l3_c4_b3_s9", "k12_d20_l2_c3_b5_s7", "k8_d4_l1_c1_b1_s1", "k4_d8_l3_c2_b64_s2",
                  "k256_d64_l15_c10_b4_s28", "k256_d32_l4_c10_b2_s32"):
-        assert all(v[0] == "blk" for v in plans(case).values()), case
+        assert all(form(v)[0] == "blk" for v in plans(case).values()), case
     p = plans("k256_d64_l15_c10_b4_s28")                     # 98 blocks, 12 splits of 9 blocks
-    assert p["v"][1] == 98 and p["v"][4] > 8
+    assert p["v"].items == 98 and p["v"].splits > 8
 
 
 def test_kernel_cases_reach_the_branches_they_name():
@@ -157,20 +157,26 @@ def test_kernel_cases_reach_the_branches_they_name():
     for B, Cin, Cout in E.CONV1X1_CASES:
         assert E.conv_is_wide(B, 8, Cin, Cout) and not E.conv_is_wide(504, 8, Cin, Cout)
     for B, H, W, Cin, Cout, taps, ips, ns in E.WGRAD_MAP_CASES:
-        assert E.wgrad_is_map(H, W, Cin, Cout, E.TAPS[taps]), (B, H, W)
-        assert E.wgrad_map_plan(B, Cin, Cout, len(E.TAPS[taps]))[:2] == (ips, ns), (B, H, W, taps)
-    assert E.wgrad_map_plan(257, 32, 64, 6) == (2, 129, 1)   # the last split holds one image
-    assert E.wgrad_map_plan(1000, 64, 128, 28) == (32, 32, 8)
+        got = E.taps_wgrad_plan(B, H, W, Cin, Cout, E.TAPS[taps])
+        assert got.kernel == "taps_wgrad_map", (B, H, W)
+        assert (got.per_split, got.splits) == (ips, ns), (B, H, W, taps)
+    got = E.taps_wgrad_plan(257, 7, 5, 32, 64, E.T6)
+    assert (got.per_split, got.splits, got.last) == (2, 129, 1)   # the last split holds one image
+    got = E.taps_wgrad_plan(1000, 8, 8, 64, 128, E.T28)
+    assert (got.per_split, got.splits, got.last) == (32, 32, 8)
     B, H, W, Cin, Cout, taps = E.WGRAD_PATTERN_CASE
-    assert E.wgrad_is_map(H, W, Cin, Cout, E.TAPS[taps]) and E.wgrad_map_plan(B, Cin, Cout, 6)[0] == 8
+    got = E.taps_wgrad_plan(B, H, W, Cin, Cout, E.TAPS[taps])
+    assert got.kernel == "taps_wgrad_map" and len(E.TAPS[taps]) == 6 and got.per_split == 8
     for B, H, W, Cin, Cout, taps, nblk, ns in E.WGRAD_BLK_CASES:
-        assert not E.wgrad_is_map(H, W, Cin, Cout, E.TAPS[taps])
-        got = E.wgrad_blk_plan(B, H, W, Cin, Cout, len(E.TAPS[taps]))
-        assert (got[0], got[3]) == (nblk, ns), (B, H, W, got)
-    assert E.wgrad_blk_plan(32, 28, 28, 64, 128, 6)[1] > 64  # the 64-split clamp acts
+        got = E.taps_wgrad_plan(B, H, W, Cin, Cout, E.TAPS[taps])
+        assert got.kernel == "taps_wgrad_blk", (B, H, W)
+        assert (got.items, got.splits) == (nblk, ns), (B, H, W, got)
+    got = E.taps_wgrad_plan(32, 28, 28, 64, 128, E.T6)
+    assert got.want > 64 and got.splits <= 64                # the 64-split clamp acts
     assert 7 * 81 % 32 != 0                                   # the last pixel block is partly filled
-    assert [E.bias_plan(P)[0] > 512 for P, _ in E.BIAS_CASES] == [True, True, True, False]
-    assert E.bias_plan(65536) == (1024, 128, 512) and E.bias_plan(4096) == (64, 64, 64)
+    assert [E.bias_wide_plan(P, C).want > 512 for P, C in E.BIAS_CASES] == [True, True, True, False]
+    bp = [E.bias_wide_plan(P, 128) for P in (65536, 4096)]
+    assert [(q.want, q.per_split, q.splits) for q in bp] == [(1024, 128, 512), (64, 64, 64)]
     assert any(C > 256 for _, C in E.BIAS_CASES) and any(C <= 256 and 256 % C for _, C in E.BIAS_CASES)
 
 

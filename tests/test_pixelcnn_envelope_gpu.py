@@ -1,7 +1,7 @@
 """The GatedPixelCNN prior at the corners of its documented envelope and at the batches it is measured at, against references:
 whole-model forward + backward against the fp64 restatement (tests/pixelcnn_train_ref.py) and the reference's forward
 (oracle/pixelcnn_port.py); single kernels at the sizes a B = 1024 step gives them against their defining fp64 sums; the cached
-sampler against the reference's forward and the documented draw.  Case tables, planner mirrors and the ReLU-decision rule:
+sampler against the reference's forward and the documented draw.  Case tables, planner queries and mirrors, and the ReLU-decision rule:
 tests/pixelcnn_envelope.py (tests/test_pixelcnn_envelope_cpu.py asserts which kernel form each case reaches).
 
 Tolerances are the project's own, none is new: gradients, tap sums and conv outputs atol 1e-5 max|ref| + rtol 1e-4 over the whole
@@ -210,7 +210,7 @@ def test_taps_weight_gradient_map_kernel_image_magnitudes(pattern):
     over a split): the kernel's products and sums are plain fp32 without scales, so the tolerance is the same"""
     B, H, W, Cin, Cout, taps = E.WGRAD_PATTERN_CASE
     tl = E.TAPS[taps]
-    ips = E.wgrad_map_plan(B, Cin, Cout, len(tl))[0]
+    ips = E.taps_wgrad_plan(B, H, W, Cin, Cout, tl).per_split
     g = torch.Generator().manual_seed(E.WGRAD_PATTERNS.index(pattern))
     fa, fb = E.image_factors(pattern, B, ips)
     x = torch.randn(B, H, W, Cin, generator=g) * fb[:, None, None, None]

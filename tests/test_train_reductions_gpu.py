@@ -8,9 +8,9 @@ driven to many images (rows, pixels) per workgroup, against a plain fp64 restate
   codebook gradient  index_add_ in fp64; 1 ulp of the rounded value + 2^-45 scale (cnt |e_k| + sum |z|) for cancellation
   EMA update         tests/vq_ema_ref.py; the _ulps limits of tests/test_vq_ema_gpu.py
 
-Each case mirrors the host's split plan (the functions below copy it from the sources they cite) and asserts the split it is there to
-reach, so that a change of the plan cannot quietly turn it back into one image per range.  Every reduction is also required to give
-the same bits on a second call."""
+Each case asks the library what it would launch (vqvae_train_reduction_plan: the plan functions the entry points themselves launch
+from) and asserts the split it is there to reach, so that a change of the plan cannot quietly turn it back into one image per range.
+Every reduction is also required to give the same bits on a second call."""
 import numpy as np
 import pytest
 import torch
@@ -30,55 +30,46 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-# ---- mirrors of the host split plans --------------------------------------------------------------------------------------------
+# ---- the library's own split plans -----------------------------------------------------------------------------------------------
 
-def map8_plan(B, k, CA, CB):
-    """csrc/backward.hip:803-813 (vqvae_conv_wgrad_ex_f32, the map-resident branch): wave layout, (ca, cb) tiles, image ranges"""
-    wa = wb = 0
-    if k == 4:
-        if CA % 64 == 0 and CB % 32 == 0:
-            wa, wb = 2, 1
-    elif CA % 64 == 0 and CB % 64 == 0:
-        wa, wb = 2, 2
-    elif CA % 32 == 0 and CB % 128 == 0:
-        wa, wb = 1, 4
-    elif CA % 128 == 0 and CB % 32 == 0:
-        wa, wb = 4, 1
-    assert wa, "not a map-resident shape"
-    tiles = (CA // (32 * wa)) * (CB // (32 * wb))
-    ns = min(_cdiv(512, tiles), B)                       # kWgMapSplit = 512
-    ips = _cdiv(B, ns)
-    return {"tiles": tiles, "ns": _cdiv(B, ips), "ips": ips}
+def _plan(what, *dims):
+    from vqvae_amd import _lib
+    p = _lib.train_reduction_plan(what, *dims)
+    assert p is not None, (what, dims)
+    return p
 
 
-def img_plan(B):
-    """csrc/backward.hip:784-787 (the image-operand branch): workgroups and images per workgroup of conv_wgrad_img_kernel"""
-    nwg = min(_cdiv(B, 4), 512)                          # kWgImgSplit = 512
-    ipw = _cdiv(B, nwg)
-    return {"nwg": _cdiv(B, ipw), "ipw": ipw}
+def map8_plan(B, k, CA, CB, exact=False):
+    """vqvae_conv_wgrad_ex_f32 on 8x8 A maps: splits = image ranges, per_split = images per range of the map-resident kernels"""
+    s = 2 if k == 4 else 1
+    p = _plan("conv_wgrad", B, 8, 8, CA, 8 * s, 8 * s, CB, k, s, 0 if k == 1 else 1, 0, 0x4 if exact else 0)
+    assert p.kernel == ("conv_wgrad_map8_h2" if k >= 3 and not exact else "conv_wgrad_map8"), p
+    return p
 
 
-def generic_plan(B, HA, WA, CA, CB, k, cus):
-    """csrc/backward.hip:723-734 (wgrad_plan): pixel-block splits of conv_wgrad_kernel -> nsplit, rows_per_split and the number of
-    32-pixel blocks in the last split"""
-    nblk = _cdiv(B * HA * WA, 32)
-    tiles = _cdiv(CA, 64) * _cdiv(CB, 64) * k * k
-    ns = max(1, min(_cdiv(8 * cus, tiles), _cdiv(nblk, 8), 64))     # kWgMaxSplit = 64
-    rps = _cdiv(nblk, ns)
-    return {"nsplit": ns, "rows_per_split": rps, "last": nblk - min(nblk, (ns - 1) * rps)}
+def img_plan(B, CA, CB):
+    """the image-operand branch (4x4 stride 2 on 32x32 NCHW images): workgroups and images per workgroup of conv_wgrad_img_kernel"""
+    p = _plan("conv_wgrad", B, 16, 16, CA, 32, 32, CB, 4, 2, 1, 1, 0)
+    assert p.kernel == "conv_wgrad_img", p
+    return p
 
 
-def bias_plan(P):
-    """csrc/backward.hip:848-852 (vqvae_bias_grad_f32): blocks and rows per block of bias_grad_partial_kernel"""
-    nb = min(_cdiv(P, 1024), 512)
-    rpb = _cdiv(P, nb)
-    nb = _cdiv(P, rpb)
-    return {"nblocks": nb, "rows_per_block": rpb, "last": P - (nb - 1) * rpb}
+def generic_plan(B, HA, WA, CA, CB, k):
+    """conv_wgrad_kernel on stride-1 maps of the current device: splits, 32-pixel blocks per split and in the last split"""
+    p = _plan("conv_wgrad", B, HA, WA, CA, HA, WA, CB, k, 1, 1 if k == 3 else 0, 0, 0)
+    assert p.kernel == "conv_wgrad", p
+    return p
 
 
-def bwd_units(idx, K):
-    """csrc/train.hip:26, :86 (kBwdChunk, vqb_units_kernel): a code owns ceil(count / 512) units of its sorted rows"""
-    return (torch.bincount(idx.reshape(-1).cpu(), minlength=K) + 511) // 512
+def bias_plan(P, C):
+    """vqvae_bias_grad_f32: blocks, rows per block and rows of the last block of bias_grad_partial_kernel"""
+    return _plan("bias_grad", P, C)
+
+
+def bwd_units(idx, K, D):
+    """a code owns ceil(count / chunk) units of its sorted rows; the chunk is the segmented sum's own"""
+    chunk = _plan("segsum", idx.numel(), K, D).aux0
+    return (torch.bincount(idx.reshape(-1).cpu(), minlength=K) + chunk - 1) // chunk, chunk
 
 
 # ---- fp64 restatement of the weight gradient ----------------------------------------------------------------------------------
@@ -131,8 +122,9 @@ MAP8_SHAPES = [(3, 1, 128, 128), (4, 2, 128, 64), (3, 1, 64, 128), (1, 1, 64, 12
 @pytest.mark.parametrize("k,s,CA,CB", MAP8_SHAPES, ids=lambda v: str(v))
 def test_map8_weight_gradient_at_the_bench_batch(k, s, CA, CB):
     """conv_wgrad_map8_h2_kernel (fp16x2, k >= 3) and conv_wgrad_map8_kernel (fp32) with 8, 16 or 32 images per range"""
-    plan = map8_plan(BENCH_B, k, CA, CB)
-    assert plan["ips"] >= 8 and plan["ns"] * plan["ips"] == BENCH_B, plan
+    for exact in (False, True):
+        plan = map8_plan(BENCH_B, k, CA, CB, exact)
+        assert plan.per_split >= 8 and plan.splits * plan.per_split == BENCH_B, plan
     pad = 0 if k == 1 else 1
     g = torch.Generator().manual_seed(k * 1000 + CA + CB)
     a = torch.randn(BENCH_B, 8, 8, CA, generator=g)
@@ -142,7 +134,7 @@ def test_map8_weight_gradient_at_the_bench_batch(k, s, CA, CB):
     del a, bt
     for exact in (False, True):
         got = _wgrad(ad, bd, k, s, pad, exact)
-        what = f"grad_w {'fp32' if exact else 'fp16x2'} ips={plan['ips']}"
+        what = f"grad_w {'fp32' if exact else 'fp16x2'} ips={plan.per_split}"
         _close_grad(got, ref.float(), what)
         worst = _per_slice(got, ref)
         assert worst <= 1.0, (what, worst)
@@ -192,12 +184,12 @@ PATTERNS = ["small-first", "falling", "spread", "zero-tiles", "zero-among-tiny",
 @pytest.mark.parametrize("k,s,CA,CB", H2_SHAPES, ids=lambda v: str(v))
 def test_two_term_weight_gradient_scales_inside_ranges(k, s, CA, CB, pattern):
     # the smallest batch with eight images in every range: ns = ceil(512 / tiles) ranges
-    B = 8 * map8_plan(BENCH_B, k, CA, CB)["ns"]
+    B = 8 * map8_plan(BENCH_B, k, CA, CB).splits
     plan = map8_plan(B, k, CA, CB)
-    assert plan["ips"] == 8 and plan["ns"] * 8 == B, plan
+    assert plan.per_split == 8 and plan.splits * 8 == B, plan
     pad = 1
     g = torch.Generator().manual_seed(k * 100 + CA + PATTERNS.index(pattern))
-    fa, fb = _factors(pattern, B, plan["ips"], g)
+    fa, fb = _factors(pattern, B, plan.per_split, g)
     a = torch.randn(B, 8, 8, CA, generator=g) * fa[:, None, None, None]
     bt = torch.randn(B, 8 * s, 8 * s, CB, generator=g) * fb[:, None, None, None]
     ref = _wgrad_ref(a, bt, k, s, pad)
@@ -214,8 +206,8 @@ def test_two_term_weight_gradient_scales_inside_ranges(k, s, CA, CB, pattern):
 def test_image_operand_weight_gradient_at_the_bench_batch(CA, CB):
     """Conv2d(CB, CA, 4, 2, 1) on 32x32 images (A = grad_y, Bt = x) and ConvTranspose2d(CA, CB, 4, 2, 1) (A = t, Bt = grad_y): the
     same sum, eight images per workgroup at B = 4096"""
-    plan = img_plan(BENCH_B)
-    assert plan["ipw"] >= 8 and plan["nwg"] * plan["ipw"] == BENCH_B, plan
+    plan = img_plan(BENCH_B, CA, CB)
+    assert plan.per_split >= 8 and plan.splits * plan.per_split == BENCH_B, plan
     g = torch.Generator().manual_seed(CA + CB)
     a = torch.randn(BENCH_B, 16, 16, CA, generator=g)
     bt = torch.randn(BENCH_B, CB, 32, 32, generator=g)
@@ -225,11 +217,11 @@ def test_image_operand_weight_gradient_at_the_bench_batch(CA, CB):
     assert _per_slice(got, ref) <= 1.0
 
 
-def _generic_batch(k, CA, CB, cus, want):
-    """the smallest batch of 56x56 maps whose last split is ragged (0 < last < rows_per_split) or empty (last == 0)"""
+def _generic_batch(k, CA, CB, want):
+    """the smallest batch of 56x56 maps whose last split is ragged (0 < last < per_split) or empty (last == 0)"""
     for B in range(4, 64):
-        p = generic_plan(B, 56, 56, CA, CB, k, cus)
-        if (want == "empty" and p["last"] == 0) or (want == "ragged" and 0 < p["last"] < p["rows_per_split"]):
+        p = generic_plan(B, 56, 56, CA, CB, k)
+        if (want == "empty" and p.last == 0) or (want == "ragged" and 0 < p.last < p.per_split):
             return B, p
     raise AssertionError(f"no batch with a {want} last split")
 
@@ -238,9 +230,8 @@ def _generic_batch(k, CA, CB, cus, want):
 @pytest.mark.parametrize("k,CA,CB", [(3, 128, 128), (1, 128, 32)], ids=lambda v: str(v))
 def test_generic_weight_gradient_last_split(k, CA, CB, last):
     """conv_wgrad_kernel on the 56x56 latent maps of config 4 (224x224 images): near its 64-split cap, the last split ragged or empty"""
-    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
-    B, plan = _generic_batch(k, CA, CB, cus, last)
-    assert plan["nsplit"] >= 32, plan
+    B, plan = _generic_batch(k, CA, CB, last)
+    assert plan.splits >= 32, plan
     pad = 1 if k == 3 else 0
     g = torch.Generator().manual_seed(B * 10 + k)
     a = torch.randn(B, 56, 56, CA, generator=g)
@@ -269,8 +260,8 @@ def _fp32_ulps(got, ref64):
 def test_bias_gradient_over_a_million_pixels(layout, B, H, W, C):
     from vqvae_amd import autograd_conv as A
     P = B * H * W
-    plan = bias_plan(P)
-    assert P >= 1 << 20 and plan["nblocks"] == 512 and 0 < plan["last"] < plan["rows_per_block"], plan
+    plan = bias_plan(P, C)
+    assert P >= 1 << 20 and plan.splits == 512 and 0 < plan.last < plan.per_split, plan
     g = torch.Generator().manual_seed(C + H)
     shape = (B, C, H, W) if layout == "nchw" else (B, H, W, C)
     x = torch.randn(*shape, generator=g) + 0.25                       # an offset: no column sum near zero
@@ -314,9 +305,10 @@ VQ_CASES = [  # histogram, B, D, K -- N = 64 B rows
 ]
 
 
-def _check_units(hist, B, units):
+def _check_units(hist, B, units, chunk):
+    assert chunk == 512                                              # VQ_CASES' unit counts (512 .. 515 units) are written for it
     if hist == "one-code":
-        assert int(units.max()) == _cdiv(B * 64, 512) and int(units.sum()) == int(units.max()), units.max()
+        assert int(units.max()) == _cdiv(B * 64, chunk) and int(units.sum()) == int(units.max()), units.max()
     elif hist == "fresh":
         assert int(units.max()) >= 100, int(units.max())             # hundreds of units on the busiest code
     else:
@@ -329,7 +321,7 @@ def test_codebook_gradient_and_ema_update_at_the_bench_batch(hist, B, D, K, rowm
     from vqvae_amd import training as T
     g = torch.Generator().manual_seed(B + D + len(hist))
     z, cb, idx = _vq_case(hist, B, D, K, g)
-    _check_units(hist, B, bwd_units(idx, K))
+    _check_units(hist, B, *bwd_units(idx, K, D))
     N = B * 64
     rows = R.rows_of(z.permute(0, 2, 3, 1), True).double()
     flat = idx.reshape(-1)

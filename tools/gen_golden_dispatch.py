@@ -8,6 +8,11 @@ forms assume 256 CUs, as they do without a device) into tests/golden/dispatch_ta
   vq_ws       vqvae_vq_workspace_bytes over K x D
   conv        vqvae_conv_term_products over kinds x map sizes x channel pairs x flags
   model_ws    vqvae_workspace_bytes and vqvae_workspace_ze_offset for a few VqvaeDims and batch shapes
+  train_ws    every training *_workspace_bytes query over channels x k, taps x channels, rows x keys x channels (one table each),
+              asked in a child process that sees no GPU: the radix sort's scratch inside three of them is rocPRIM's and follows the
+              device's architecture
+  train_plans vqvae_train_reduction_plan over the same shapes x batch: indices into "train_plan_values", the distinct answers
+              (None where the entry point refuses the shape)
 
 Every table is a flat list in the row-major order of its grid's axes.  tests/test_capi.py::test_dispatch_table_unchanged asserts
 every entry.  Regenerate only when a selection changes on purpose:
@@ -17,6 +22,7 @@ every entry.  Regenerate only when a selection changes on purpose:
 import itertools
 import json
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,7 +48,65 @@ GRID = {
     "model_dims": [[128, 32, 2, 512, 64, 3], [128, 32, 2, 1024, 64, 3], [128, 32, 2, 2048, 128, 3], [64, 32, 1, 512, 48, 3],
                    [256, 64, 2, 512, 64, 1]],
     "model_shape": [[1, 32, 32], [4096, 32, 32], [2, 64, 64], [3, 28, 28], [4, 30, 32], [8, 224, 224]],
+    # training reductions
+    "train_ch": [3, 32, 48, 64, 96, 100, 128, 256, 512],
+    "train_k": [1, 2, 3, 4],
+    "train_ntaps": [1, 2, 6, 8, 9, 21, 28, 32],
+    "train_N": [1, 4096, 262144],
+    "train_keys": [10, 512],
+    "train_B": [1, 37, 257, 1024, 4096],
+    # weight-gradient geometries: A map side, Bt is an NCHW image, flags.  stride 2 for k = 4, else 1; pad 0 for k = 1, else 1; the
+    # Bt map is stride times the A map
+    "train_wgrad_geom": [[8, 0, 0x0], [16, 1, 0x0]],
+    "train_taps_side": 8,      # tap lists: the first ntaps of a 5 x 7 window above and around the pixel, row by row
 }
+
+
+def taps_of(ntaps):
+    """(dy list, dx list) of the grid's tap lists; 28 taps are layer 0's vertical stack"""
+    win = [(ky - 3, kx - 3) for ky in range(5) for kx in range(7)][:ntaps]
+    return [t[0] for t in win], [t[1] for t in win]
+
+
+def train_ws(L, g=GRID):
+    """the workspace-size tables of the training entry points (L: the loaded library)"""
+    ch, N = g["train_ch"], g["train_N"]
+    rows = list(itertools.product(N, g["train_keys"], ch))
+    return {
+        "conv_wgrad": [L.vqvae_conv_wgrad_workspace_bytes(ca, cb, k) for ca, cb, k in itertools.product(ch, ch, g["train_k"])],
+        "conv_taps_wgrad": [L.vqvae_conv_taps_wgrad_workspace_bytes(t, ci, co) for t, ci, co in itertools.product(g["train_ntaps"], ch, ch)],
+        "bias_grad": [L.vqvae_bias_grad_workspace_bytes(c) for c in ch],
+        "bias_grad_wide": [L.vqvae_bias_grad_wide_workspace_bytes(c) for c in ch],
+        "vq_backward": [L.vqvae_vq_backward_workspace_bytes(n, K, D) for n, K, D in rows],
+        "vq_ema": [L.vqvae_vq_ema_workspace_bytes(n, K, D) for n, K, D in rows],
+        "gather_rows_backward": [L.vqvae_gather_rows_backward_workspace_bytes(n, C, r) for n, r, C in rows],
+        "cross_entropy": [L.vqvae_cross_entropy_workspace_bytes(n) for n in N],
+        "recon_loss": [L.vqvae_recon_loss_workspace_bytes()],
+    }
+
+
+def train_ws_without_device(g=GRID):
+    """train_ws as a machine without a GPU answers it (this file as a child process with every device hidden)"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--train-ws", json.dumps(g)], env=env, check=True,
+                         capture_output=True, text=True).stdout
+    return json.loads(out.strip().splitlines()[-1])
+
+
+def train_plan_queries(g=GRID):
+    """(reduction, dims) of every vqvae_train_reduction_plan query of the goldens, in table order"""
+    ch, Bs = g["train_ch"], g["train_B"]
+    for (side, nchw, flags), ca, cb, k, B in itertools.product(g["train_wgrad_geom"], ch, ch, g["train_k"], Bs):
+        s = 2 if k == 4 else 1
+        yield "conv_wgrad", (B, side, side, ca, side * s, side * s, cb, k, s, 0 if k == 1 else 1, nchw, flags)
+    side = g["train_taps_side"]
+    for t, ci, co, B in itertools.product(g["train_ntaps"], ch, ch, Bs):
+        dy, dx = taps_of(t)
+        yield "conv_taps_wgrad", (B, side, side, ci, co, t, *dy, *dx)
+    for what, c, B in itertools.product(("bias_grad", "bias_grad_wide"), ch, Bs):
+        yield what, (B * 64, c)
+    for n, K, D in itertools.product(g["train_N"], g["train_keys"], ch):
+        yield "segsum", (n, K, D)
 
 
 def table():
@@ -70,11 +134,18 @@ def table():
     for dm, (B, H, W) in itertools.product(g["model_dims"], g["model_shape"]):
         d = _lib.VqvaeDims(*dm, 0.25)
         model_ws.append([L.vqvae_workspace_bytes(d, B, H, W), L.vqvae_workspace_ze_offset(d, B, H, W)])
+    plan_values, plans = [], []
+    for what, dims in train_plan_queries(g):
+        p = _lib.train_reduction_plan(what, *dims)
+        plans.append(idx_of(plan_values, None if p is None else list(p)))
     return {"grid": g, "names": names, "instances": instances, "vq": vq, "vq_forms": forms, "vq_ws": vq_ws, "conv": conv,
-            "model_ws": model_ws}
+            "model_ws": model_ws, "train_ws": train_ws_without_device(g), "train_plan_values": plan_values, "train_plans": plans}
 
 
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--train-ws":
+        print(json.dumps(train_ws(_lib.load(), json.loads(sys.argv[2]))))
+        return
     t = table()
     with open(OUT, "w") as f:
         f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" for k, v in t.items()) + "\n}\n")

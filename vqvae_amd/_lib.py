@@ -7,6 +7,7 @@ process is required for shared streams and device pointers).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -127,6 +128,7 @@ SIGNATURES = {
     "vqvae_cross_entropy_backward_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "vqvae_bias_grad_wide_workspace_bytes": (_sz, [_i32]),
     "vqvae_bias_grad_wide_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "vqvae_train_reduction_plan": (_i32, [_i32, C.POINTER(_i64), _i32, C.POINTER(_i64)]),
     "vqvae_pixelcnn_sample_packed_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vqvae_pixelcnn_sample_pack_f32": (_i32, [C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "vqvae_pixelcnn_sample_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
@@ -235,6 +237,21 @@ def vq_kernel_instance(n_rows: int, K: int, D: int, HW: int = 64, flags: int = 0
     # but 64-row units on eight waves of row-major rows, which the rule no longer picks for such codebooks)
     unrolled = ", 16" if 480 < K <= 512 and not (f[0] == 8 and f[1] == 64 and flags & 0x1) and f[0] != 12 else ""
     return f"{name}<{f[0]}, {'false' if flags & 0x1 else 'true'}, {f[1] // 32}{unrolled}>" + (f" (last {f[2]} % of the units pooled)" if f[2] else "")
+
+
+TRAIN_PLANS = {"conv_wgrad": 0, "conv_taps_wgrad": 1, "bias_grad": 2, "bias_grad_wide": 3, "segsum": 4}   # VQVAE_TRAIN_PLAN_*
+TRAIN_KERNELS = [None, "conv_wgrad_img", "conv_wgrad_map8_h2", "conv_wgrad_map8", "conv_wgrad", "taps_wgrad_map", "taps_wgrad_blk",
+                 "bias_grad", "bias_grad_wide", "segsum"]                                                  # VQVAE_TRAIN_KERNEL_*
+TrainPlan = collections.namedtuple("TrainPlan", "kernel items splits per_split last want aux0 aux1")
+
+
+def train_reduction_plan(what: str, *dims):
+    """what a training reduction would launch for these dimensions (vqvae_train_reduction_plan in include/vqvae_hip.h lists them
+    per reduction; a tap list is passed as its dy values, then its dx values), or None where the entry point refuses them"""
+    d, out = (_i64 * len(dims))(*dims), (_i64 * 8)()
+    if load().vqvae_train_reduction_plan(TRAIN_PLANS[what], d, len(dims), out) != 0:
+        return None
+    return TrainPlan(TRAIN_KERNELS[out[0]], *out[1:])
 
 
 PROF_IDS = {"vq_main": 0, "conv_igemm": 1, "res_layer": 2, "conv_in": 3, "conv_out": 4}

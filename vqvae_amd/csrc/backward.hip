@@ -16,7 +16,7 @@
 //      taps folded into the MFMA N dimension (conv_wgrad_img_kernel: first / last layer).
 //   vqvae_bias_grad_f32    db[c] = sum over pixels of grad_y[pixel][c]   (fixed-order two-stage reduction, fp64)
 //   vqvae_relu_backward_f32  g_in = g_out * (y > 0)
-#include "common.h"
+#include "train_reduce.h"
 
 namespace vqvae {
 
@@ -602,25 +602,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_img_kernel(const float *__rest
     }
 }
 
-// dW[ca][cb][tap] = sum_split partial[split][tap][ca][cb]   (fixed order)
-__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__restrict__ partial, int nsplit, int ntap,
-                                                                int CA, int CB, float *__restrict__ dw) {
-    const long long total = (long long)ntap * CA * CB;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        // eight interleaved running sums (loads in flight instead of one dependent add per load), combined in a fixed order
-        float s8[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        int sp = 0;
-        for (; sp + 8 <= nsplit; sp += 8)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s8[j] += partial[(size_t)(sp + j) * total + e];
-        for (int j = 0; sp < nsplit; ++sp, ++j) s8[j] += partial[(size_t)sp * total + e];
-        const float s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-        const int tap = (int)(e / ((long long)CA * CB));
-        const long long rem = e - (long long)tap * CA * CB;          // ca * CB + cb
-        dw[rem * ntap + tap] = s;
-    }
-}
-
 // per-channel sums of a (P, C) row-major tensor [or an NCHW one: (B, C, HW)] -- stage 1: one partial per block.
 // Row-major with C % 4 == 0: a thread owns four consecutive channels (16-byte loads), 1024 / C rows in flight per
 // block iteration, fp64 accumulators; otherwise one channel per thread.
@@ -687,22 +668,6 @@ __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float *__r
     }
 }
 
-// stage 2: one workgroup per channel, fixed-order tree over the block partials
-__global__ __launch_bounds__(256) void bias_grad_final_kernel(const double *__restrict__ partial, int nblocks, int C,
-                                                              float *__restrict__ db) {
-    __shared__ double red[256];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    double s = 0.0;
-    for (int b = tid; b < nblocks; b += 256) s += partial[(size_t)b * C + c];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) db[c] = (float)red[0];
-}
-
 __global__ __launch_bounds__(256) void relu_backward_kernel(const float *__restrict__ gout, const float *__restrict__ y,
                                                             long long n, float *__restrict__ gin) {
     const long long n4 = n >> 2;
@@ -719,17 +684,68 @@ __global__ __launch_bounds__(256) void relu_backward_kernel(const float *__restr
         for (long long i = (n4 << 2) + threadIdx.x; i < n; i += 256) gin[i] = y[i] > 0.0f ? gout[i] : 0.0f;
 }
 
-static int wgrad_plan(int64_t B, int HA, int WA, int CA, int CB, int k, WgradGeom &g) {
-    const long long nblk = ((long long)B * HA * WA + 31) / 32;        // 32-pixel blocks
-    // enough workgroups to fill the chip a few times over: tiles * taps * splits >= ~8 per CU
-    const long long tiles = (long long)((CA + 63) / 64) * ((CB + 63) / 64) * k * k;
-    long long ns = (8LL * num_cus() + tiles - 1) / tiles;
-    if (ns > (nblk + 7) / 8) ns = (nblk + 7) / 8;         // at least 8 blocks per workgroup
-    if (ns > kWgMaxSplit) ns = kWgMaxSplit;
-    if (ns < 1) ns = 1;
-    g.nsplit = (int)ns;
-    g.rows_per_split = (nblk + ns - 1) / ns;
-    return VQVAE_OK;
+constexpr size_t kWgImgLdsMax = 96 * 1024;
+
+// the image-operand kernel folds the taps into the MFMA N dimension: one 64 x 64 tile holds (ca, tap * cb)
+static bool wgrad_img_fits(int CA, int CB, int k) { return CA <= 64 && k * k * CB <= 64; }
+static size_t wgrad_img_lds(int HB, int WB, int CB) { return (size_t)4 * CB * HB * WB * sizeof(float); }
+
+// waves along (ca, cb) of the map-resident kernels' workgroup tile, false where no instance covers the channel counts
+static bool wgrad_map8_layout(int CA, int CB, int k, int &wa, int &wb) {
+    wa = wb = 0;
+    if (k == 4) { if (CA % 64 == 0 && CB % 32 == 0) wa = 2, wb = 1; }
+    else if (CA % 64 == 0 && CB % 64 == 0) wa = 2, wb = 2;
+    else if (CA % 32 == 0 && CB % 128 == 0) wa = 1, wb = 4;
+    else if (CA % 128 == 0 && CB % 32 == 0) wa = 4, wb = 1;
+    return wa != 0;
+}
+
+// (ca, cb) tiles of the map-resident kernels: 4096 channel pairs per workgroup, 64 x 32 for k = 4.  Under every layout of
+// wgrad_map8_layout this is (CA / 32 wa) (CB / 32 wb) exactly; channel counts without a layout round up (the size query asks).
+static long long wgrad_map8_tiles(int CA, int CB, int k) {
+    return k == 4 ? (long long)((CA + 63) / 64) * (CB / 32) : ((long long)CA * CB + 4095) / 4096;
+}
+// image ranges they ask for: kWgMapSplit workgroups (two per CU of 256) over the tiles
+static long long wgrad_map8_splits(int CA, int CB, int k) {
+    const long long tiles = wgrad_map8_tiles(CA, CB, k);
+    return (kWgMapSplit + tiles - 1) / tiles;
+}
+
+// What vqvae_conv_wgrad_ex_f32 launches: the one place that decides it.
+ReducePlan conv_wgrad_plan(long long B, int HA, int WA, int CA, int HB, int WB, int CB, int k, int stride, int pad, int bt_nchw,
+                           int flags) {
+    ReducePlan p;
+    int wa, wb;
+    if (bt_nchw && wgrad_img_fits(CA, CB, k) && wgrad_img_lds(HB, WB, CB) <= kWgImgLdsMax) {
+        // small NCHW image operand: one image per wave, at most kWgImgSplit workgroups
+        p.kernel = VQVAE_TRAIN_KERNEL_CONV_WGRAD_IMG;
+        p.items = B;
+        p.want = (B + 3) / 4;
+        plan_ranges(p, kWgImgSplit);
+    } else if (!bt_nchw && HA == 8 && WA == 8 && HB == 8 * stride && WB == 8 * stride && pad == (k == 1 ? 0 : 1) &&
+               ((k == 4 && stride == 2) || ((k == 3 || k == 1) && stride == 1)) && wgrad_map8_layout(CA, CB, k, wa, wb)) {
+        // 8x8 A maps with whole 32-channel tiles: both maps resident in LDS, all taps from one staging.  Two-term fp16 products
+        // where they multiply enough to pay for the conversion pass (the 1x1 layers are operand-bound: their fp32 form is the
+        // faster one, 38 against 53 us at B = 4096)
+        const bool h2 = !(flags & VQVAE_CONV_EXACT_FP32) && k >= 3;
+        p.kernel = h2 ? VQVAE_TRAIN_KERNEL_CONV_WGRAD_MAP8_H2 : VQVAE_TRAIN_KERNEL_CONV_WGRAD_MAP8;
+        p.items = B;
+        p.want = wgrad_map8_splits(CA, CB, k);
+        plan_ranges(p, B);
+        p.aux0 = wa;
+        p.aux1 = wb;
+    } else {
+        // any map, per tap, over 32-pixel blocks: enough workgroups to fill the chip a few times over (tiles * taps * splits >= ~8
+        // per CU), at least 8 blocks per workgroup.  The kernel keeps the split count it asked for: its last splits may be empty.
+        p.kernel = VQVAE_TRAIN_KERNEL_CONV_WGRAD;
+        p.items = (B * HA * WA + 31) / 32;
+        const long long tiles = (long long)((CA + 63) / 64) * ((CB + 63) / 64) * k * k;
+        p.want = (8LL * num_cus() + tiles - 1) / tiles;
+        if (p.want > (p.items + 7) / 8) p.want = (p.items + 7) / 8;
+        plan_ranges(p, kWgMaxSplit);
+        p.splits = p.want < kWgMaxSplit ? (p.want < 1 ? 1 : p.want) : kWgMaxSplit;
+    }
+    return p;
 }
 
 }  // namespace vqvae
@@ -740,15 +756,12 @@ extern "C" {
 
 size_t vqvae_conv_wgrad_workspace_bytes(int CA, int CB, int k) {
     if (CA < 1 || CB < 1 || k < 1 || k > 4) return 0;
-    // image-operand kernel: kWgImgSplit partials; map-resident kernel: kWgMapSplit workgroups over its (ca, cb) tiles
-    // (a tile is 64 x 64 or 32 x 128 channels, 64 x 32 for k = 4); generic kernel: kWgMaxSplit
-    size_t splits = (k * k * CB <= 64 && CA <= 64) ? kWgImgSplit : kWgMaxSplit;
-    if (CA % 32 == 0 && CB % 32 == 0) {
-        const size_t tiles = k == 4 ? (size_t)((CA + 63) / 64) * (CB / 32) : ((size_t)CA * CB + 4095) / 4096;
-        const size_t ns = ((size_t)kWgMapSplit + tiles - 1) / tiles;
-        if (ns > splits) splits = ns;
-    }
-    return splits * k * k * CA * CB * sizeof(float);
+    // the largest split count of conv_wgrad_plan's branches these channel counts may reach on some map; the map-resident bound is
+    // taken for every pair of 32-channel multiples, also those without a layout
+    long long splits = kWgMaxSplit;
+    if (wgrad_img_fits(CA, CB, k) && kWgImgSplit > splits) splits = kWgImgSplit;
+    if (CA % 32 == 0 && CB % 32 == 0 && wgrad_map8_splits(CA, CB, k) > splits) splits = wgrad_map8_splits(CA, CB, k);
+    return (size_t)splits * k * k * CA * CB * sizeof(float);
 }
 
 int vqvae_conv_wgrad_f32(const float *a, const float *bt, int64_t B, int HA, int WA, int CA, int HB, int WB, int CB,
@@ -763,79 +776,52 @@ int vqvae_conv_wgrad_ex_f32(const float *a, const float *bt, int64_t B, int HA, 
                             size_t workspace_bytes, vqvae_stream_t stream) {
     if (!a || !bt || !grad_w) return VQVAE_ERR_NULL;
     if (flags & ~VQVAE_CONV_EXACT_FP32) return VQVAE_ERR_UNSUPPORTED;
-    // two-term fp16 products where the map-resident kernel applies and multiplies enough to pay for its conversion pass (the
-    // 1x1 layers are operand-bound: their fp32 form is the faster one, 38 against 53 us at B = 4096)
-    const bool h2 = !(flags & VQVAE_CONV_EXACT_FP32) && k >= 3;
     if (B < 1 || HA < 1 || WA < 1 || CA < 1 || HB < 1 || WB < 1 || CB < 1 || stride < 1 || pad < 0) return VQVAE_ERR_SHAPE;
     if (k < 1 || k > 4) return VQVAE_ERR_UNSUPPORTED;
     if (B * (int64_t)HA * WA > INT32_MAX || B * (int64_t)HB * WB * CB > ((int64_t)1 << 40)) return VQVAE_ERR_OVERFLOW;
     if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bt)) & 15) return VQVAE_ERR_UNSUPPORTED;   // 16-byte loads
     if (!workspace || workspace_bytes < vqvae_conv_wgrad_workspace_bytes(CA, CB, k)) return VQVAE_ERR_WORKSPACE;
+    const ReducePlan p = conv_wgrad_plan(B, HA, WA, CA, HB, WB, CB, k, stride, pad, bt_nchw, flags);
     WgradGeom g;
     g.B = (int)B; g.HA = HA; g.WA = WA; g.CA = CA; g.HB = HB; g.WB = WB; g.CB = CB;
     g.k = k; g.stride = stride; g.pad = pad; g.bt_nchw = bt_nchw ? 1 : 0;
-    wgrad_plan(B, HA, WA, CA, CB, k, g);
+    g.nsplit = (int)p.splits;
+    g.rows_per_split = p.per_split;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *partial = static_cast<float *>(workspace);
-    const size_t img_lds = (size_t)4 * CB * HB * WB * sizeof(float);
-    if (bt_nchw && CA <= 64 && k * k * CB <= 64 && img_lds <= 96 * 1024) {
-        // small NCHW image operand: taps folded into the MFMA N dimension, one image per wave
-        long long nwg = (B + 3) / 4;
-        if (nwg > kWgImgSplit) nwg = kWgImgSplit;
-        const int ipw = (int)((B + nwg - 1) / nwg);
-        nwg = (B + ipw - 1) / ipw;
-        const size_t lds = img_lds > 16384 ? img_lds : 16384;
+    const int per = (int)p.per_split;
+    if (p.kernel == VQVAE_TRAIN_KERNEL_CONV_WGRAD_IMG) {
+        const size_t img_lds = wgrad_img_lds(HB, WB, CB), lds = img_lds > 16384 ? img_lds : 16384;
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_wgrad_img_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        hipLaunchKernelGGL(conv_wgrad_img_kernel, dim3((unsigned)nwg), dim3(256), lds, st, a, bt, partial, g, ipw);
-        const long long tot = (long long)k * k * CA * CB;
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, partial,
-                           (int)nwg, k * k, CA, CB, grad_w);
-        return (int)hipGetLastError();
-    }
-    const long long total = (long long)k * k * CA * CB;
-    long long rgrid = (total + 255) / 256;
-    if (rgrid > 4096) rgrid = 4096;
-    // 8x8 A maps with whole 32-channel tiles: both maps resident in LDS, all taps from one staging
-    if (!bt_nchw && HA == 8 && WA == 8 && HB == 8 * stride && WB == 8 * stride && pad == (k == 1 ? 0 : 1) &&
-        ((k == 4 && stride == 2) || ((k == 3 || k == 1) && stride == 1))) {
-        int wa = 0, wb = 0;
-        if (k == 4) { if (CA % 64 == 0 && CB % 32 == 0) wa = 2, wb = 1; }
-        else if (CA % 64 == 0 && CB % 64 == 0) wa = 2, wb = 2;
-        else if (CA % 32 == 0 && CB % 128 == 0) wa = 1, wb = 4;
-        else if (CA % 128 == 0 && CB % 32 == 0) wa = 4, wb = 1;
-        if (wa) {
-            const long long tiles = (long long)(CA / (32 * wa)) * (CB / (32 * wb));
-            long long ns = (kWgMapSplit + tiles - 1) / tiles;              // two workgroups per CU of the 256
-            if (ns > B) ns = B;
-            const int ips = (int)((B + ns - 1) / ns);
-            ns = (B + ips - 1) / ips;
-            const dim3 grid((unsigned)tiles, (unsigned)ns);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgImgLdsMax);
+        hipLaunchKernelGGL(conv_wgrad_img_kernel, dim3((unsigned)p.splits), dim3(256), lds, st, a, bt, partial, g, per);
+    } else if (p.kernel == VQVAE_TRAIN_KERNEL_CONV_WGRAD) {
+        const unsigned gx = (unsigned)(((CA + 63) / 64) * ((CB + 63) / 64) * k * k);
+        hipLaunchKernelGGL(conv_wgrad_kernel, dim3(gx, (unsigned)p.splits), dim3(256), 0, st, a, bt, partial, g);
+    } else {
+        const bool h2 = p.kernel == VQVAE_TRAIN_KERNEL_CONV_WGRAD_MAP8_H2;
+        const int wa = p.aux0;
+        const dim3 grid((unsigned)wgrad_map8_tiles(CA, CB, k), (unsigned)p.splits);
 #define MAP8_LAUNCH(K_, S_, WA_, WB_)                                                                                         \
     do {                                                                                                                      \
-        if (h2) hipLaunchKernelGGL((conv_wgrad_map8_h2_kernel<K_, S_, WA_, WB_>), grid, dim3(256), 0, st, a, bt, partial, g, ips); \
-        else hipLaunchKernelGGL((conv_wgrad_map8_kernel<K_, S_, WA_, WB_>), grid, dim3(256), 0, st, a, bt, partial, g, ips);  \
+        if (h2) hipLaunchKernelGGL((conv_wgrad_map8_h2_kernel<K_, S_, WA_, WB_>), grid, dim3(256), 0, st, a, bt, partial, g, per); \
+        else hipLaunchKernelGGL((conv_wgrad_map8_kernel<K_, S_, WA_, WB_>), grid, dim3(256), 0, st, a, bt, partial, g, per);  \
     } while (0)
-            if (k == 4) MAP8_LAUNCH(4, 2, 2, 1);
-            else if (k == 3 && wa == 2) MAP8_LAUNCH(3, 1, 2, 2);
-            else if (k == 3 && wa == 1) MAP8_LAUNCH(3, 1, 1, 4);
-            else if (k == 3) MAP8_LAUNCH(3, 1, 4, 1);
-            else if (wa == 2) MAP8_LAUNCH(1, 1, 2, 2);
-            else if (wa == 1) MAP8_LAUNCH(1, 1, 1, 4);
-            else MAP8_LAUNCH(1, 1, 4, 1);
+        if (k == 4) MAP8_LAUNCH(4, 2, 2, 1);
+        else if (k == 3 && wa == 2) MAP8_LAUNCH(3, 1, 2, 2);
+        else if (k == 3 && wa == 1) MAP8_LAUNCH(3, 1, 1, 4);
+        else if (k == 3) MAP8_LAUNCH(3, 1, 4, 1);
+        else if (wa == 2) MAP8_LAUNCH(1, 1, 2, 2);
+        else if (wa == 1) MAP8_LAUNCH(1, 1, 1, 4);
+        else MAP8_LAUNCH(1, 1, 4, 1);
 #undef MAP8_LAUNCH
-            hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)rgrid), dim3(256), 0, st, partial, (int)ns, k * k, CA, CB, grad_w);
-            return (int)hipGetLastError();
-        }
     }
-    const unsigned gx = (unsigned)(((CA + 63) / 64) * ((CB + 63) / 64) * k * k);
-    hipLaunchKernelGGL(conv_wgrad_kernel, dim3(gx, (unsigned)g.nsplit), dim3(256), 0, st, a, bt, partial, g);
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)rgrid), dim3(256), 0, st, partial, g.nsplit, k * k, CA,
-                       CB, grad_w);
+    launch_split_reduce(partial, (int)p.splits, k * k, CA, CB, grad_w, st);
     return (int)hipGetLastError();
 }
 
-size_t vqvae_bias_grad_workspace_bytes(int C) { return C < 1 || C > 256 ? 0 : (size_t)1024 * C * sizeof(double); }
+// (twice the plan's kColsumBlocks: the size this entry has asked for since its plan allowed 1024 blocks)
+size_t vqvae_bias_grad_workspace_bytes(int C) { return C < 1 || C > 256 ? 0 : (size_t)2 * kColsumBlocks * C * sizeof(double); }
 
 int vqvae_bias_grad_f32(const float *grad_y, int64_t B, int HW, int C, int nchw, float *grad_b, void *workspace,
                         size_t workspace_bytes, vqvae_stream_t stream) {
@@ -845,14 +831,11 @@ int vqvae_bias_grad_f32(const float *grad_y, int64_t B, int HW, int C, int nchw,
     if (!workspace || workspace_bytes < vqvae_bias_grad_workspace_bytes(C)) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long P = (long long)B * HW;
-    long long nb = (P + 1023) / 1024;
-    if (nb > 512) nb = 512;
-    const long long rpb = (P + nb - 1) / nb;
-    nb = (P + rpb - 1) / rpb;
+    const ReducePlan p = bias_grad_plan(P);
     double *partial = static_cast<double *>(workspace);
-    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, grad_y, P, C, (long long)HW,
-                       nchw ? 1 : 0, rpb, partial);
-    hipLaunchKernelGGL(bias_grad_final_kernel, dim3((unsigned)C), dim3(256), 0, st, partial, (int)nb, C, grad_b);
+    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3((unsigned)p.splits), dim3(256), 0, st, grad_y, P, C, (long long)HW,
+                       nchw ? 1 : 0, p.per_split, partial);
+    launch_colsum_final(partial, (int)p.splits, C, grad_b, st);
     return (int)hipGetLastError();
 }
 
@@ -861,10 +844,7 @@ int vqvae_relu_backward_f32(const float *grad_out, const float *y, int64_t n, fl
     if (n < 1) return VQVAE_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(grad_in)) & 15)
         return VQVAE_ERR_UNSUPPORTED;                    // 16-byte accesses
-    long long grid = ((n >> 2) + 255) / 256;
-    if (grid > 65536) grid = 65536;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(relu_backward_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(relu_backward_kernel, dim3(grid_of(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        grad_out, y, (long long)n, grad_in);
     return (int)hipGetLastError();
 }

@@ -50,6 +50,25 @@ bool prof_dispatch(int id, hipEvent_t *start, hipEvent_t *stop);    // events fo
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// workgroups of 256 threads for `total` elements of a grid-stride kernel: at least one, at most `cap`
+inline unsigned grid_of(long long total, long long cap = 65536) {
+    long long g = (total + 255) / 256;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+
+// Sum of one fp64 value per thread of a 256-thread workgroup through red[256], by a fixed tree (o = 128 ... 1).  Every thread of
+// the workgroup must call it; the total is left in red[0].
+__device__ __forceinline__ void block_sum_f64(double *red, int tid, double v) {
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+}
+
 // ---- quantizer workspace layout (host + device agree on it) -----------------
 struct VqPlan {
     int KC;           // codes per LDS chunk (multiple of 32)

@@ -15,9 +15,7 @@
 //   vqvae_cross_entropy_f32 / _backward_f32   mean softmax cross-entropy over rows (max-subtracted log-sum-exp), fixed-order mean
 //   vqvae_bias_grad_wide_f32         per-channel column sums of any width (the 512-wide hidden layer and the K logits)
 // No floating-point atomics anywhere: every result is bit-reproducible run to run.
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "train_reduce.h"
 
 namespace vqvae {
 
@@ -245,23 +243,7 @@ __global__ __launch_bounds__(256, 1) void taps_wgrad_map_kernel(const float *__r
         }
 }
 
-// dW[ca][cb][tap] = sum_split partial[split][tap][ca][cb]   (fixed order)
-__global__ __launch_bounds__(256) void taps_wgrad_reduce_kernel(const float *__restrict__ partial, int nsplit, int ntap, int CA,
-                                                                int CB, float *__restrict__ dw) {
-    const long long total = (long long)ntap * CA * CB;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        float s8[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        int sp = 0;
-        for (; sp + 8 <= nsplit; sp += 8)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s8[j] += partial[(size_t)(sp + j) * total + e];
-        for (int j = 0; sp < nsplit; ++sp, ++j) s8[j] += partial[(size_t)sp * total + e];
-        const float s = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-        const int tap = (int)(e / ((long long)CA * CB));
-        const long long rem = e - (long long)tap * CA * CB;
-        dw[rem * ntap + tap] = s;
-    }
-}
+static int taps_groups(int ntaps) { return (ntaps + kTwTapsPerGroup - 1) / kTwTapsPerGroup; }
 
 static int taps_fill(TapsWgGeom &g, int ntaps, const int8_t *dy, const int8_t *dx) {
     g.ntaps = ntaps;
@@ -276,7 +258,7 @@ static int taps_fill(TapsWgGeom &g, int ntaps, const int8_t *dy, const int8_t *d
     g.ylo = ylo; g.xlo = xlo;
     g.PH = g.H + yhi - ylo; g.PW = g.W + xhi - xlo;
     for (int i = 0; i < 32; ++i) g.toff[i] = g.dy[i] * g.PW + g.dx[i];
-    const int ngroups = (ntaps + kTwTapsPerGroup - 1) / kTwTapsPerGroup;
+    const int ngroups = taps_groups(ntaps);
     g.per_group = (ntaps + ngroups - 1) / ngroups;
     return VQVAE_OK;
 }
@@ -287,10 +269,42 @@ static bool taps_map_ok(const TapsWgGeom &g) {
     return g.H <= 8 && g.W <= 8 && g.CA % 32 == 0 && g.CB % 32 == 0 && taps_map_lds(g) <= 96 * 1024;
 }
 
+static long long taps_tiles(int CA, int CB) { return (long long)((CA + 63) / 64) * ((CB + 63) / 64); }
+
+// image ranges the map-resident kernel asks for: kTwMapWgs workgroups over its (ca, cb) tiles and tap groups
 static long long taps_map_splits(int ntaps, int CA, int CB) {
-    const int ngroups = (ntaps + kTwTapsPerGroup - 1) / kTwTapsPerGroup;
-    const long long tiles = (long long)((CA + 63) / 64) * ((CB + 63) / 64) * ngroups;
-    return (kTwMapWgs + tiles - 1) / tiles;
+    const long long wgs = taps_tiles(CA, CB) * taps_groups(ntaps);
+    return (kTwMapWgs + wgs - 1) / wgs;
+}
+
+// What vqvae_conv_taps_wgrad_f32 launches for a filled geometry: the map-resident kernel over ranges of images, or the per-tap
+// kernel over ranges of 32-pixel blocks (enough workgroups for eight per CU of 256, at least 8 blocks each, at most kTwBlkMaxSplit)
+static ReducePlan taps_plan(const TapsWgGeom &g) {
+    ReducePlan p;
+    if (taps_map_ok(g)) {
+        p.kernel = VQVAE_TRAIN_KERNEL_CONV_TAPS_WGRAD_MAP;
+        p.items = g.B;
+        p.want = taps_map_splits(g.ntaps, g.CA, g.CB);
+        plan_ranges(p, g.B);
+        p.aux0 = taps_groups(g.ntaps);
+        p.aux1 = g.per_group;
+    } else {
+        p.kernel = VQVAE_TRAIN_KERNEL_CONV_TAPS_WGRAD_BLK;
+        p.items = ((long long)g.B * g.H * g.W + 31) / 32;
+        const long long wgs = taps_tiles(g.CA, g.CB) * g.ntaps;
+        p.want = (8LL * 256 + wgs - 1) / wgs;
+        if (p.want > (p.items + 7) / 8) p.want = (p.items + 7) / 8;
+        plan_ranges(p, kTwBlkMaxSplit);
+    }
+    return p;
+}
+
+int conv_taps_wgrad_plan(long long B, int H, int W, int Cin, int Cout, int ntaps, const int8_t *dy, const int8_t *dx, ReducePlan &p) {
+    TapsWgGeom g;
+    g.B = (int)B; g.H = H; g.W = W; g.CA = Cout; g.CB = Cin;
+    const int rc = taps_fill(g, ntaps, dy, dx);
+    if (rc == VQVAE_OK) p = taps_plan(g);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------- dgrad pack staging
@@ -351,123 +365,7 @@ __global__ __launch_bounds__(256) void gated_backward_kernel(const float *__rest
 }
 
 // ------------------------------------------------------------------------------------------------- gather (embedding) backward
-constexpr int kGbChunk = 512;           // sorted rows per workgroup of the segmented sum
-
-struct GbPlan {
-    size_t off_keys, off_keys_out, off_vals, off_vals_out, off_offsets, off_units, off_partials, off_sort, sort_bytes, total;
-    long long max_units;
-    int key_bits;
-};
-
-static GbPlan gb_plan(long long n, int C, int rows) {
-    GbPlan p;
-    p.key_bits = 1;
-    while ((1LL << p.key_bits) < rows) ++p.key_bits;
-    p.off_keys = 0;
-    p.off_keys_out = align_up(p.off_keys + (size_t)n * 4, 256);
-    p.off_vals = align_up(p.off_keys_out + (size_t)n * 4, 256);
-    p.off_vals_out = align_up(p.off_vals + (size_t)n * 4, 256);
-    p.off_offsets = align_up(p.off_vals_out + (size_t)n * 4, 256);
-    p.off_units = align_up(p.off_offsets + (size_t)(rows + 1) * 4, 256);
-    p.max_units = n / kGbChunk + rows;
-    p.off_partials = align_up(p.off_units + (size_t)(rows + 1) * 4, 256);
-    p.off_sort = align_up(p.off_partials + (size_t)p.max_units * C * sizeof(double), 256);
-    size_t sb = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sb, (const unsigned *)nullptr, (unsigned *)nullptr, (const int *)nullptr,
-                                             (int *)nullptr, (int)n, 0, p.key_bits, 0);
-    p.sort_bytes = sb;
-    p.total = align_up(p.off_sort + sb, 256);
-    return p;
-}
-
-// keys = the row each index reads in the forward (clamped into [0, rows) exactly as gather_rows_kernel clamps)
-__global__ __launch_bounds__(256) void gb_keys_kernel(const long long *__restrict__ idx, long long n, int rows,
-                                                      unsigned *__restrict__ keys, int *__restrict__ vals) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const long long k = idx[i];
-        keys[i] = (unsigned)(k < 0 ? 0 : (k >= rows ? rows - 1 : k));
-        vals[i] = (int)i;
-    }
-}
-
-__global__ __launch_bounds__(256) void gb_offsets_kernel(const unsigned *__restrict__ keys, long long n, int rows,
-                                                         int *__restrict__ offsets) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k > rows) return;
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < (unsigned)k) lo = mid + 1; else hi = mid;
-    }
-    offsets[k] = (int)lo;
-}
-
-__global__ __launch_bounds__(1024) void gb_units_kernel(const int *__restrict__ offsets, int rows, int *__restrict__ unit_start) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (rows + 1023) / 1024;
-    int local = 0;
-    for (int j = 0; j < per; ++j) {
-        const int k = tid * per + j;
-        if (k < rows) local += (offsets[k + 1] - offsets[k] + kGbChunk - 1) / kGbChunk;
-    }
-    part[tid] = local;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - local;
-    for (int j = 0; j < per; ++j) {
-        const int k = tid * per + j;
-        if (k < rows) {
-            unit_start[k] = run;
-            run += (offsets[k + 1] - offsets[k] + kGbChunk - 1) / kGbChunk;
-        }
-    }
-    if (tid == 1023) unit_start[rows] = part[1023];
-}
-
-// partial[unit][c] = sum over the unit's (<= kGbChunk, ascending) source rows of grad_out[i][c], fp64, fixed order.
-// C <= 256: 256 / C row groups; wider rows: one group, channels in 256-wide passes.
-__global__ __launch_bounds__(256) void gb_segsum_kernel(const float *__restrict__ go, const int *__restrict__ src,
-                                                        const int *__restrict__ offsets, const int *__restrict__ unit_start, int rows,
-                                                        int C, double *__restrict__ partial) {
-    __shared__ double red[256];
-    const int unit = blockIdx.x, tid = threadIdx.x;
-    if (unit >= unit_start[rows]) return;
-    int lo_k = 0, hi_k = rows;
-    while (hi_k - lo_k > 1) {
-        const int mid = (lo_k + hi_k) >> 1;
-        if (unit_start[mid] <= unit) lo_k = mid; else hi_k = mid;
-    }
-    const int k = lo_k;
-    const int a = offsets[k] + (unit - unit_start[k]) * kGbChunk;
-    const int e = a + kGbChunk < offsets[k + 1] ? a + kGbChunk : offsets[k + 1];
-    if (C > 256) {
-        for (int c = tid; c < C; c += 256) {
-            double acc = 0.0;
-            for (int j = a; j < e; ++j) acc += (double)go[(size_t)src[j] * C + c];
-            partial[(size_t)unit * C + c] = acc;
-        }
-        return;
-    }
-    const int G = 256 / C;
-    const int gq = tid / C, c = tid - gq * C;
-    double acc = 0.0;
-    if (gq < G)
-        for (int j = a + gq; j < e; j += G) acc += (double)go[(size_t)src[j] * C + c];
-    red[tid] = acc;
-    __syncthreads();
-    if (tid < C) {
-        double t = 0.0;
-        for (int q = 0; q < G; ++q) t += red[q * C + tid];
-        partial[(size_t)unit * C + tid] = t;
-    }
-}
-
+// the sorted segmented sum (launch_segsum, train_reduce.h), then per table row:
 // grad_table[k][c] = sum of the code's units in unit order (0 for rows nobody read)
 __global__ __launch_bounds__(256) void gb_final_kernel(const int *__restrict__ unit_start, const double *__restrict__ partial, int rows,
                                                        int C, float *__restrict__ gt) {
@@ -512,12 +410,7 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const double *__restrict__
     const int tid = threadIdx.x;
     double s = 0.0;
     for (long long r = tid; r < N; r += 256) s += row_loss[r];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
+    block_sum_f64(red, tid, s);
     if (tid == 0) out[0] = (float)(red[0] / (double)N);
 }
 
@@ -539,8 +432,6 @@ __global__ __launch_bounds__(256) void ce_backward_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------- wide column sums
-constexpr int kBwBlocks = 512;
-
 // partial[block][c] = sum over the block's row range of g[row][c] (fp64, fixed order).  C <= 256: 256 / C row groups, combined in
 // group order; wider rows: one group, channels in 256-wide passes.
 __global__ __launch_bounds__(256) void bias_wide_partial_kernel(const float *__restrict__ g, long long P, int C, long long rpb,
@@ -571,28 +462,6 @@ __global__ __launch_bounds__(256) void bias_wide_partial_kernel(const float *__r
     }
 }
 
-// one workgroup per channel: strided sums over the block partials, then a fixed tree
-__global__ __launch_bounds__(256) void bias_wide_final_kernel(const double *__restrict__ partial, int nb, int C, float *__restrict__ db) {
-    __shared__ double red[256];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    double s = 0.0;
-    for (int b = tid; b < nb; b += 256) s += partial[(size_t)b * C + c];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) db[c] = (float)red[0];
-}
-
-static unsigned grid_of(long long total, long long cap = 65536) {
-    long long g = (total + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
-
 static bool misaligned(const void *p) { return reinterpret_cast<uintptr_t>(p) & 15; }
 
 }  // namespace vqvae
@@ -603,6 +472,7 @@ extern "C" {
 
 size_t vqvae_conv_taps_wgrad_workspace_bytes(int ntaps, int Cin, int Cout) {
     if (ntaps < 1 || ntaps > 32 || Cin < 1 || Cout < 1 || Cin % 4 || Cout % 4) return 0;
+    // the larger of taps_plan's two bounds, whichever kernel the map size and the taps will select
     long long ns = kTwBlkMaxSplit;
     const long long nm = taps_map_splits(ntaps, Cout, Cin);
     if (nm > ns) ns = nm;
@@ -621,33 +491,21 @@ int vqvae_conv_taps_wgrad_f32(const float *grad_y, const float *x, int64_t B, in
     g.B = (int)B; g.H = H; g.W = W; g.CA = Cout; g.CB = Cin;
     const int rc = taps_fill(g, ntaps, dy, dx);
     if (rc != VQVAE_OK) return rc;
+    const ReducePlan p = taps_plan(g);
+    g.rows_per_split = p.per_split;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *partial = static_cast<float *>(workspace);
-    const long long tiles = (long long)((Cout + 63) / 64) * ((Cin + 63) / 64);
-    long long ns;
-    if (taps_map_ok(g)) {
-        const int ngroups = (ntaps + g.per_group - 1) / g.per_group;
-        ns = taps_map_splits(ntaps, Cout, Cin);
-        if (ns > B) ns = B;
-        g.rows_per_split = (B + ns - 1) / ns;
-        ns = (B + g.rows_per_split - 1) / g.rows_per_split;
-        const size_t lds = taps_map_lds(g);
+    const long long tiles = taps_tiles(Cout, Cin);
+    if (p.kernel == VQVAE_TRAIN_KERNEL_CONV_TAPS_WGRAD_MAP) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(taps_wgrad_map_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   96 * 1024);
-        hipLaunchKernelGGL(taps_wgrad_map_kernel, dim3((unsigned)(tiles * ngroups), (unsigned)ns), dim3(256), lds, st, grad_y, x,
-                           partial, g);
+        hipLaunchKernelGGL(taps_wgrad_map_kernel, dim3((unsigned)(tiles * p.aux0), (unsigned)p.splits), dim3(256), taps_map_lds(g), st,
+                           grad_y, x, partial, g);
     } else {
-        const long long nblk = (B * (long long)H * W + 31) / 32;
-        ns = (8LL * 256 + tiles * ntaps - 1) / (tiles * ntaps);
-        if (ns > (nblk + 7) / 8) ns = (nblk + 7) / 8;
-        if (ns > kTwBlkMaxSplit) ns = kTwBlkMaxSplit;
-        if (ns < 1) ns = 1;
-        g.rows_per_split = (nblk + ns - 1) / ns;
-        ns = (nblk + g.rows_per_split - 1) / g.rows_per_split;
-        hipLaunchKernelGGL(taps_wgrad_blk_kernel, dim3((unsigned)(tiles * ntaps), (unsigned)ns), dim3(256), 0, st, grad_y, x, partial, g);
+        hipLaunchKernelGGL(taps_wgrad_blk_kernel, dim3((unsigned)(tiles * ntaps), (unsigned)p.splits), dim3(256), 0, st, grad_y, x,
+                           partial, g);
     }
-    hipLaunchKernelGGL(taps_wgrad_reduce_kernel, dim3(grid_of((long long)ntaps * Cin * Cout, 4096)), dim3(256), 0, st, partial, (int)ns,
-                       ntaps, Cout, Cin, grad_w);
+    launch_split_reduce(partial, (int)p.splits, ntaps, Cout, Cin, grad_w, st);
     return (int)hipGetLastError();
 }
 
@@ -693,7 +551,7 @@ int vqvae_gated_activation_backward_f32(const float *t1, const float *t2, const 
 
 size_t vqvae_gather_rows_backward_workspace_bytes(int64_t n, int C, int rows) {
     if (n < 1 || n > INT32_MAX || C < 1 || rows < 1 || rows > (1 << 24)) return 0;
-    return gb_plan(n, C, rows).total;
+    return segsum_plan(n, rows, C).total;
 }
 
 int vqvae_gather_rows_backward_f32(const int64_t *idx, const float *grad_out, int64_t n, int C, int rows, float *grad_table,
@@ -701,24 +559,14 @@ int vqvae_gather_rows_backward_f32(const int64_t *idx, const float *grad_out, in
     if (!idx || !grad_out || !grad_table) return VQVAE_ERR_NULL;
     if (n < 1 || C < 1 || rows < 1) return VQVAE_ERR_SHAPE;
     if (n > INT32_MAX || rows > (1 << 24)) return VQVAE_ERR_OVERFLOW;
-    const GbPlan p = gb_plan(n, C, rows);
+    const SegsumPlan p = segsum_plan(n, rows, C);
     if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);
-    unsigned *keys = reinterpret_cast<unsigned *>(ws + p.off_keys), *keys_out = reinterpret_cast<unsigned *>(ws + p.off_keys_out);
-    int *vals = reinterpret_cast<int *>(ws + p.off_vals), *vals_out = reinterpret_cast<int *>(ws + p.off_vals_out);
-    int *offsets = reinterpret_cast<int *>(ws + p.off_offsets), *unit_start = reinterpret_cast<int *>(ws + p.off_units);
-    double *partial = reinterpret_cast<double *>(ws + p.off_partials);
-    hipLaunchKernelGGL(gb_keys_kernel, dim3(grid_of(n, 4096)), dim3(256), 0, st, reinterpret_cast<const long long *>(idx), (long long)n,
-                       rows, keys, vals);
-    size_t sb = p.sort_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + p.off_sort, sb, keys, keys_out, vals, vals_out, (int)n, 0, p.key_bits, st);
+    const hipError_t e = launch_segsum(p, grad_out, reinterpret_cast<const long long *>(idx), n, rows, C, 1, 1, ws, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(gb_offsets_kernel, dim3((unsigned)((rows + 1 + 255) / 256)), dim3(256), 0, st, keys_out, (long long)n, rows, offsets);
-    hipLaunchKernelGGL(gb_units_kernel, dim3(1), dim3(1024), 0, st, offsets, rows, unit_start);
-    hipLaunchKernelGGL(gb_segsum_kernel, dim3((unsigned)p.max_units), dim3(256), 0, st, grad_out, vals_out, offsets, unit_start, rows, C,
-                       partial);
-    hipLaunchKernelGGL(gb_final_kernel, dim3((unsigned)(((long long)rows * C + 255) / 256)), dim3(256), 0, st, unit_start, partial, rows, C,
+    hipLaunchKernelGGL(gb_final_kernel, dim3((unsigned)(((long long)rows * C + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const int *>(ws + p.off_units), reinterpret_cast<const double *>(ws + p.off_partials), rows, C,
                        grad_table);
     return (int)hipGetLastError();
 }
@@ -749,7 +597,7 @@ int vqvae_cross_entropy_backward_f32(const float *logits, const int64_t *targets
     return (int)hipGetLastError();
 }
 
-size_t vqvae_bias_grad_wide_workspace_bytes(int C) { return C < 1 ? 0 : (size_t)kBwBlocks * C * sizeof(double); }
+size_t vqvae_bias_grad_wide_workspace_bytes(int C) { return C < 1 ? 0 : (size_t)kColsumBlocks * C * sizeof(double); }
 
 int vqvae_bias_grad_wide_f32(const float *grad_y, int64_t P, int C, float *grad_b, void *workspace, size_t workspace_bytes,
                              vqvae_stream_t stream) {
@@ -758,13 +606,11 @@ int vqvae_bias_grad_wide_f32(const float *grad_y, int64_t P, int C, float *grad_
     if (P * (int64_t)C > ((int64_t)1 << 40)) return VQVAE_ERR_OVERFLOW;
     if (!workspace || workspace_bytes < vqvae_bias_grad_wide_workspace_bytes(C)) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    long long nb = (P + 63) / 64;                          // at least 64 rows per block
-    if (nb > kBwBlocks) nb = kBwBlocks;
-    const long long rpb = (P + nb - 1) / nb;
-    nb = (P + rpb - 1) / rpb;
+    const ReducePlan p = bias_grad_wide_plan(P);
     double *partial = static_cast<double *>(workspace);
-    hipLaunchKernelGGL(bias_wide_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, grad_y, (long long)P, C, rpb, partial);
-    hipLaunchKernelGGL(bias_wide_final_kernel, dim3((unsigned)C), dim3(256), 0, st, partial, (int)nb, C, grad_b);
+    hipLaunchKernelGGL(bias_wide_partial_kernel, dim3((unsigned)p.splits), dim3(256), 0, st, grad_y, (long long)P, C, p.per_split,
+                       partial);
+    launch_colsum_final(partial, (int)p.splits, C, grad_b, st);
     return (int)hipGetLastError();
 }
 

@@ -17,143 +17,13 @@
 //   vqvae_recon_loss_f32       main.py:75-76 and the three scalars of :81-83 packed into one 3-float buffer
 //                              (one D2H copy per step instead of three).
 //   vqvae_recon_loss_backward_f32   d/dx_hat of mean((x_hat - x)^2) / var.
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "train_reduce.h"
 
 namespace vqvae {
 
-constexpr int kBwdChunk = 512;        // rows per workgroup of the segmented sum (a code owns ceil(count/512) units)
 constexpr int kReconGrid = 1024;      // partial sums of the reconstruction loss
 
-struct BwdPlan {
-    size_t off_keys, off_keys_out, off_vals, off_vals_out, off_offsets, off_units, off_partials, off_sort, sort_bytes, total;
-    long long max_units;
-    int key_bits;
-};
-
-static BwdPlan bwd_plan(long long N, int K, int D) {
-    BwdPlan p;
-    p.key_bits = 1;
-    while ((1 << p.key_bits) < K) ++p.key_bits;
-    p.off_keys = 0;
-    p.off_keys_out = align_up(p.off_keys + (size_t)N * 4, 256);
-    p.off_vals = align_up(p.off_keys_out + (size_t)N * 4, 256);
-    p.off_vals_out = align_up(p.off_vals + (size_t)N * 4, 256);
-    p.off_offsets = align_up(p.off_vals_out + (size_t)N * 4, 256);
-    p.off_units = align_up(p.off_offsets + (size_t)(K + 1) * 4, 256);
-    p.max_units = N / kBwdChunk + K;                       // sum_k ceil(count_k / chunk) <= N/chunk + K
-    p.off_partials = align_up(p.off_units + (size_t)(K + 1) * 4, 256);
-    p.off_sort = align_up(p.off_partials + (size_t)p.max_units * D * sizeof(double), 256);
-    size_t sb = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sb, (const unsigned *)nullptr, (unsigned *)nullptr,
-                                             (const int *)nullptr, (int *)nullptr, (int)N, 0, p.key_bits, 0);
-    p.sort_bytes = sb;
-    p.total = align_up(p.off_sort + sb, 256);
-    return p;
-}
-
-__global__ __launch_bounds__(256) void vqb_keys_kernel(const long long *__restrict__ idx, long long N, int K,
-                                                       unsigned *__restrict__ keys, int *__restrict__ vals) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
-        const long long k = idx[i];
-        keys[i] = (unsigned)(k < 0 ? 0 : (k >= K ? K - 1 : k));
-        vals[i] = (int)i;
-    }
-}
-
-// offsets[k] = first sorted position whose key is >= k (k = 0..K): one binary search per code
-__global__ __launch_bounds__(256) void vqb_offsets_kernel(const unsigned *__restrict__ keys, long long N, int K,
-                                                          int *__restrict__ offsets) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k > K) return;
-    long long lo = 0, hi = N;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < (unsigned)k) lo = mid + 1; else hi = mid;
-    }
-    offsets[k] = (int)lo;
-}
-
-// unit_start[k] = number of work units (chunks of kBwdChunk sorted rows) owned by codes < k; one block scans K+1
-__global__ __launch_bounds__(1024) void vqb_units_kernel(const int *__restrict__ offsets, int K, int *__restrict__ unit_start) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (K + 1023) / 1024;
-    int local = 0;
-    for (int j = 0; j < per; ++j) {
-        const int k = tid * per + j;
-        if (k < K) local += (offsets[k + 1] - offsets[k] + kBwdChunk - 1) / kBwdChunk;
-    }
-    part[tid] = local;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                    // inclusive scan
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - local;                             // exclusive prefix of this thread's codes
-    for (int j = 0; j < per; ++j) {
-        const int k = tid * per + j;
-        if (k < K) {
-            unit_start[k] = run;
-            run += (offsets[k + 1] - offsets[k] + kBwdChunk - 1) / kBwdChunk;
-        }
-    }
-    if (tid == 1023) unit_start[K] = part[1023];
-}
-
-// partial[unit][c] = sum over the unit's (<= kBwdChunk, sorted) rows of z_i[c]   (fp64, fixed order).  Work is
-// proportional to the rows, however skewed the histogram (a freshly initialised codebook uses a handful of codes).
-__global__ __launch_bounds__(256) void vqb_segsum_kernel(const float *__restrict__ z, const int *__restrict__ rows,
-                                                         const int *__restrict__ offsets,
-                                                         const int *__restrict__ unit_start, int K, int D, int HW,
-                                                         int rowmajor, double *__restrict__ partial) {
-    __shared__ double red[256];
-    const int unit = blockIdx.x, tid = threadIdx.x;
-    if (unit >= unit_start[K]) return;
-    int lo_k = 0, hi_k = K;                                  // last k with unit_start[k] <= unit
-    while (hi_k - lo_k > 1) {
-        const int mid = (lo_k + hi_k) >> 1;
-        if (unit_start[mid] <= unit) lo_k = mid; else hi_k = mid;
-    }
-    const int k = lo_k;
-    const int a = offsets[k] + (unit - unit_start[k]) * kBwdChunk;
-    const int b = a + kBwdChunk < offsets[k + 1] ? a + kBwdChunk : offsets[k + 1];
-    // D <= 256: threads [0, G*D) are G row groups of D channels each
-    const int G = 256 / D;
-    const int g = tid / D, c = tid - g * D;
-    double acc = 0.0;
-    if (g < G) {
-        auto zat = [&](long long r) {
-            if (rowmajor) return z[(size_t)r * D + c];
-            const long long bb = r / HW;
-            const int hw = (int)(r - bb * HW);
-            return z[((size_t)bb * D + c) * HW + hw];
-        };
-        int j = a + g;
-        for (; j + 3 * G < b; j += 4 * G) {                 // four rows' (index, value) loads in flight; same summation order
-            long long r[4];
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) r[q] = rows[j + q * G];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = zat(r[q]);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc += (double)v[q];
-        }
-        for (; j < b; j += G) acc += (double)zat(rows[j]);
-    }
-    red[tid] = acc;
-    __syncthreads();
-    if (tid < D) {
-        double t = 0.0;
-        for (int q = 0; q < G; ++q) t += red[q * D + tid];
-        partial[(size_t)unit * D + tid] = t;
-    }
-}
-
+// dL/dE_k from the units of the sorted segmented sum (launch_segsum, train_reduce.h): cnt_k e_k - sum of the code's rows
 __global__ __launch_bounds__(256) void vqb_codebook_grad_kernel(const float *__restrict__ cb,
                                                                 const int *__restrict__ offsets,
                                                                 const int *__restrict__ unit_start,
@@ -239,12 +109,7 @@ __global__ __launch_bounds__(256) void recon_partial_kernel(const float *__restr
             const float d = a[i] - b[i];
             acc += (double)(d * d);
         }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_sum_f64(red, threadIdx.x, acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -255,12 +120,7 @@ __global__ __launch_bounds__(256) void recon_final_kernel(const double *__restri
     __shared__ double red[256];
     double acc = 0.0;
     for (int i = threadIdx.x; i < np; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_sum_f64(red, threadIdx.x, acc);
     if (threadIdx.x == 0) {
         const float mse = (float)(red[0] / (double)n);          // torch.mean((x_hat - x)**2)   main.py:75
         const float recon = mse * inv_var;                       //   / x_train_var
@@ -279,42 +139,16 @@ __global__ __launch_bounds__(256) void recon_backward_kernel(const float *__rest
         grad[i] = s * (a[i] - b[i]);
 }
 
-// The per-code segmented sum shared by the codebook gradient and the EMA update: keys, stable radix sort of the rows by code,
-// per-code offsets, unit starts, fp64 partial sums per unit (workspace laid out by bwd_plan).  Fixed order throughout.
-static hipError_t launch_code_segsum(const BwdPlan &p, const float *z_e, const long long *idx, long long N, int K, int D, int HW,
-                                     int rowmajor, char *ws, hipStream_t st) {
-    unsigned *keys = reinterpret_cast<unsigned *>(ws + p.off_keys);
-    unsigned *keys_out = reinterpret_cast<unsigned *>(ws + p.off_keys_out);
-    int *vals = reinterpret_cast<int *>(ws + p.off_vals);
-    int *vals_out = reinterpret_cast<int *>(ws + p.off_vals_out);
-    int *offsets = reinterpret_cast<int *>(ws + p.off_offsets);
-    int *unit_start = reinterpret_cast<int *>(ws + p.off_units);
-    double *partial = reinterpret_cast<double *>(ws + p.off_partials);
-    long long grid = (N + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(vqb_keys_kernel, dim3((unsigned)grid), dim3(256), 0, st, idx, N, K, keys, vals);
-    size_t sb = p.sort_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + p.off_sort, sb, keys, keys_out, vals, vals_out, (int)N, 0,
-                                                      p.key_bits, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(vqb_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st, keys_out, N, K,
-                       offsets);
-    hipLaunchKernelGGL(vqb_units_kernel, dim3(1), dim3(1024), 0, st, offsets, K, unit_start);
-    hipLaunchKernelGGL(vqb_segsum_kernel, dim3((unsigned)p.max_units), dim3(256), 0, st, z_e, vals_out, offsets,
-                       unit_start, K, D, HW, rowmajor, partial);
-    return hipSuccess;
-}
-
 // ---- EMA codebook update (arXiv 1711.00937 Appendix A.1; include/vqvae_hip.h, vqvae_vq_ema_update_f32) ----
 
 struct EmaPlan {
-    BwdPlan seg;                 // the segmented sum's workspace, first
+    SegsumPlan seg;                 // the segmented sum's workspace, first
     size_t off_nk, off_n, total;
 };
 
 static EmaPlan ema_plan(long long N, int K, int D) {
     EmaPlan p;
-    p.seg = bwd_plan(N, K, D);
+    p.seg = segsum_plan(N, K, D);
     p.off_nk = align_up(p.seg.total, 256);
     p.off_n = align_up(p.off_nk + (size_t)K * sizeof(double), 256);
     p.total = align_up(p.off_n + sizeof(double), 256);
@@ -398,7 +232,7 @@ extern "C" {
 
 size_t vqvae_vq_backward_workspace_bytes(int64_t N, int K, int D) {
     if (N < 1 || N > INT32_MAX || K < 1 || K > 16384 || D < 1 || D > 256) return 0;
-    return bwd_plan(N, K, D).total;
+    return segsum_plan(N, K, D).total;
 }
 
 int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t *idx, const float *grad_zq,
@@ -421,17 +255,15 @@ int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t
         const bool vec4 = rowmajor && (D & 3) == 0 &&
                           !((reinterpret_cast<uintptr_t>(z_e) | reinterpret_cast<uintptr_t>(codebook) | reinterpret_cast<uintptr_t>(grad_z) |
                              reinterpret_cast<uintptr_t>(grad_zq)) & 15);
-        long long grid = ((vec4 ? total >> 2 : total) + 255) / 256;
-        if (grid > 65536) grid = 65536;
-        hipLaunchKernelGGL(vqb_gradz_kernel, dim3((unsigned)grid), dim3(256), 0, st, z_e, codebook,
+        hipLaunchKernelGGL(vqb_gradz_kernel, dim3(grid_of(vec4 ? total >> 2 : total)), dim3(256), 0, st, z_e, codebook,
                            reinterpret_cast<const long long *>(idx), grad_zq, grad_loss, total, D, (int)HW, vec4 ? -1 : rowmajor,
                            gz_scale, grad_z);
     }
     if (grad_codebook) {
-        const BwdPlan p = bwd_plan(N, K, D);
+        const SegsumPlan p = segsum_plan(N, K, D);
         if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
         char *ws = static_cast<char *>(workspace);
-        const hipError_t e = launch_code_segsum(p, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
+        const hipError_t e = launch_segsum(p, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
         if (e != hipSuccess) return (int)e;
         const int *offsets = reinterpret_cast<const int *>(ws + p.off_offsets);
         const int *unit_start = reinterpret_cast<const int *>(ws + p.off_units);
@@ -461,7 +293,7 @@ int vqvae_vq_ema_update_f32(const float *z_e, const int64_t *idx, int64_t B, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rowmajor = (flags & VQVAE_VQ_ROWMAJOR) ? 1 : 0;
     char *ws = static_cast<char *>(workspace);
-    const hipError_t e = launch_code_segsum(p.seg, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
+    const hipError_t e = launch_segsum(p.seg, z_e, reinterpret_cast<const long long *>(idx), N, K, D, (int)HW, rowmajor, ws, st);
     if (e != hipSuccess) return (int)e;
     const int *offsets = reinterpret_cast<const int *>(ws + p.seg.off_offsets);
     const int *unit_start = reinterpret_cast<const int *>(ws + p.seg.off_units);
@@ -486,11 +318,9 @@ int vqvae_recon_loss_f32(const float *x_hat, const float *x, int64_t n, float in
     if (!workspace || workspace_bytes < vqvae_recon_loss_workspace_bytes()) return VQVAE_ERR_WORKSPACE;
     if ((reinterpret_cast<uintptr_t>(x_hat) | reinterpret_cast<uintptr_t>(x)) & 15) return VQVAE_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    long long grid = ((n >> 2) + 255) / 256;
-    if (grid > kReconGrid) grid = kReconGrid;
-    if (grid < 1) grid = 1;
+    const unsigned grid = grid_of(n >> 2, kReconGrid);
     double *partial = static_cast<double *>(workspace);
-    hipLaunchKernelGGL(recon_partial_kernel, dim3((unsigned)grid), dim3(256), 0, st, x_hat, x, (long long)n, partial);
+    hipLaunchKernelGGL(recon_partial_kernel, dim3(grid), dim3(256), 0, st, x_hat, x, (long long)n, partial);
     hipLaunchKernelGGL(recon_final_kernel, dim3(1), dim3(256), 0, st, partial, (int)grid, (long long)n, inv_var,
                        embedding_loss, perplexity, out3);
     return (int)hipGetLastError();
@@ -501,9 +331,7 @@ int vqvae_recon_loss_backward_f32(const float *x_hat, const float *x, int64_t n,
     if (!x_hat || !x || !grad_x_hat) return VQVAE_ERR_NULL;
     if (n < 1) return VQVAE_ERR_SHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    long long grid = (n + 255) / 256;
-    if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL(recon_backward_kernel, dim3((unsigned)grid), dim3(256), 0, st, x_hat, x, (long long)n,
+    hipLaunchKernelGGL(recon_backward_kernel, dim3(grid_of(n)), dim3(256), 0, st, x_hat, x, (long long)n,
                        (float)(2.0 * (double)inv_var / (double)n), grad_loss, grad_x_hat);
     return (int)hipGetLastError();
 }
