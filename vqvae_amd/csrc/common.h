@@ -184,8 +184,16 @@ struct VqFuse {
     int K, K32;
     float *zq; long long *idx; int *hist; double *partials;
 };
+// The decoder's head riding behind that quantizer (conv_res_pair8_h2_kernel<2, true, false, false, true>, models/decoder.py:28-30):
+// the wave that quantized an image goes on with its z_q rows, which never leave the chip (vq->zq must be NULL).  The arguments
+// are those of the stand-alone launch conv_res_pair_forward_impl(VQVAE_CONVT_3x3_S1, z_q, ...), Cin = 64.
+struct ResPairDecHead { const float *packed_front; const float *bias_front; const float *packed_w1; const float *packed_w2; int flags;
+                        float *y; int *out_amax; };
 struct ResPairPost { const float *packed; const float *bias; int Cout; float *out; int *zero = nullptr; int zero_n = 0;
-                     const VqFuse *vq = nullptr; bool debug_ze = false; };      // debug_ze: the fused quantizer also writes its z_e rows to `out`
+                     const VqFuse *vq = nullptr; bool debug_ze = false;         // debug_ze: the fused quantizer also writes its z_e rows to `out`
+                     const ResPairDecHead *dec_head = nullptr; };
+// loss / perplexity of the quantizer (vq_finalize_kernel's arguments) for a kernel that computes them on the side
+struct VqFinalizeArgs { const double *partials; int nparts; const int *hist; int K; long long N; int D; float beta; float *loss; float *perplexity; };
 bool res_pair_post_supported(int C, int Cout);
 int res_pair_forward_impl(const float *x, const float *packed_w1, const float *packed_w2, int64_t B, int H, int W, int C,
                           int Rh, int flags, float *y, hipStream_t stream, const int *in_amax, int *out_amax,
@@ -224,7 +232,8 @@ int enc_front_forward_impl(const float *x_nchw, const float *packed_in, const fl
                            int *out_amax, int *zero_buf = nullptr, int zero_n = 0);
 bool dec_tail_supported(int h4, int w4, int C, int C1, int Cout);
 int dec_tail_forward_impl(const float *x, const float *packed2, const float *bias2, const float *packed4, const float *bias4,
-                          int64_t B, int h4, int w4, int C, int C1, int Cout, float *y_nchw, hipStream_t st, const int *in_amax);
+                          int64_t B, int h4, int w4, int C, int C1, int Cout, float *y_nchw, hipStream_t st, const int *in_amax,
+                          const VqFinalizeArgs *finalize = nullptr);      // finalize: workgroup 0 also computes loss / perplexity
 int conv_in_forward_impl(const float *x_nchw, const float *packed, const float *bias, int64_t B, int H, int W, int Cin,
                          int Cout, int flags, float *y, hipStream_t stream, int *out_amax, const float *ep_mask = nullptr);
 

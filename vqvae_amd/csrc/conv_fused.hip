@@ -26,7 +26,19 @@ namespace vqvae {
 #define CRP_MINW 2      // waves per SIMD the register allocation must allow (tools/build_variant.py crp1 -DCRP_MINW=1: 388 registers, no
                         // scratch, one workgroup per CU)
 #endif
-template <int NT3, bool VQ = false, bool GATHER = false, bool ZEOUT = false>
+// DECHEAD (with <2, true> only): the decoder's head (models/decoder.py:28-30: conv-transpose 3x3 + residual stack, the <0> instance's
+// work) rides behind the quantizer.  The wave that quantized an image holds its z_q rows in LDS; it takes its own pixel row into
+// registers and runs the same front conv and layers once more with the decoder's weights: z_q is neither stored nor loaded, and
+// the forward has one kernel boundary less.  Operand order per accumulator = the <0> instance's: the same bits.
+struct DecHeadArgs {
+    FrontConv fc;                                          // Cin = 64
+    const u32x4 *w1img, *w2img;
+    const int *hdr1, *hdr2;
+    int flags;
+    float *out;
+    int *out_amax;
+};
+template <int NT3, bool VQ = false, bool GATHER = false, bool ZEOUT = false, bool DECHEAD = false>
 __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kernel(const float *__restrict__ in, FrontConv fc,
                                                                    const u32x4 *__restrict__ w1img, const u32x4 *__restrict__ w2img,
                                                                    float *__restrict__ out, int B, int flags,
@@ -34,7 +46,8 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                                                                    const int *__restrict__ in_amax, int *__restrict__ out_amax,
                                                                    const u32x4 *__restrict__ w3img, const int *__restrict__ hdr3,
                                                                    const float *__restrict__ bias3, float *__restrict__ out3,
-                                                                   int *__restrict__ zero_buf, int zero_n, VqFuse vq) {
+                                                                   int *__restrict__ zero_buf, int zero_n, VqFuse vq, DecHeadArgs dh) {
+    static_assert(!DECHEAD || (VQ && !GATHER && !ZEOUT), "the decoder's head continues the quantizing instance");
     static_assert(NT3 == 0 || NT3 == 1 || NT3 == 2 || NT3 == 4, "the 1x1 post conv streams through NT3 weight stages of 16 KiB");
     static_assert(!VQ || (NT3 == 2 && CRP_NW == 4), "the fused quantizer takes the 64-channel z_e of four images per workgroup");
     constexpr int NT2 = 4, C = 128, MT = 2, PX = 64, HP = PX + 1, PLANE = HP * 2;
@@ -49,7 +62,10 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     constexpr int WBUF = 18 * 64;
     // stages after the front conv: 18 (two residual layers) + NT3 (post conv) + (VQ) one per four 32-code tiles of the codebook
     const int nvq = VQ ? (vq.K32 >> 7) : 0;
-    const int NSTAGE = 18 + NT3 + nvq;
+    int NSTAGE = 18 + NT3 + nvq;
+    // the weight set in use (DECHEAD: the encoder's, then the decoder's; wave-uniform)
+    FrontConv fcc = fc;
+    const u32x4 *w1c = w1img, *w2c = w2img;
     __shared__ u32x4 Wb_all[2 * WBUF];
     // fused quantizer: per-wave tables (vq_unit.h), the workgroup's histogram and loss partials
     __shared__ __attribute__((aligned(16))) unsigned char vq_tab_all[VQ ? CRP_NW * 1040 : 16];
@@ -63,10 +79,14 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     if constexpr (VQ) {
         for (int i = threadIdx.x; i < vq.K; i += CRP_NW * 64) vq_hist_s[i] = 0;        // (a stage barrier precedes every use)
     }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    u32x4 *As = As_all + wave * TILE4;
-    float *Hs = reinterpret_cast<float *>(As);
+    const int tid = threadIdx.x, wave = tid >> 6;
+    // what a lane derives from its number: set once -- and once more by DECHEAD's second run (lane_setup)
+    int lane, l31, h;
+    u32x4 *As;
+    float *Hs;
+    unsigned dma_lane;                                     // (dma: this lane's constant byte offset)
+    int spx[MT];
+    unsigned tapok[MT], tapok0[MT];
     const bool relu_out = flags & kFlagReluOut;            // of the SECOND residual layer (the stack's final ReLU)
     constexpr int cpt = C >> 5;
 
@@ -77,23 +97,41 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
         for (int i = tid; i < zero_n; i += CRP_NW * 64) zero_buf[i] = 0;
 
     // pixel bookkeeping: the residual 3x3 (taps t/3-1, t%3-1) and the front conv (taps from the geometry masks)
-    int spx[MT];
-    unsigned tapok[MT], tapok0[MT];
+    auto lane_setup = [&](int t_id) {
+        lane = t_id & 63;
+        l31 = lane & 31;
+        h = lane >> 5;
+        As = As_all + (t_id >> 6) * TILE4;
+        Hs = reinterpret_cast<float *>(As);
+        dma_lane = (unsigned)lane * 16u;
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        spx[mt] = 32 * mt + l31;
-        const int y = spx[mt] >> 3, x = spx[mt] & 7;
-        unsigned m = 0, m0 = 0;
+        for (int mt = 0; mt < MT; ++mt) {
+            spx[mt] = 32 * mt + l31;
+            const int y = spx[mt] >> 3, x = spx[mt] & 7;
+            unsigned m = 0;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-            if (yy >= 0 && yy < 8 && xx >= 0 && xx < 8) m |= 1u << t;
-            const int y0 = y + (int)((fc.dym >> (4 * t)) & 15) - 8, x0 = x + (int)((fc.dxm >> (4 * t)) & 15) - 8;
-            if (y0 >= 0 && y0 < 8 && x0 >= 0 && x0 < 8) m0 |= 1u << t;
+            for (int t = 0; t < 9; ++t) {
+                const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+                if (yy >= 0 && yy < 8 && xx >= 0 && xx < 8) m |= 1u << t;
+            }
+            tapok[mt] = m;
         }
-        tapok[mt] = m;
-        tapok0[mt] = m0;
-    }
+    };
+    lane_setup(tid);
+    auto front_masks = [&]() {                             // of the front conv in use
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int y = spx[mt] >> 3, x = spx[mt] & 7;
+            unsigned m0 = 0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int y0 = y + (int)((fcc.dym >> (4 * t)) & 15) - 8, x0 = x + (int)((fcc.dxm >> (4 * t)) & 15) - 8;
+                if (y0 >= 0 && y0 < 8 && x0 >= 0 && x0 < 8) m0 |= 1u << t;
+            }
+            tapok0[mt] = m0;
+        }
+    };
+    front_masks();
 
     // Y[mt][nt][r]: channel 32 nt + (r & 3) + 8 (r >> 2) + 4 h of pixel 32 mt + l31
     f32x16 Y[MT][NT2];
@@ -104,14 +142,13 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     // The waits are explicit here (dma_wait_sync); the compiler's own vmcnt waits stay correct (loads return in order and an
     // uncounted outstanding load only makes a counted wait longer).
     // (scalar source base + this lane's constant byte offset: no vector instruction and no address register per piece)
-    const unsigned dma_lane = (unsigned)lane * 16u;
     auto dma = [&](const u32x4 *src_uniform, u32x4 *dst_piece) {
         const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)(char *)dst_piece);
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(dma_lane), "s"(src_uniform), "s"(lds) : "memory");
     };
     // the nine taps of slice sl of the residual 3x3 -> buffer `buf`: piece p = tap * 2 + term
     auto dma_slice = [&](int sl, int buf) {
-        const u32x4 *base = w1img + (size_t)(sl >> 1) * 256 + (sl & 1) * 64;
+        const u32x4 *base = w1c + (size_t)(sl >> 1) * 256 + (sl & 1) * 64;
         for (int p = wave_u; p < 18; p += CRP_NW)
             dma(base + (size_t)(p >> 1) * cpt * 256 + (p & 1) * 128, Wb_all + buf * WBUF + p * 64);
     };
@@ -129,7 +166,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
             if (wave_u == 0) dma(reinterpret_cast<const u32x4 *>(vq.seeds) + (size_t)j * 32, Wb_all + buf * WBUF + 16 * 64);
         }
         else if (k >= 18) dma_linear(w3img + (size_t)(k - 18) * 1024, buf);
-        else if (k % 9 == 8) dma_linear(w2img, buf);
+        else if (k % 9 == 8) dma_linear(w2c, buf);
         else dma_slice(k % 9, buf);
     };
     auto dma_wait_sync = [&]() {
@@ -139,8 +176,21 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     float ymax = 0.0f;                                     // largest |Y| (the next consumer's scale)
     int wstage = 0;                                        // weight stages of the front conv (LDS buffer parity)
     // =========================================== front conv ===========================================
-    {
-        const int cpt0 = fc.Cin >> 5;
+    // FROMZ (DECHEAD's second run): the lane's pixel row is in registers -- zr[cc] = chunk cc of two -- and nothing is loaded.
+    // always_inline and instantiated per call, as `layer` below
+    f32x4 zr[2][8];
+    f32x16(&Yo)[MT][NT2] = Y;
+    float &ymax_o = ymax;
+    int &wstage_o = wstage;
+    auto front = [&](auto FZ) __attribute__((always_inline)) {
+        constexpr bool FROMZ = decltype(FZ)::value;
+        const FrontConv &fc = fcc;
+        // (the accumulators, the maximum and the stage counter are this function's own and handed over at the end: captured by
+        // reference, the map would not be promoted to registers before the tap loop is optimised -- 1144 B of scratch per lane)
+        f32x16 Y[MT][NT2];
+        float ymax = 0.0f;
+        int wstage = 0;
+        const int cpt0 = FROMZ ? 2 : fc.Cin >> 5;
         const float *src = in + ((size_t)(img_ok ? img : 0) * PX + lane) * fc.Cin;     // this lane's pixel row
         // decode-from-indices (vqvae_decode_f32; the GATHER instance): `in` is the codebook and a pixel's row is its code's row --
         // z_q never exists in memory (visualization.ipynb:358-365).  An index outside [0, K) never reads the codebook: its
@@ -154,6 +204,11 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
         const bool gany = GATHER && __builtin_amdgcn_ballot_w64(gbad) != 0;
         f32x4 raw[8];
         auto load_raw0 = [&](int cc) {
+            if constexpr (FROMZ) {                         // (called for chunk 0 up front and for chunk 1 inside chunk 0: cpt0 = 2)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) raw[j] = cc == 0 ? zr[0][j] : zr[1][j];
+                return;
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) raw[j] = *reinterpret_cast<const f32x4 *>(src + 32 * cc + 4 * j);
             if (gany) {
@@ -163,13 +218,19 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
             }
         };
         float m = 0.0f;
-        const int given = (in_amax && img_ok) ? in_amax[img] : -1;
-        if (given >= 0) m = __int_as_float(given);
-        else for (int cc = 0; cc < cpt0; ++cc) {
-            load_raw0(cc);
+        const int given = (!FROMZ && in_amax && img_ok) ? in_amax[img] : -1;      // (z_q has no producer that publishes its maximum)
+        auto fold_raw = [&]() {
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(raw[j].x), __builtin_fabsf(raw[j].y)), fmaxf(__builtin_fabsf(raw[j].z), __builtin_fabsf(raw[j].w))));
+        };
+        if constexpr (FROMZ) {
+            load_raw0(0); fold_raw();
+            load_raw0(1); fold_raw();
+        } else if (given >= 0) m = __int_as_float(given);
+        else for (int cc = 0; cc < cpt0; ++cc) {
+            load_raw0(cc);
+            fold_raw();
         }
         const int kx = wave_scale_exp(img_ok ? m : 0.0f);
         const float xs = __builtin_ldexpf(1.0f, kx), d0 = __builtin_ldexpf(1.0f, -kx);
@@ -223,14 +284,15 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                 // this stage's weights are in; everyone is done with the other buffer.  The next chunk's eight activation loads
                 // go out BEHIND tap 1's weights and may stay in flight across tap 1's wait (they are its youngest requests):
                 // in front of tap 0's wait, as before, every chunk sat out their whole latency at that barrier
-                if (tap == 1 && cc + 1 < cpt0) {
+                // (FROMZ: no activation loads are in flight, every request is a weight piece)
+                if (!FROMZ && tap == 1 && cc + 1 < cpt0) {
                     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                     __syncthreads();
                 } else dma_wait_sync();
                 if (tap + 1 < 9) dma_front(cc, tap + 1, (wstage + 1) & 1);
                 else if (cc + 1 < cpt0) dma_front(cc + 1, 0, (wstage + 1) & 1);
                 else dma_stage(0, (wstage + 1) & 1);           // the first slice of the first residual layer
-                if (tap == 0 && cc + 1 < cpt0) load_raw0(cc + 1);
+                if (tap == 0 && cc + 1 < cpt0) load_raw0(FROMZ ? 1 : cc + 1);
                 const u32x4 *wt = Wb_all + (wstage & 1) * WBUF + lane;
                 // group g = (t, nt): weights one group ahead of the matrix instructions
                 u32x4 Wc0 = wt[0], Wc1 = wt[64];
@@ -265,8 +327,15 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                     for (int q = 0; q < 4; q += 2)
                         SCALE2_BIAS_RELU2(Y[mt][nt][4 * g + q], Y[mt][nt][4 * g + q + 1], dv[q], dv[q + 1], bv[q], bv[q + 1], ymax);
             }
-    }
-    lds_order_wave();
+        lds_order_wave();
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT2; ++nt) Yo[mt][nt] = Y[mt][nt];
+        ymax_o = ymax;
+        wstage_o = wstage;
+    };
+    front(std::false_type{});
 
     // =========================================== residual layers from Y ===========================================
     // stage k: wait for its weights, start the next stage's, return this lane's column of its buffer
@@ -618,7 +687,18 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                            [&](int rr, int jc) { return *zchunk(rr, jc); },
                            [&](int rr, int c) { return reinterpret_cast<const float *>(zchunk(rr, c >> 2))[c & 3]; });
             const int j16 = lane & 15, g4 = lane >> 4;
-            const float sacc = vqu::epilogue_sp<false, MT>(R, lane, vq.cb, vq.K, [&](int t, int i) { return *zchunk(32 * t + 4 * i + g4, j16); },
+            float sacc;
+            if constexpr (DECHEAD) {
+                // every 16-byte chunk of the straight-through z_q goes back into the LDS slot its z_e chunk came from (the lane that read
+                // a slot writes it): no global store.  Then this lane's own pixel row, all 16 chunks, into registers
+                sacc = vqu::epilogue_sp<false, MT>(R, lane, vq.cb, vq.K, [&](int t, int i) { return *zchunk(32 * t + 4 * i + g4, j16); },
+                                                   nullptr, img_ok ? PX : 0, vq.idx + (size_t)(img_ok ? img : 0) * PX, vq_hist_s, nullptr, 0, 0u,
+                                                   [&](int t, int i, const f32x4 &o) { *zchunk(32 * t + 4 * i + g4, j16) = o; });
+                lds_order_wave();
+#pragma unroll
+                for (int c16 = 0; c16 < 16; ++c16) zr[c16 >> 3][c16 & 7] = *zchunk(lane, c16);
+            } else
+            sacc = vqu::epilogue_sp<false, MT>(R, lane, vq.cb, vq.K, [&](int t, int i) { return *zchunk(32 * t + 4 * i + g4, j16); },
                                              (img_ok && vq.zq) ? vq.zq + (size_t)img * PX * 64 : nullptr, img_ok ? PX : 0,
                                              vq.idx + (size_t)(img_ok ? img : 0) * PX, vq_hist_s);
             // loss partial and histogram of the workgroup (fixed order: run-to-run bitwise loss / perplexity)
@@ -626,7 +706,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o);
             if (lane == 0) vq_red_s[wave_u] = dacc;
-            __syncthreads();
+            __syncthreads();                        // (DECHEAD: and every wave has its z_q rows out of the weight buffers)
             if (tid == 0) {
                 double sum = 0.0;
                 for (int w = 0; w < CRP_NW; ++w) sum += vq_red_s[w];
@@ -635,6 +715,39 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
             for (int k = tid; k < vq.K; k += CRP_NW * 64) {
                 const int c = vq_hist_s[k];
                 if (c) atomicAdd(&vq.hist[k], c);
+            }
+            if constexpr (DECHEAD) {
+                // ================= the decoder's head on this image's z_q (zr), as the <0> instance runs it =================
+                // the decoder's weight set and its four scale tables (behind the barrier above; a stage barrier precedes every use);
+                // waves without an image keep every barrier
+                // (every value a lane derives from its number is derived AGAIN from an opaque copy: shared with the first run, these
+                // live across the whole kernel, are the cheapest values to spill by the allocator's measure and the hottest to
+                // reload -- 11 scratch loads per 3x3 slice instead of 1)
+                int tid2 = tid;
+                asm volatile("" : "+v"(tid2));
+                lane_setup(tid2);
+                fcc = dh.fc;
+                w1c = dh.w1img;
+                w2c = dh.w2img;
+                NSTAGE = 18;
+                for (int i = tid; i < 288; i += CRP_NW * 64)
+                    dw_s[i] = i < 128 ? h2_dw(dh.fc.hdr)[i] : (i < 160 ? h2_dw(dh.hdr1)[i - 128] : h2_dw(dh.hdr2)[i - 160]);
+                front_masks();
+                front(std::true_type{});
+                layer(std::integral_constant<int, 0>{}, true);
+                layer(std::integral_constant<int, 1>{}, (dh.flags & kFlagReluOut) != 0);
+                if (dh.out_amax && img_ok) publish_amax_exclusive(dh.out_amax, img, ymax, lane);
+                if (img_ok) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < NT2; ++nt) {
+                            float v[16];
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) v[r] = Y[mt][nt][r];
+                            store_tile(v, dh.out + (wbase + mt * 32) * C + nt * 32, C);
+                        }
+                }
             }
         } else
         if (img_ok) {
@@ -963,8 +1076,15 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
                                                               const int *__restrict__ hdr2, const float *__restrict__ bias2,
                                                               TailGeom tg, const u32x4 *__restrict__ w4img,
                                                               const int *__restrict__ hdr4, const float *__restrict__ bias4,
-                                                              float *__restrict__ out, int B, const int *__restrict__ in_amax) {
+                                                              float *__restrict__ out, int B, const int *__restrict__ in_amax,
+                                                              VqFinalizeArgs fin) {
     constexpr int NT = 2, MT = 2, PX = 64, HP = PX + 1, PLANE = HP * 2, CIN = 128, CPT = CIN / 32, CO = 3;
+    // The quantizer's loss / perplexity on the side (fin.loss != NULL): the partials and the histogram are complete when this kernel
+    // starts (stream order: their producer is an earlier kernel), only the two scalars depend on them, and workgroup 0 is the first
+    // to start -- no one-workgroup launch between two kernels that fill the GPU.  Same function, same bits as vq_finalize_kernel.
+    __shared__ double fin_red[256];
+    if (fin.loss && blockIdx.x == 0)
+        vqu::finalize_block(fin_red, fin.partials, fin.nparts, fin.hist, fin.K, fin.N, fin.D, fin.beta, fin.loss, fin.perplexity);
     constexpr int TILE4 = 2 * 2 * PLANE;                   // [k-step 2][term 2][half 2][pixel + zero] = 520 units
     constexpr int WBUF = 16 * 64, NSTAGE = 34;             // per pass: 4 chunks x 4 tap pairs (16 pieces each) + the second layer's image
     __shared__ u32x4 As_all[4 * TILE4];
@@ -1286,6 +1406,31 @@ int vqvae::conv_res_pair_forward_impl(int kind, const float *x, const float *pac
                  make_geom(VQVAE_CONV_1x1, 1, 8, 8, C, post->Cout, 0, g3) != VQVAE_OK)) return VQVAE_ERR_UNSUPPORTED;
     if (post && post->vq && (post->Cout != 64 || CRP_NW != 4 || post->vq->K32 % 128 || post->vq->K32 > 1024 || !post->vq->partials))
         return VQVAE_ERR_UNSUPPORTED;
+    // the decoder's head behind the quantizer: the stand-alone launch's arguments (conv-transpose 3x3 on z_q: Cin = 64), same widths
+    const ResPairDecHead *hd = post ? post->dec_head : nullptr;
+    DecHeadArgs dha{};
+    if (hd) {
+        ConvGeom gd;
+        if (!post->vq || post->debug_ze || post->vq->zq || !hd->packed_front || !hd->packed_w1 || !hd->packed_w2 || !hd->y ||
+            (reinterpret_cast<uintptr_t>(hd->y) & 15) || make_geom(VQVAE_CONVT_3x3_S1, B, H, W, 64, C, 0, gd) != VQVAE_OK)
+            return VQVAE_ERR_UNSUPPORTED;
+        const char *hfd = reinterpret_cast<const char *>(hd->packed_front) + packed_h2_offset(gd, VQVAE_CONVT_3x3_S1);
+        dha.fc.wimg = reinterpret_cast<const u32x4 *>(hfd + h2_header_bytes(gd.ntile));
+        dha.fc.hdr = reinterpret_cast<const int *>(hfd);
+        dha.fc.bias = hd->bias_front;
+        dha.fc.dym = gd.dymask[0];
+        dha.fc.dxm = gd.dxmask[0];
+        dha.fc.Cin = 64;
+        const char *d1 = reinterpret_cast<const char *>(hd->packed_w1) + (size_t)9 * cpt * (1024 * sizeof(float) + 3072 * sizeof(unsigned short));
+        const char *d2 = reinterpret_cast<const char *>(hd->packed_w2) + (size_t)cpt * (1024 * sizeof(float) + 3072 * sizeof(unsigned short));
+        dha.w1img = reinterpret_cast<const u32x4 *>(d1 + h2_header_bytes(1));
+        dha.w2img = reinterpret_cast<const u32x4 *>(d2 + h2_header_bytes((C + 31) / 32));
+        dha.hdr1 = reinterpret_cast<const int *>(d1);
+        dha.hdr2 = reinterpret_cast<const int *>(d2);
+        dha.flags = hd->flags;
+        dha.out = hd->y;
+        dha.out_amax = hd->out_amax;
+    }
     prof_begin(VQVAE_PROF_RES_LAYER, st);
     if (post) {
         const char *h3 = reinterpret_cast<const char *>(post->packed) + packed_h2_offset(g3, VQVAE_CONV_1x1);
@@ -1293,14 +1438,18 @@ int vqvae::conv_res_pair_forward_impl(int kind, const float *x, const float *pac
         const int *hd3 = reinterpret_cast<const int *>(h3);
 #define CRP_POST(NT3_)                                                                                                          \
     hipLaunchKernelGGL((conv_res_pair8_h2_kernel<NT3_>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B, flags, hd1, hd2, \
-                       in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, VqFuse{})
+                       in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, VqFuse{}, DecHeadArgs{})
         if (post->vq && post->debug_ze) {
             hipLaunchKernelGGL((conv_res_pair8_h2_kernel<2, true, false, true>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B, flags,
-                               hd1, hd2, in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, *post->vq);
+                               hd1, hd2, in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, *post->vq, DecHeadArgs{});
+        } else if (post->vq && hd) {
+            // ... and the decoder's head behind the quantizer: neither z_e nor z_q is written
+            hipLaunchKernelGGL((conv_res_pair8_h2_kernel<2, true, false, false, true>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B,
+                               flags, hd1, hd2, in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, *post->vq, dha);
         } else if (post->vq) {
             // the quantizer rides behind the 1x1 conv: z_e is never written (post->out unused)
             hipLaunchKernelGGL((conv_res_pair8_h2_kernel<2, true>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B, flags,
-                               hd1, hd2, in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, *post->vq);
+                               hd1, hd2, in_amax, out_amax, w3h, hd3, post->bias, post->out, post->zero, post->zero_n, *post->vq, DecHeadArgs{});
         } else
         switch (post->Cout / 32) {
             case 1: CRP_POST(1); break;
@@ -1314,10 +1463,10 @@ int vqvae::conv_res_pair_forward_impl(int kind, const float *x, const float *pac
             gf.idx = reinterpret_cast<long long *>(const_cast<int64_t *>(gather_idx));       // (read only; x = the codebook)
             gf.K = gather_K;
             hipLaunchKernelGGL((conv_res_pair8_h2_kernel<0, false, true>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B, flags,
-                               hd1, hd2, in_amax, out_amax, nullptr, nullptr, nullptr, nullptr, nullptr, 0, gf);
+                               hd1, hd2, in_amax, out_amax, nullptr, nullptr, nullptr, nullptr, nullptr, 0, gf, DecHeadArgs{});
         } else
         hipLaunchKernelGGL((conv_res_pair8_h2_kernel<0>), dim3(gtc), dim3(CRP_NW * 64), 0, st, x, fc, w1h, w2h, y, (int)B, flags, hd1, hd2,
-                           in_amax, out_amax, nullptr, nullptr, nullptr, nullptr, nullptr, 0, VqFuse{});
+                           in_amax, out_amax, nullptr, nullptr, nullptr, nullptr, nullptr, 0, VqFuse{}, DecHeadArgs{});
     }
     prof_end(VQVAE_PROF_RES_LAYER, st);
     return (int)hipGetLastError();
@@ -1351,7 +1500,8 @@ int vqvae::enc_front_forward_impl(const float *x_nchw, const float *packed_in, c
 bool vqvae::dec_tail_supported(int h4, int w4, int C, int C1, int Cout) { return h4 == 8 && w4 == 8 && C == 128 && C1 == 64 && Cout == 3; }
 
 int vqvae::dec_tail_forward_impl(const float *x, const float *packed2, const float *bias2, const float *packed4, const float *bias4,
-                                 int64_t B, int h4, int w4, int C, int C1, int Cout, float *y_nchw, hipStream_t st, const int *in_amax) {
+                                 int64_t B, int h4, int w4, int C, int C1, int Cout, float *y_nchw, hipStream_t st, const int *in_amax,
+                                 const VqFinalizeArgs *finalize) {
     if (!x || !packed2 || !packed4 || !y_nchw) return VQVAE_ERR_NULL;
     if (B < 1 || !dec_tail_supported(h4, w4, C, C1, Cout)) return VQVAE_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y_nchw)) & 15) return VQVAE_ERR_UNSUPPORTED;
@@ -1367,7 +1517,7 @@ int vqvae::dec_tail_forward_impl(const float *x, const float *packed2, const flo
     hipLaunchKernelGGL(dec_tail8_h2_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, x,
                        reinterpret_cast<const u32x4 *>(h2 + h2_header_bytes(g.ntile)), reinterpret_cast<const int *>(h2), bias2, tg,
                        reinterpret_cast<const u32x4 *>(h4p + h2_header_bytes(1) + cells * 2048 * sizeof(unsigned short)),
-                       reinterpret_cast<const int *>(h4p), bias4, y_nchw, (int)B, in_amax);
+                       reinterpret_cast<const int *>(h4p), bias4, y_nchw, (int)B, in_amax, finalize ? *finalize : VqFinalizeArgs{});
     prof_end(VQVAE_PROF_CONV_OUT, st);
     return (int)hipGetLastError();
 }

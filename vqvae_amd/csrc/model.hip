@@ -125,6 +125,8 @@ struct FwdPlan {
     bool fused;          // all four: every per-image maximum that is read has ONE producing wave that stores it plainly -- no fill
     bool vq_fuse;        // and the quantizer can run inside the encoder's last kernel (vq_fuse_ok)
     bool zq_amax;        // the decoder's first conv, handed z_q's maxima, reads them (the 8x8-map kernel measures its image itself)
+    bool mid_fuse;       // vqvae_forward_f32: the decoder's head runs inside the quantizing kernel (z_q never leaves the chip): three launches
+    bool tail_finalize;  // vqvae_forward_f32: loss / perplexity come from the decoder's last kernel, not from a launch between the big ones
 };
 FwdPlan fwd_plan(const VqvaeDims *d, int H, int W, int flags) {
     FwdPlan p{};
@@ -147,6 +149,13 @@ FwdPlan fwd_plan(const VqvaeDims *d, int H, int W, int flags) {
 #endif
     p.fused = p.enc_front && p.enc_pair_post && p.dec_front && p.dec_tail;
     p.vq_fuse = p.fused && vq_fuse_ok(d->n_embeddings, d->embedding_dim, flags);
+    const bool plain = p.vq_fuse && !(flags & kVqFormFlags) && !(flags & VQVAE_FWD_DEBUG_ZE);     // (the debug route keeps the separate launches)
+#ifndef VQVAE_NO_MID_FUSION
+    p.mid_fuse = plain && p.dec_front;
+#endif
+#ifndef VQVAE_NO_TAIL_FINALIZE
+    p.tail_finalize = plain && p.dec_tail;
+#endif
     return p;
 }
 
@@ -307,7 +316,8 @@ int vqvae_resstack_f32(const float *packed_w1, const float *packed_w2, const flo
 // vq: quantize inside the last kernel (fused 32x32 path only; z_e is then NOT written and zero_buf is cleared by the FIRST kernel)
 static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, int W, float *z_e, void *workspace,
                        size_t workspace_bytes, hipStream_t st, const FwdPlan &p, int *am_given, int *zero_buf = nullptr, int zero_n = 0,
-                       bool *zeroed = nullptr, const VqFuse *vq = nullptr, float *hid_given = nullptr, bool debug_ze = false) {
+                       bool *zeroed = nullptr, const VqFuse *vq = nullptr, float *hid_given = nullptr, bool debug_ze = false,
+                       const ResPairDecHead *dec_head = nullptr) {
     if (!w || !x || !z_e || !workspace) return VQVAE_ERR_NULL;
     const VqvaeDims *d = &w->dims;
     if (!dims_ok(d) || B < 1 || H < 4 || W < 4 || H % 4 || W % 4) return VQVAE_ERR_SHAPE;
@@ -345,7 +355,7 @@ static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, 
     // encoder.py:35-38 + vqvae.py:33 in ONE launch where the shapes allow (8x8 latent maps, h_dim 128, two residual layers):
     // 3x3 conv + ReLU, both residual layers and the pre-quantisation conv; none of the three intermediate maps is written
     if (p.enc_pair_post) {
-        const ResPairPost post{w->pre, w->pre_b, d->embedding_dim, z_e, vq ? nullptr : zero_buf, vq ? 0 : zero_n, vq, vq && debug_ze};
+        const ResPairPost post{w->pre, w->pre_b, d->embedding_dim, z_e, vq ? nullptr : zero_buf, vq ? 0 : zero_n, vq, vq && debug_ze, dec_head};
         if (zeroed) *zeroed = zero_buf != nullptr;
         return conv_res_pair_forward_impl(VQVAE_CONV_3x3_S1, b, w->enc4, w->enc4_b, h, w->enc_res_w1, w->enc_res_w2, B, H / 4, W / 4, h,
                                           d->res_h_dim, VQVAE_CONV_RELU_OUT, nullptr, st, am1, nullptr, &post);
@@ -389,8 +399,11 @@ static int *zq_amax_slot(const VqvaeDims *d, int64_t B, int *am) { return am + (
 // gather_idx: z_q = the codebook and the first kernel takes pixel p's row from code gather_idx[p] (p.dec_front only)
 static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h4, int w4, float *x_hat, void *workspace,
                        size_t workspace_bytes, hipStream_t st, const FwdPlan &p, int *am_given, bool zq_amax_given = false,
-                       float *hid_given = nullptr, const int64_t *gather_idx = nullptr) {
-    if (!w || !z_q || !x_hat || !workspace) return VQVAE_ERR_NULL;
+                       float *hid_given = nullptr, const int64_t *gather_idx = nullptr, ResPairDecHead *head_out = nullptr,
+                       bool head_done = false, const VqFinalizeArgs *finalize = nullptr) {
+    // head_out: do not launch -- report the arguments of the first kernel (p.dec_front) for the caller to fuse elsewhere;
+    // head_done: that kernel has run (its output and maxima lie where head_out said); finalize: see dec_tail_forward_impl
+    if (!w || (!z_q && !head_out && !head_done) || !x_hat || !workspace) return VQVAE_ERR_NULL;
     const VqvaeDims *d = &w->dims;
     if (!dims_ok(d) || B < 1 || h4 < 1 || w4 < 1) return VQVAE_ERR_SHAPE;
     Carve c{static_cast<char *>(workspace), workspace_bytes};
@@ -414,7 +427,7 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
     // from one more pass over z_q (array [2 + n_res_layers] of the region)
     if (gather_idx && !p.dec_front) return VQVAE_ERR_UNSUPPORTED;
     int *amz = nullptr;
-    if (am && !gather_idx && p.zq_amax) {
+    if (am && !gather_idx && p.zq_amax && !head_out && !head_done) {
         amz = zq_amax_slot(d, B, am);
         if (!zq_amax_given) act_absmax_impl(z_q, B, (long long)h4 * w4 * d->embedding_dim, amz, st);
     }
@@ -423,6 +436,11 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
     // decoder.py:28-30 in one launch where the shapes allow: conv-transpose 3x3 (+ the stack's first ReLU) and both residual layers
     if (p.dec_front) {
         int *aout = am ? am + (size_t)2 * B : nullptr;
+        if (head_out) {
+            *head_out = ResPairDecHead{w->dec0, w->dec0_b, w->dec_res_w1, w->dec_res_w2, VQVAE_CONV_RELU_OUT, a, aout};
+            return VQVAE_OK;
+        }
+        if (!head_done)
         if ((rc = conv_res_pair_forward_impl(VQVAE_CONVT_3x3_S1, z_q, w->dec0, w->dec0_b, d->embedding_dim, w->dec_res_w1, w->dec_res_w2, B, h4,
                                              w4, h, d->res_h_dim, VQVAE_CONV_RELU_OUT, a, st, amz, aout, nullptr, gather_idx,
                                              d->n_embeddings)) != 0) return rc;
@@ -437,7 +455,8 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
     }
     // decoder.py:31-35 in ONE launch on 8x8 latent maps: the 16x16 x h/2 map between the two stride-2 transposed convs is never written
     if (p.dec_tail)
-        return dec_tail_forward_impl(t, w->dec2, w->dec2_b, w->dec4, w->dec4_b, B, h4, w4, h, h / 2, d->in_ch, x_hat, st, amt);
+        return dec_tail_forward_impl(t, w->dec2, w->dec2_b, w->dec4, w->dec4_b, B, h4, w4, h, h / 2, d->in_ch, x_hat, st, amt, finalize);
+    if (finalize) return VQVAE_ERR_UNSUPPORTED;
     float *u = (t == a) ? b : a;
     int *am_u = am ? am + (size_t)(3 + d->n_res_layers) * B : nullptr;       // dec2's output maxima for the last layer
     if ((rc = conv_forward_impl(VQVAE_CONVT_4x4_S2, t, w->dec2, w->dec2_b, B, h4, w4, h, h / 2, VQVAE_CONV_RELU_OUT | cf, u, st, amt, am_u)) != 0) return rc;
@@ -536,11 +555,22 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
         const bool debug_ze = vq_flags & VQVAE_FWD_DEBUG_ZE;
         if (debug_ze && !idx) return VQVAE_ERR_NULL;
         if (debug_ze) vf.partials = reinterpret_cast<double *>(idx_ws);
+        // Nothing between the two big kernels that the decoder does not need: loss / perplexity come from the decoder's last kernel
+        // (p.tail_finalize), and where the decoder's head runs inside the quantizing kernel (p.mid_fuse) z_q is never stored either:
+        // enc_front, the quantizing kernel with the decoder's head, dec_tail -- three launches
+        const VqFinalizeArgs fin{vf.partials, (int)((B + 3) / 4), hist, d->n_embeddings, (long long)rows, d->embedding_dim, d->beta, loss, perplexity};
+        ResPairDecHead head{};
+        if (p.mid_fuse) {
+            if ((rc = decoder_run(w, nullptr, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, p, am_dec, false, nullptr, nullptr, &head)) != 0) return rc;
+            vf.zq = nullptr;
+        }
         if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, p, am2, hist, d->n_embeddings, &hist_zeroed, &vf, nullptr,
-                              debug_ze)) != 0) return rc;
-        if ((rc = vq_finalize_impl(vf.partials, (int)((B + 3) / 4), hist, d->n_embeddings, (int64_t)rows, d->embedding_dim, d->beta, loss,
+                              debug_ze, p.mid_fuse ? &head : nullptr)) != 0) return rc;
+        if (!p.tail_finalize &&
+            (rc = vq_finalize_impl(vf.partials, (int)((B + 3) / 4), hist, d->n_embeddings, (int64_t)rows, d->embedding_dim, d->beta, loss,
                                    perplexity, st)) != 0) return rc;
-        return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, p, am_dec);                      // :36
+        return decoder_run(w, z_q, B, H / 4, W / 4, x_hat, acts, acts_bytes, st, p, am_dec, false, nullptr, nullptr, nullptr, p.mid_fuse,
+                           p.tail_finalize ? &fin : nullptr);                                                    // :36
     }
     bool zq_amax_done = false;
     if ((rc = encoder_run(w, x, B, H, W, z_e, acts, acts_bytes, st, p, am2, p.fused ? hist : nullptr, d->n_embeddings, &hist_zeroed,

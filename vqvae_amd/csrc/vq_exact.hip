@@ -21,6 +21,7 @@
 // image [c/8][c&1][code][(c%8)/2], read conflict-free with ds_read_b128.
 #include "common.h"
 #include "vq_device.h"
+#include "vq_unit.h"
 
 namespace vqvae {
 
@@ -371,37 +372,7 @@ __global__ __launch_bounds__(256) void vq_finalize_kernel(const double *__restri
                                                           float *__restrict__ loss,
                                                           float *__restrict__ perplexity) {
     __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    const float fn = (float)N;
-    for (int k = tid; k < K; k += 256) {
-        const float p = (float)hist[k] / fn;
-        const float lg = (float)log((double)(p + 1e-10f));
-        s += (double)(p * lg);
-    }
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const double ent = red[0];
-    __syncthreads();
-    // squared-error partials: fixed-order tree (deterministic run to run)
-    double q = 0.0;
-    for (int i = tid; i < nparts; i += 256) q += partials[i];
-    red[tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *perplexity = (float)exp(-(double)(float)ent);
-        const float m = (float)(red[0] / ((double)N * (double)D));
-        const float bm = beta * m;
-        *loss = m + bm;
-    }
+    vqu::finalize_block(red, partials, nparts, hist, K, N, D, beta, loss, perplexity);
 }
 
 __global__ __launch_bounds__(256) void vq_onehot_kernel(const long long *__restrict__ idx, long long N,

@@ -13,6 +13,7 @@
 #pragma once
 #include "common.h"
 #include "vq_track.h"
+#include <type_traits>
 
 #ifndef VQ_ZQ_STORE_AUX
 #define VQ_ZQ_STORE_AUX 0          // cache policy of the z_q stores (gfx950 aux bits: 1 = sc0, 2 = nt, 16 = sc1); see vq_track.hip
@@ -377,11 +378,17 @@ __device__ __forceinline__ void exact_end_sp(RowsSp<T> &R, Flagged &F, int ntask
 
 // epilogue() with the rows' indices on their speaker lanes: frow / zq_unit / nleft / idx_unit / hist_s / NCHW arguments as there
 // HALF (NCHW, four-wave form): `tile_f` holds 32 x 32 floats only -- z_q leaves in two halves of 32 channels
-template <bool NCHW = false, int T = 2, bool HALF = false, class FRow>
+// sink (row-major form only): instead of the global store, sink(t, i, o) takes the 16-byte chunk lane & 15 of row 32 t + 4 i + (lane >> 4)
+// of the straight-through z_q -- the bits the store would have written (the fused decoder head keeps them in LDS)
+struct NoSink {};
+template <bool NCHW = false, int T = 2, bool HALF = false, class FRow, class Sink = NoSink>
 __device__ __forceinline__ float epilogue_sp(const RowsSp<T> &R, int lane, const float *__restrict__ cb, int K, FRow &&frow,
                                              float *__restrict__ zq_unit, int nleft, long long *__restrict__ idx_unit,
-                                             int *__restrict__ hist_s, float *tile_f = nullptr, int HW = 0, unsigned zq_bytes = 0u) {
+                                             int *__restrict__ hist_s, float *tile_f = nullptr, int HW = 0, unsigned zq_bytes = 0u,
+                                             Sink &&sink = Sink{}) {
     constexpr int D = 64, RU = 32 * T;
+    constexpr bool kSink = !std::is_same<typename std::remove_reference<Sink>::type, NoSink>::value;
+    static_assert(!kSink || !NCHW, "the sink takes row-major chunks");
     const int j16 = lane & 15, g4 = lane >> 4;
     const auto cb_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(cb), 0, (unsigned)K * (D * 4), 0x00020000);
     f32x4 ev[T][8];
@@ -418,7 +425,9 @@ __device__ __forceinline__ float epilogue_sp(const RowsSp<T> &R, int lane, const
             f32x4 o;
             o.x = zv.x + d0; o.y = zv.y + d1; o.z = zv.z + d2; o.w = zv.w + d3;
             sqv[t][i] = ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-            if constexpr (!NCHW) {
+            if constexpr (kSink) {
+                sink(t, i, o);
+            } else if constexpr (!NCHW) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, o), zq_rs, vo[(t * 8 + i) >> 2] + (unsigned)((t * 8 + i) & 3) * 1024u, 0, VQ_ZQ_STORE_AUX);
             } else if constexpr (HALF) {
                 oh[i] = o;                                  // (collected: the tile takes them in two halves below)
@@ -478,6 +487,46 @@ __device__ __forceinline__ float epilogue_sp(const RowsSp<T> &R, int lane, const
             for (int i = 0; i < 8; ++i) sacc += 32 * t + 4 * i + g4 < nleft ? sqv[t][i] : 0.0f;
     }
     return sacc;
+}
+
+// loss = m + beta*m with m = sum((z_q-z)^2)/(N*D) (models/quantizer.py:63-64); perplexity = exp(-sum p log(p + 1e-10)), p = hist/N
+// (:70-71).  One workgroup of 256 threads, all of them in the call; red = 256 doubles of LDS.  Two fixed-order trees: the same bits
+// from vq_finalize_kernel and from the workgroup of dec_tail8_h2_kernel that runs it on the side.
+__device__ __forceinline__ void finalize_block(double *red, const double *__restrict__ partials, int nparts, const int *__restrict__ hist,
+                                               int K, long long N, int D, float beta, float *__restrict__ loss,
+                                               float *__restrict__ perplexity) {
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    const float fn = (float)N;
+    for (int k = tid; k < K; k += 256) {
+        const float p = (float)hist[k] / fn;
+        const float lg = (float)log((double)(p + 1e-10f));
+        s += (double)(p * lg);
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    const double ent = red[0];
+    __syncthreads();
+    // squared-error partials: fixed-order tree (deterministic run to run)
+    double q = 0.0;
+    for (int i = tid; i < nparts; i += 256) q += partials[i];
+    red[tid] = q;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *perplexity = (float)exp(-(double)(float)ent);
+        const float m = (float)(red[0] / ((double)N * (double)D));
+        const float bm = beta * m;
+        *loss = m + bm;
+    }
+    __syncthreads();                                    // (red may be reused by the caller)
 }
 
 }  // namespace vqu
