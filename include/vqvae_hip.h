@@ -535,8 +535,26 @@ VQVAE_API int vqvae_train_reduction_plan(int what, const int64_t *dims, int ndim
  *   status (B,) int32, 0 or VQVAE_SAMPLE_* bits.  The draw: m = max l, e_k = exp(l_k - m), C_k the running sums of e_k in ascending
  *   k (a fixed order), S = C_{K-1}; the code is the smallest k with u S < C_k, or, where rounding leaves none, the largest k with
  *   e_k > 0.  A position whose logits are not all finite sets VQVAE_SAMPLE_NONFINITE and that image gets code 0 from there on.
- *   workspace: vqvae_pixelcnn_sample_workspace_bytes (0 = unsupported), never read before the call writes it.                    */
+ *   workspace: vqvae_pixelcnn_sample_workspace_bytes (0 = unsupported), never read before the call writes it.
+ * vqvae_pixelcnn_sample_ex_f32 -- the same call with sampling controls; vqvae_pixelcnn_sample_f32 is it with (1, 0, 1, NULL), which
+ *   runs the plain kernel.  VQVAE_ERR_SHAPE for a temperature that is not finite and > 0, top_k < 0, top_p outside (0, 1] or NaN;
+ *   every other check as above, all before any HIP call.  Same packed image, same workspace size.  In order, per position:
+ *     top_k (1 <= top_k < K; 0 or >= K: off): code j stays iff #{i : l_i > l_j or (l_i == l_j and i < j)} < top_k, on the raw fp32
+ *       logits: exactly top_k codes, ties at the threshold go to the lower index; top_k = 1 is greedy decoding.
+ *     temperature: m = max l, e_k = expf((l_k - m) / temperature) for the codes that stay (a correctly rounded divide, exact at 1),
+ *       0 for the others.
+ *     top_p (1: off): rank the codes by (l descending, index ascending); with S the sum of all e_k, code k stays iff the mass of
+ *       the codes ranked before it is < top_p S, so the first always stays; the others get e_k = 0.  The masses are fp32 sums in a
+ *       fixed order that depends on K and the logits only (no floating-point atomics): the same bits in every run and batch.
+ *     the draw: the rule above over the e_k that remain (running sums in ascending k, the smallest k with u S' < C_k, the same
+ *       fallback).
+ *   given (B, H, W) int64, may be NULL: a value >= 0 fixes the code of that position -- it is written to samples, the uniform is
+ *   ignored and the layers' state advances as after a draw of that code; a negative value means draw.  A value >= K sets
+ *   VQVAE_SAMPLE_GIVEN_RANGE and that image gets code 0 from there on.  logits, when asked for, are written at given positions
+ *   too (teacher-forced logits); when they are not, the head is not computed there, which changes no other output.  Logits are
+ *   not checked for VQVAE_SAMPLE_NONFINITE at given positions.                                                                   */
 #define VQVAE_SAMPLE_NONFINITE 1
+#define VQVAE_SAMPLE_GIVEN_RANGE 2
 VQVAE_API size_t vqvae_pixelcnn_sample_packed_bytes(int K, int dim, int n_layers, int n_classes);
 VQVAE_API int vqvae_pixelcnn_sample_pack_f32(const float *const *params, int n_params, int K, int dim, int n_layers, int n_classes,
                                              void *packed, size_t packed_bytes, vqvae_stream_t stream);
@@ -544,6 +562,10 @@ VQVAE_API size_t vqvae_pixelcnn_sample_workspace_bytes(int64_t B, int H, int W, 
 VQVAE_API int vqvae_pixelcnn_sample_f32(const void *packed, size_t packed_bytes, const int64_t *label, const float *uniforms, int64_t B,
                                         int H, int W, int K, int dim, int n_layers, int n_classes, int64_t *samples, float *logits,
                                         int32_t *status, void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_pixelcnn_sample_ex_f32(const void *packed, size_t packed_bytes, const int64_t *label, const float *uniforms,
+                                           int64_t B, int H, int W, int K, int dim, int n_layers, int n_classes, float temperature,
+                                           int top_k, float top_p, const int64_t *given, int64_t *samples, float *logits,
+                                           int32_t *status, void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
 /* ------------------------------------------------------------------- whole path
  * models/vqvae.py:29-44 as ONE call: Encoder (models/encoder.py:28-43) -> pre_quantization_conv (models/vqvae.py:33)

@@ -133,6 +133,8 @@ SIGNATURES = {
     "vqvae_pixelcnn_sample_pack_f32": (_i32, [C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "vqvae_pixelcnn_sample_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
     "vqvae_pixelcnn_sample_f32": (_i32, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_pixelcnn_sample_ex_f32": (_i32, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _vp,
+                                            _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

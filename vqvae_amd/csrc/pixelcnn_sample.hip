@@ -83,6 +83,10 @@ struct PsArgs {
     float *ws;
     size_t ws_per_image;
     int S, dim, K, nl, ncls;
+    // the filtered instantiations only (pixelcnn_sample_kernel<true, .>)
+    float temperature, top_p;            // top_p >= 1: off
+    int top_k;                           // 0: off
+    const long long *given;              // (B, S, S), < 0: draw; may be NULL
 };
 
 __device__ __forceinline__ float fma4(f32x4 w, f32x4 v, float acc) {
@@ -142,7 +146,68 @@ __device__ __forceinline__ void matvec(const float *__restrict__ w, const float 
     }
 }
 
-__global__ __launch_bounds__(kPsThreads) void pixelcnn_sample_kernel(PsArgs a) {
+// ---- the filtered draw (pixelcnn_sample_kernel<true, .>): top-k, temperature, top-p -----------------------------------------------
+// Both truncations are a threshold on the codes ranked by (logit descending, index ascending).  The threshold is found by bisection
+// on an order-preserving integer key of the fp32 logit, two key bits per step: each step takes the block's count (top-k) or mass
+// (top-p) above three candidate keys.  Counts are integers; masses are fp32 sums in one fixed tree (a thread's codes in ascending
+// order, an xor butterfly over the wave, the waves in sequence), so they depend on K and the logits alone.  Every operation of that
+// tree is monotone in its operands and a dropped code adds an exact zero, so the mass above a key never grows with the key: the
+// bisection is exact for the sums it uses.  Ties at a threshold are cut by index in a second, short step.
+constexpr int kPsCand = 3;                            // candidate thresholds per bisection step: two bits per block reduction
+
+// a > b <=> ps_key(a) > ps_key(b) for finite a, b; -0 ranks as +0
+__device__ __forceinline__ unsigned ps_key(float v) {
+    const unsigned b = __float_as_uint(v + 0.0f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// v[i] <- the block's sum of v[i], the same bits in every thread.  red: kPsWaves * N words; consecutive calls alternate between two
+// such buffers, so a call needs one barrier: a wave that runs ahead writes the other buffer
+template <typename T, int N>
+__device__ __forceinline__ void block_sums(T (&v)[N], T *red, int lane, int wave) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int sh = kWave / 2; sh >= 1; sh >>= 1) v[i] = v[i] + __shfl_xor(v[i], sh);
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < N; ++i) red[wave * N + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        T s = red[i];
+        for (int w = 1; w < kPsWaves; ++w) s = s + red[w * N + i];
+        v[i] = s;
+    }
+}
+
+// the smallest v in [0, 2^kBits) with pred(v), for a monotone pred (false .. false true .. true) that holds at 2^kBits - 1.
+// eval(t, ok) sets ok[i] = pred(t[i]) for the tops t[i] of the first three of the four buckets that the next two bits select
+template <int kBits, typename F>
+__device__ __forceinline__ unsigned ps_bisect(F eval) {
+    static_assert(kBits % 2 == 0, "two bits per step");
+    unsigned lo = 0;
+    for (int sh = kBits - 2; sh >= 0; sh -= 2) {
+        unsigned t[kPsCand];
+        bool ok[kPsCand];
+#pragma unroll
+        for (int i = 0; i < kPsCand; ++i) t[i] = lo | ((unsigned)i << sh) | ((1u << sh) - 1u);
+        eval(t, ok);
+        int d = 0;
+#pragma unroll
+        for (int i = 0; i < kPsCand; ++i) d += !ok[i];
+        lo |= (unsigned)d << sh;
+    }
+    return lo;
+}
+
+// kFilter = false: the plain draw (temperature 1, every code, every position drawn).  kFilter = true adds the filtered draw and the
+// given codes; it is a separate instantiation so that the plain one keeps its registers, LDS and barriers.
+// Two workgroups share a CU once B exceeds the CU count.  The plain kernel fits twice (126 VGPRs, 43 KiB of LDS); the filtered one
+// (75 KiB of LDS) takes 141 VGPRs, one workgroup per CU and 1.8 x the time at B = 1024.  kTwoPerCu holds it to 128 VGPRs, which costs
+// four spilled dwords and 5 % at small B: the launch picks it for B above the CU count only.  Same arithmetic, same bits
+template <bool kFilter, bool kTwoPerCu>
+__global__ __launch_bounds__(kPsThreads, kTwoPerCu ? 4 : 1) void pixelcnn_sample_kernel(PsArgs a) {
     __shared__ int idx_ring[4 * kPsMaxSide];                       // sampled codes of rows y-3 .. y (row r at r & 3)
     __shared__ __attribute__((aligned(16))) float vin[kPsTapsH0 * kPsMaxDim];   // the horizontal stack's tap vector
     __shared__ __attribute__((aligned(16))) float gout[kPsMaxDim];              // gate output of the horizontal stack
@@ -172,6 +237,17 @@ __global__ __launch_bounds__(kPsThreads) void pixelcnn_sample_kernel(PsArgs a) {
     const int k_lo = tid * ck < K ? tid * ck : K, k_hi = k_lo + ck < K ? k_lo + ck : K;
     const int owner = (K - 1) / ck;                                   // the thread holding the last code
     if (tid == 0) status_s = 0;
+    float *ev = nullptr;                                              // e_k after the filters (this thread touches k_lo .. k_hi only)
+    unsigned *sel_red = nullptr;                                      // block_sums' two buffers
+    int ph = 0;
+    if constexpr (kFilter) {
+        __shared__ float ev_s[kPsMaxK];
+        __shared__ unsigned sel_red_s[2 * kPsWaves * kPsCand];
+        ev = ev_s;
+        sel_red = sel_red_s;
+    }
+    auto red_next = [&]() { ph ^= 1; return sel_red + ph * kPsWaves * kPsCand; };
+    (void)red_next;
 
     for (int y = 0; y < S; ++y) {
         // ------------------------------------------------------------------ row pass: hv_L, V_L, v2h_L of row y, every layer
@@ -260,6 +336,28 @@ __global__ __launch_bounds__(kPsThreads) void pixelcnn_sample_kernel(PsArgs a) {
                 }
                 __syncthreads();
             }
+            const size_t pos = ((size_t)b * S + y) * S + x;
+            long long gv = -1;                                           // >= 0: the code of (y, x) is given, nothing is drawn
+            if constexpr (kFilter)
+                if (a.given) gv = a.given[pos];
+            if (gv >= 0) {
+                // the head only where its logits are asked for; the state of the layers is already that of this position
+                if (a.logits) {
+                    matvec<true>(w0, b0, hs, d4, kPsHidden, hidden, g, l);
+                    __syncthreads();
+                    matvec<false>(w2, b2, hidden, kPsHidden / 4, K, lg, g, l);
+                    __syncthreads();
+                    for (int k = tid; k < K; k += kPsThreads) a.logits[(((size_t)b * K + k) * S + y) * S + x] = lg[k];
+                }
+                if (tid == 0) {
+                    if (gv >= K) status_s |= VQVAE_SAMPLE_GIVEN_RANGE;
+                    const int k = status_s ? 0 : (int)gv;
+                    idx_ring[(y & 3) * kPsMaxSide + x] = k;
+                    a.out[pos] = k;
+                }
+                __syncthreads();
+                continue;
+            }
             // output_conv (:111-115)
             matvec<true>(w0, b0, hs, d4, kPsHidden, hidden, g, l);
             __syncthreads();
@@ -284,8 +382,110 @@ __global__ __launch_bounds__(kPsThreads) void pixelcnn_sample_kernel(PsArgs a) {
             m = red_f[0];
             bad = red_i[0];
             for (int w = 1; w < kPsWaves; ++w) { m = fmaxf(m, red_f[w]); bad |= red_i[w]; }
+            if constexpr (kFilter) {
+                // a. top-k: vk the top_k-th largest key, i.e. the smallest key with fewer than top_k codes above it; the codes above
+                // it stay, and of those at it the first top_k - (codes above) by index
+                const bool tk = a.top_k >= 1 && a.top_k < K;
+                unsigned vk = 0;
+                int rank = 0, need = 0;
+                if (tk) {
+                    vk = ps_bisect<32>([&](const unsigned *t, bool *ok) {
+                        int c[kPsCand] = {0, 0, 0};
+                        for (int k = k_lo; k < k_hi; ++k) {
+                            const unsigned key = ps_key(lg[k]);
+#pragma unroll
+                            for (int i = 0; i < kPsCand; ++i) c[i] += key > t[i];
+                        }
+                        block_sums(c, reinterpret_cast<int *>(red_next()), lane, wave);
+#pragma unroll
+                        for (int i = 0; i < kPsCand; ++i) ok[i] = c[i] < a.top_k;
+                    });
+                    int above = 0, ties = 0;
+                    for (int k = k_lo; k < k_hi; ++k) {
+                        const unsigned key = ps_key(lg[k]);
+                        above += key > vk;
+                        ties += key == vk;
+                    }
+                    int inc = ties;                                      // ties before this thread's codes: a scan over the threads
+#pragma unroll
+                    for (int sh = 1; sh < kWave; sh <<= 1) {
+                        const int o = __shfl_up(inc, sh);
+                        if (lane >= sh) inc += o;
+                    }
+#pragma unroll
+                    for (int sh = kWave / 2; sh >= 1; sh >>= 1) above += __shfl_xor(above, sh);
+                    int *sc = reinterpret_cast<int *>(red_next());
+                    if (lane == kWave - 1) sc[wave] = inc;
+                    if (lane == 0) sc[kPsWaves + wave] = above;
+                    __syncthreads();
+                    rank = inc - ties;
+                    need = a.top_k;
+                    for (int w = 0; w < kPsWaves; ++w) {
+                        if (w < wave) rank += sc[w];
+                        need -= sc[kPsWaves + w];
+                    }
+                }
+                // b. temperature: a correctly rounded divide, exact at temperature 1
+                for (int k = k_lo; k < k_hi; ++k) {
+                    const float v = lg[k];
+                    bool keep = true;
+                    if (tk) {
+                        const unsigned key = ps_key(v);
+                        keep = key > vk || (key == vk && rank++ < need);
+                    }
+                    ev[k] = keep ? expf((v - m) / a.temperature) : 0.0f;
+                }
+                // c. top-p: v0 the smallest key with a mass of less than top_p S above it.  The codes above it stay, as does the
+                // first code at it; the codes below it have at least top_p S before them.  Of several codes at v0, those below
+                // the smallest index J with a mass of at least top_p S before it stay
+                if (a.top_p < 1.0f) {
+                    float tot[1] = {0.0f};
+                    for (int k = k_lo; k < k_hi; ++k) tot[0] = tot[0] + ev[k];
+                    block_sums(tot, reinterpret_cast<float *>(red_next()), lane, wave);
+                    const float P = a.top_p * tot[0];
+                    const unsigned v0 = ps_bisect<32>([&](const unsigned *t, bool *ok) {
+                        float f[kPsCand] = {0.0f, 0.0f, 0.0f};
+                        for (int k = k_lo; k < k_hi; ++k) {
+                            const unsigned key = ps_key(lg[k]);
+                            const float e = ev[k];
+#pragma unroll
+                            for (int i = 0; i < kPsCand; ++i) f[i] = f[i] + (key > t[i] ? e : 0.0f);
+                        }
+                        block_sums(f, reinterpret_cast<float *>(red_next()), lane, wave);
+#pragma unroll
+                        for (int i = 0; i < kPsCand; ++i) ok[i] = f[i] < P;
+                    });
+                    int nt[1] = {0};
+                    for (int k = k_lo; k < k_hi; ++k) nt[0] += ps_key(lg[k]) == v0;
+                    block_sums(nt, reinterpret_cast<int *>(red_next()), lane, wave);
+                    unsigned J = (unsigned)K;
+                    if (nt[0] > 1)
+                        J = ps_bisect<14>([&](const unsigned *t, bool *ok) {          // 2^14 > kPsMaxK
+                            float f[kPsCand] = {0.0f, 0.0f, 0.0f};
+                            for (int k = k_lo; k < k_hi; ++k) {
+                                const unsigned key = ps_key(lg[k]);
+                                const float e = ev[k];
+#pragma unroll
+                                for (int i = 0; i < kPsCand; ++i)
+                                    f[i] = f[i] + (key > v0 || (key == v0 && (unsigned)k < t[i]) ? e : 0.0f);
+                            }
+                            block_sums(f, reinterpret_cast<float *>(red_next()), lane, wave);
+#pragma unroll
+                            for (int i = 0; i < kPsCand; ++i) ok[i] = t[i] >= (unsigned)K || f[i] >= P;
+                        });
+                    for (int k = k_lo; k < k_hi; ++k) {
+                        const unsigned key = ps_key(lg[k]);
+                        if (key < v0 || (key == v0 && (unsigned)k >= J)) ev[k] = 0.0f;
+                    }
+                }
+            }
+            // d. the draw over e_k: the filtered ones in ev, or exp(l_k - m)
+            auto ek = [&](int k) {
+                if constexpr (kFilter) return ev[k];
+                else return expf(lg[k] - m);
+            };
             float r = 0.0f;                                              // this thread's sum of e_k, ascending k
-            for (int k = k_lo; k < k_hi; ++k) r = r + expf(lg[k] - m);
+            for (int k = k_lo; k < k_hi; ++k) r = r + ek(k);
             part[tid] = r;
             __syncthreads();
             if (tid < kWave) {                                           // exclusive prefix of the thread sums, fixed order:
@@ -314,7 +514,7 @@ __global__ __launch_bounds__(kPsThreads) void pixelcnn_sample_kernel(PsArgs a) {
             int first = K, last = -1;
             float run = 0.0f;
             for (int k = k_lo; k < k_hi; ++k) {
-                const float e = expf(lg[k] - m);
+                const float e = ek(k);
                 run = run + e;
                 if (first == K && thr < base + run) first = k;
                 if (e > 0.0f) last = k;
@@ -439,8 +639,17 @@ size_t vqvae_pixelcnn_sample_workspace_bytes(int64_t B, int H, int W, int dim, i
 int vqvae_pixelcnn_sample_f32(const void *packed, size_t packed_bytes, const int64_t *label, const float *uniforms, int64_t B, int H,
                               int W, int K, int dim, int n_layers, int n_classes, int64_t *samples, float *logits, int32_t *status,
                               void *workspace, size_t workspace_bytes, vqvae_stream_t stream) {
+    return vqvae_pixelcnn_sample_ex_f32(packed, packed_bytes, label, uniforms, B, H, W, K, dim, n_layers, n_classes, 1.0f, 0, 1.0f,
+                                        nullptr, samples, logits, status, workspace, workspace_bytes, stream);
+}
+
+int vqvae_pixelcnn_sample_ex_f32(const void *packed, size_t packed_bytes, const int64_t *label, const float *uniforms, int64_t B,
+                                 int H, int W, int K, int dim, int n_layers, int n_classes, float temperature, int top_k,
+                                 float top_p, const int64_t *given, int64_t *samples, float *logits, int32_t *status,
+                                 void *workspace, size_t workspace_bytes, vqvae_stream_t stream) {
     if (!packed || !label || !uniforms || !samples || !status || !workspace) return VQVAE_ERR_NULL;
     if (B < 1 || H < 1 || W < 1 || K < 1 || dim < 1 || n_layers < 1 || n_classes < 1) return VQVAE_ERR_SHAPE;
+    if (!std::isfinite(temperature) || !(temperature > 0.0f) || top_k < 0 || !(top_p > 0.0f && top_p <= 1.0f)) return VQVAE_ERR_SHAPE;
     if (H != W || H > kPsMaxSide || !ps_supported(K, dim, n_layers, n_classes)) return VQVAE_ERR_UNSUPPORTED;
     if (B > 0x7fffffff) return VQVAE_ERR_OVERFLOW;
     if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(workspace)) & 15) return VQVAE_ERR_UNSUPPORTED;
@@ -456,7 +665,21 @@ int vqvae_pixelcnn_sample_f32(const void *packed, size_t packed_bytes, const int
     a.ws = static_cast<float *>(workspace);
     a.ws_per_image = ps_ws_floats(H, dim, n_layers);
     a.S = H; a.dim = dim; a.K = K; a.nl = n_layers; a.ncls = n_classes;
-    hipLaunchKernelGGL(pixelcnn_sample_kernel, dim3((unsigned)B), dim3(kPsThreads), 0, static_cast<hipStream_t>(stream), a);
+    a.temperature = temperature;
+    a.top_k = top_k >= K ? 0 : top_k;
+    a.top_p = top_p;
+    a.given = reinterpret_cast<const long long *>(given);
+    // the plain draw is its own instantiation: no option costs it a register, a byte of LDS or a barrier; the filtered one has a
+    // form for batches that put two workgroups on a CU (see the kernel)
+    const bool filtered = temperature != 1.0f || a.top_k != 0 || top_p < 1.0f || given;
+    const dim3 grid((unsigned)B), block(kPsThreads);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!filtered)
+        hipLaunchKernelGGL((pixelcnn_sample_kernel<false, false>), grid, block, 0, st, a);
+    else if (B <= num_cus())
+        hipLaunchKernelGGL((pixelcnn_sample_kernel<true, false>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((pixelcnn_sample_kernel<true, true>), grid, block, 0, st, a);
     return (int)hipGetLastError();
 }
 

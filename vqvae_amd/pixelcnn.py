@@ -6,7 +6,8 @@ initialisation as the reference, so a PixelCNN checkpoint written by `pixelcnn/g
     GatedPixelCNN(input_dim=256, dim=64, n_layers=15, n_classes=10)
         .forward(x (B,H,W) int64, label (B,) int64) -> logits (B, input_dim, H, W)          (models.py:118-127)
         .generate(label, shape=(8, 8), batch_size=64) -> (B, *shape) int64                   (models.py:129-142)
-        .generate_cached(label, shape, batch_size, *, uniforms, generator, return_logits)   the same draw, one cached kernel
+        .generate_cached(label, shape, batch_size, *, uniforms, generator, return_logits,   the same draw, one cached kernel
+                         temperature, top_k, top_p, given)
 
 Activations are row-major (B,H,W,C); a masked convolution is a stride-1 convolution over its causal tap list
 (round 4: vqvae_conv_taps_forward_f32 -- the conv path's kernels with an explicit tap list, no im2col pass; lists of more than
@@ -28,7 +29,9 @@ No CPU path, no fallback.
 
 Sampling (csrc/pixelcnn_sample.hip).  `generate_cached` keeps each layer's state and computes only what the next pixel needs: per
 row the vertical stacks of every layer, per position the horizontal stacks, the head and one draw -- one kernel, one workgroup per
-image.  `sample_images` decodes its maps with VQVAE.decode_indices.
+image.  Its draw takes a temperature, top-k and top-p, and positions whose code is given are not drawn (a second instantiation of
+the kernel; the plain draw keeps its own).  `sample_images` decodes its maps with VQVAE.decode_indices; `complete_images` keeps the
+top latent rows of encoded images and samples the rest.
 """
 from __future__ import annotations
 
@@ -41,6 +44,9 @@ from . import _cache, _lib, conv_hip
 from ._lib import VqvaeHipError
 from .autograd_conv import CONVT_1x1, _holder, conv_wgrad, relu_backward
 from .conv_hip import CONV_1x1, RELU_OUT, _sp
+
+
+SAMPLE_NONFINITE, SAMPLE_GIVEN_RANGE = 1, 2          # VQVAE_SAMPLE_* status bits of the cached sampler (include/vqvae_hip.h)
 
 
 def weights_init(m):
@@ -542,7 +548,8 @@ class GatedPixelCNN(nn.Module):
         return img
 
     @torch.no_grad()
-    def generate_cached(self, label, shape=(8, 8), batch_size=64, *, uniforms=None, generator=None, return_logits=False):
+    def generate_cached(self, label, shape=(8, 8), batch_size=64, *, uniforms=None, generator=None, return_logits=False,
+                        temperature=1.0, top_k=None, top_p=None, given=None):
         """models.py:129-142 on the cached sampler (csrc/pixelcnn_sample.hip): one kernel that keeps every layer's state and computes
         only what each next pixel needs, instead of one full forward per position.
 
@@ -550,7 +557,23 @@ class GatedPixelCNN(nn.Module):
         drive the draws (drawn with torch.rand(generator=generator) when not given): position (y, x) takes the smallest code k
         whose running sum of exp(l - max l) exceeds u times the total.  Returns the (batch_size, H, W) int64 codes and, with
         return_logits, also the (batch_size, K, H, W) logits each position was drawn from.  Like generate, it leaves the mask-A
-        taps zeroed.  Raises VqvaeHipError for CPU tensors, non-square or unsupported shapes and non-finite logits."""
+        taps zeroed.  Raises VqvaeHipError for CPU tensors, non-square or unsupported shapes and non-finite logits.
+
+        Sampling controls (vqvae_pixelcnn_sample_ex_f32 states the exact rules), applied in this order: top_k keeps the top_k
+        largest logits (ties go to the lower code; 1 is greedy decoding; None, 0 or >= K is off); temperature > 0 divides the
+        logits; top_p in (0, 1] keeps the most probable codes up to a mass of top_p (None or 1 is off).  given, a (batch_size, H, W)
+        int64 tensor on the device, fixes the code wherever it is >= 0 and leaves the negative positions to the draw; with
+        return_logits the logits of given positions are returned too (teacher-forced logits).  ValueError for bad option values
+        and shapes, IndexError for a given code >= K."""
+        temperature = float(temperature)
+        top_k = 0 if top_k is None else int(top_k)
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+        if top_k < 0:
+            raise ValueError(f"top_k must be >= 0 or None, got {top_k}")
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
         p0 = self.embedding.weight
         if not p0.is_cuda or not torch.is_tensor(label) or not label.is_cuda:
             raise VqvaeHipError("generate_cached needs the module and label on a CUDA(HIP) device: there is no CPU path")
@@ -558,6 +581,9 @@ class GatedPixelCNN(nn.Module):
         if H != W:
             raise VqvaeHipError(f"generate_cached samples square maps only, got {H} x {W}")
         B = int(batch_size)
+        if given is not None:
+            if not torch.is_tensor(given) or not given.is_cuda or given.dtype != torch.int64 or tuple(given.shape) != (B, H, W):
+                raise ValueError(f"given must be a CUDA(HIP) int64 tensor of shape ({B}, {H}, {W})")
         dev = p0.device
         label = label.to(device=dev, dtype=torch.int64).contiguous()
         if label.shape != (B,):
@@ -581,11 +607,21 @@ class GatedPixelCNN(nn.Module):
             logits = torch.empty((B, K, H, W), dtype=torch.float32, device=dev) if return_logits else None
             status = torch.empty(B, dtype=torch.int32, device=dev)
             ws = _ws(nws, dev)
-            _lib.check(L.vqvae_pixelcnn_sample_f32(img.data_ptr(), img.numel(), label.data_ptr(), uniforms.data_ptr(), B, H, W, K, dim,
-                                                   n_layers, n_classes, out.data_ptr(),
-                                                   logits.data_ptr() if logits is not None else None, status.data_ptr(),
-                                                   ws.data_ptr(), nws, _sp(out)))
-            bad = int((status != 0).sum())
+            if given is not None:
+                given = given.to(dev).contiguous()
+            # (1, 0, 1, NULL) is vqvae_pixelcnn_sample_f32: the plain kernel
+            _lib.check(L.vqvae_pixelcnn_sample_ex_f32(img.data_ptr(), img.numel(), label.data_ptr(), uniforms.data_ptr(), B, H, W, K,
+                                                      dim, n_layers, n_classes, temperature, top_k, top_p,
+                                                      given.data_ptr() if given is not None else None, out.data_ptr(),
+                                                      logits.data_ptr() if logits is not None else None, status.data_ptr(),
+                                                      ws.data_ptr(), nws, _sp(out)))
+            bad = bad_given = 0
+            if int((status != 0).sum()):
+                st = status.cpu()
+                bad = int(((st & SAMPLE_NONFINITE) != 0).sum())
+                bad_given = int(((st & SAMPLE_GIVEN_RANGE) != 0).sum())
+        if bad_given:
+            raise IndexError(f"cached sampler: a given code >= {K} in {bad_given} of {B} images (status VQVAE_SAMPLE_GIVEN_RANGE)")
         if bad:
             raise VqvaeHipError(f"cached sampler: non-finite logits in {bad} of {B} images (status VQVAE_SAMPLE_NONFINITE)")
         return (out, logits) if return_logits else out
@@ -597,3 +633,25 @@ def sample_images(prior, vqvae, label, shape=(8, 8), batch_size=64, **kw):
     idx = prior.generate_cached(label, shape, batch_size, **kw)
     H, W = idx.shape[1], idx.shape[2]
     return idx, vqvae.decode_indices(idx, batch_size, H, W)
+
+
+@torch.no_grad()
+def complete_images(prior, vqvae, x, label, keep_rows, **kw):
+    """Completes partly known images: x (B, C, 4 H, 4 W) is encoded (VQVAE.encode), latent rows [0, keep_rows) are kept as given codes,
+    the prior samples the remaining rows (GatedPixelCNN.generate_cached(given=...), keyword arguments passed on) and the VQ-VAE
+    decodes the map (VQVAE.decode_indices) -> (indices (B, H, W) int64, x_hat (B, C, 4 H, 4 W))."""
+    B = x.shape[0]
+    enc = vqvae.encode(x)
+    if enc.numel() % B:
+        raise ValueError(f"{enc.numel()} codes do not divide into {B} maps")
+    n = enc.numel() // B
+    H = int(round(n ** 0.5))
+    if H * H != n:
+        raise ValueError(f"complete_images needs square latent maps, got {n} codes per image")
+    keep_rows = int(keep_rows)
+    if not 0 <= keep_rows <= H:
+        raise ValueError(f"keep_rows must be in [0, {H}], got {keep_rows}")
+    given = enc.reshape(B, H, H).to(torch.int64).clone()
+    given[:, keep_rows:] = -1
+    idx = prior.generate_cached(label, (H, H), B, given=given, **kw)
+    return idx, vqvae.decode_indices(idx, B, H, H)
