@@ -722,6 +722,52 @@ VQVAE_API int vqvae_forward_end_f32(const VqvaeWeights *w, int64_t B, int H, int
  * replaces it (a freed and reused pointer would inherit it only until that begin).  Always VQVAE_OK. */
 VQVAE_API int vqvae_forward_abort_f32(void *workspace);
 
+/* ---------------------------------------------------------------- optimizer
+ * torch.optim.Adam(...).step() (main.py:59,80; pixelcnn/gated_pixelcnn.py:78-99) -- Adam, AMSGrad and AdamW -- over every tensor of an
+ * optimizer in ONE elementwise launch, plus the global gradient norm of torch.nn.utils.clip_grad_norm_.  Additive to ABI 9.
+ *
+ * The plan is a blob the caller builds on the host (vqvae_adam_plan_write, pure host code) and copies to the device:
+ *   [header: 8 int64 = magic, n_tensors, n_chunks, chunk elements, offset of the tensor table, of the chunk list, of the scratch, bytes]
+ *   [tensor table: per tensor 64 bytes = param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, step (device pointers), int64 numel,
+ *    int32 group, int32 0]
+ *   [chunk list: per chunk 2 int32 = tensor, index: elements [index * chunk, ...) of that tensor; tensors in table order, a tensor's
+ *    chunks in ascending order; a tensor with numel 0 or a NULL grad has none]
+ *   [scratch: 80 bytes per tensor, written by the step's first kernel on the device]
+ * grad[i] == NULL skips tensor i: its parameter, state and counter are untouched.  max_exp_avg_sq == NULL (the array, or an entry) turns
+ * AMSGrad off for that tensor.  step[i] is ONE fp32 scalar on the device per tensor (torch's capturable / fused state layout), advanced
+ * by the step itself: nothing reads device memory from the host.  All arrays fp32, 4-byte aligned; tensors whose arrays are all
+ * 16-byte aligned run on 16-byte accesses.  Per-element arithmetic and its order: the header comment of vqvae_amd/csrc/optim.hip
+ * (evaluated in fp64 from the fp32 inputs and the device counter, each result rounded to fp32 once).  An element's bits do not depend
+ * on how the data is split into tensors.                                                                                                     */
+#define VQVAE_ADAM_CHUNK        4096    /* elements per workgroup                                                                     */
+#define VQVAE_ADAM_MAX_GROUPS   16      /* parameter groups per step (their hyper-parameters travel as launch arguments)              */
+#define VQVAE_ADAM_ZERO_GRAD    0x1     /* step flag: overwrite the consumed gradients with zeros (the update's bits do not change)   */
+#define VQVAE_ADAM_DECOUPLED_WD 0x1     /* group flag: p *= 1 - lr * wd (AdamW) instead of g += wd * p                                */
+typedef struct VqvaeAdamGroup {
+    double lr, beta1, beta2, eps, weight_decay;     /* lr, eps > 0 and finite; betas in [0, 1); weight_decay >= 0                      */
+    int flags, reserved;
+} VqvaeAdamGroup;
+VQVAE_API int vqvae_adam_chunk_elems(void);
+/* Bytes that hold the plan of these tensors when every one has a gradient (0: n_tensors < 1, NULL or a negative count). */
+VQVAE_API size_t vqvae_adam_plan_bytes(int n_tensors, const int64_t *numel_host);
+/* Fills plan_host from HOST arrays of n_tensors device pointers / sizes / group indices; *n_chunks_out = chunks (= workgroups). */
+VQVAE_API int vqvae_adam_plan_write(int n_tensors, const int64_t *numel_host, void *const *param, void *const *grad,
+                                    void *const *exp_avg, void *const *exp_avg_sq, void *const *max_exp_avg_sq, void *const *step,
+                                    const int *group, int n_groups, void *plan_host, size_t plan_bytes, int64_t *n_chunks_out);
+/* One optimizer step: a one-workgroup kernel (counters, bias corrections) and the update kernel, in that order on `stream`.  The groups'
+ * hyper-parameters are read from groups_host during the call and travel as launch arguments: the caller may change them right after
+ * (an lr scheduler), and a captured step keeps those of capture time.  clip_coef: NULL, or a device scalar every gradient element is
+ * multiplied by (vqvae_grad_norm_f32's output); the gradients in memory stay unscaled -- torch's clip_grad_norm_ scales them in place. */
+VQVAE_API int vqvae_adam_step_f32(void *plan_dev, size_t plan_bytes, int n_tensors, int64_t n_chunks,
+                                  const VqvaeAdamGroup *groups_host, int n_groups, int flags, const float *clip_coef,
+                                  vqvae_stream_t stream);
+/* Global L2 norm of the plan's gradients: fp64 partial sums per chunk, added in a fixed order by one workgroup (no atomics: the same
+ * bits in every run).  total_norm_out = fp32(sqrt(sum)); clip_coef_out (may be NULL) = min(1, max_norm / (total_norm + 1e-6)).        */
+VQVAE_API size_t vqvae_grad_norm_workspace_bytes(int64_t n_chunks);
+VQVAE_API int vqvae_grad_norm_f32(const void *plan_dev, size_t plan_bytes, int n_tensors, int64_t n_chunks, float max_norm,
+                                  float *total_norm_out, float *clip_coef_out, void *workspace, size_t workspace_bytes,
+                                  vqvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 Adam) on the HIP kernels, next to the same module's ops issued through torch autograd (MIOpen / rocBLAS) on the same GPU, the two
 alternated; then the HIP step captured into a hipGraph and replayed (its gradients checked against the eager step's bits).
 
-    python tools/pixelcnn_train_bench.py [--batches 32,1024] [--steps 20] [--repeats 3] [--json OUT]
+    python tools/pixelcnn_train_bench.py [--batches 32,1024] [--steps 20] [--repeats 3] [--json OUT] [--adam torch|hip]
+        --adam hip: the HIP step's optimizer is vqvae_amd.optim.Adam (csrc/optim.hip), eager and captured; torch (the default):
+        torch.optim.Adam, capturable=True inside the graph
     python tools/pixelcnn_train_bench.py --profile-steps N --batches 1024      # HIP steps only, for a rocprofv3 --kernel-trace --stats run
     python tools/pixelcnn_train_bench.py --report-stats run_results.db --batches 1024 --profile-steps N
         -> the per-kernel split per step, and the taps weight-gradient kernel's share of the fp32 MFMA peak (FLOPs from the shapes)
@@ -75,11 +77,18 @@ def timed(f, n):
     return (time.perf_counter() - t0) / n * 1e3
 
 
-def graph_step(m, x, label, steps):
-    """capture forward + loss + backward + Adam (capturable) into one graph; replay; check the replayed gradients against an eager
-    backward at the same parameters"""
+def make_adam(params, which, capturable=False):
+    if which == "hip":
+        from vqvae_amd import optim as hip_optim
+        return hip_optim.Adam(params, lr=3e-4)                 # (captures as it is: its counters live on the device)
+    return torch.optim.Adam(params, lr=3e-4, capturable=True) if capturable else torch.optim.Adam(params, lr=3e-4)
+
+
+def graph_step(m, x, label, steps, adam="torch"):
+    """capture forward + loss + backward + Adam (torch's: capturable) into one graph; replay; check the replayed gradients against
+    an eager backward at the same parameters"""
     from vqvae_amd.pixelcnn import cross_entropy
-    opt = torch.optim.Adam(m.parameters(), lr=3e-4, capturable=True)
+    opt = make_adam(m.parameters(), adam, capturable=True)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -133,6 +142,7 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--report-stats", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--adam", choices=["torch", "hip"], default="torch")
     a = ap.parse_args()
     batches = [int(b) for b in a.batches.split(",")]
 
@@ -146,7 +156,7 @@ def main():
     base = GatedPixelCNN(K, DIM, NL, NCLS)
     if a.profile_steps:
         m = copy.deepcopy(base).to(dev).train()
-        opt = torch.optim.Adam(m.parameters(), lr=3e-4)
+        opt = make_adam(m.parameters(), a.adam)
         x = torch.randint(0, K, (batches[0], HW, HW), device=dev)
         label = torch.randint(0, NCLS, (batches[0],), device=dev)
         for _ in range(a.profile_steps):
@@ -161,7 +171,7 @@ def main():
         x = torch.randint(0, K, (B, HW, HW), generator=g).to(dev)
         label = torch.randint(0, NCLS, (B,), generator=g).to(dev)
         mh, mt = copy.deepcopy(base).to(dev).train(), copy.deepcopy(base).to(dev).train()
-        oh, ot = torch.optim.Adam(mh.parameters(), lr=3e-4), torch.optim.Adam(mt.parameters(), lr=3e-4)
+        oh, ot = make_adam(mh.parameters(), a.adam), torch.optim.Adam(mt.parameters(), lr=3e-4)
         for _ in range(a.warmup):
             hip_step(mh, oh, x, label)
             torch_step(mt, ot, x, label)
@@ -169,11 +179,11 @@ def main():
         for _ in range(a.repeats):
             th.append(timed(lambda: hip_step(mh, oh, x, label), a.steps))
             tt.append(timed(lambda: torch_step(mt, ot, x, label), a.steps))
-        tg, same, _ = graph_step(copy.deepcopy(base).to(dev).train(), x, label, a.steps)
-        r = {"B": B, "hip_ms": statistics.median(th), "torch_ms": statistics.median(tt), "hip_graph_ms": tg,
+        tg, same, _ = graph_step(copy.deepcopy(base).to(dev).train(), x, label, a.steps, a.adam)
+        r = {"B": B, "adam": a.adam, "hip_ms": statistics.median(th), "torch_ms": statistics.median(tt), "hip_graph_ms": tg,
              "graph_grads_equal_eager": same, "hip_ms_all": th, "torch_ms_all": tt}
         out["results"].append(r)
-        print(f"train step B={B:5d}: HIP {r['hip_ms']:8.2f} ms   torch autograd {r['torch_ms']:8.2f} ms   "
+        print(f"train step B={B:5d} adam={a.adam}: HIP {r['hip_ms']:8.2f} ms   torch autograd {r['torch_ms']:8.2f} ms   "
               f"HIP hipGraph {tg:8.2f} ms   (graph grads == eager: {same})", flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)

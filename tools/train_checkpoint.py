@@ -2,10 +2,12 @@
 """Train a real checkpoint with the HIP training path  --  the loop of main.py:67-98 (Adam amsgrad lr 3e-4, model.train(),
 recon / x_train_var + embedding loss, a random batch per update) on structured synthetic 32x32x3 images (tests/synthdata.py;
 no dataset can be fetched here).  Every forward and backward runs on libvqvae_hip.so (vqvae_amd/autograd_conv.py,
-training.VQStraightThrough, training.step_losses); the optimizer is torch's, as in the reference.
+training.VQStraightThrough, training.step_losses); the optimizer is torch's, as in the reference, unless --hip_adam asks for
+vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run no longer depends on which Adam torch picks).
 
     python tools/train_checkpoint.py [--n_updates 5000] [--batch_size 32] [--out gpurun_out/trained]
                                      [--ema_decay 0.99 [--restart_threshold 1]]     (the EMA codebook; off by default)
+                                     [--hip_adam]                                   (off by default: the committed checkpoints are torch's)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -48,6 +50,7 @@ def main():
     # opt-in EMA codebook (VectorQuantizerEMA); absent from the namespace unless given, so a default run writes what it always did
     p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS)
     p.add_argument("--restart_threshold", type=float, default=argparse.SUPPRESS)
+    p.add_argument("--hip_adam", action="store_true", default=argparse.SUPPRESS)        # (absent unless given, like the EMA options)
     args = p.parse_args()
     ema_kw = {}
     if hasattr(args, "ema_decay"):
@@ -77,7 +80,11 @@ def main():
     torch.manual_seed(0)
     model = VQVAE(args.n_hiddens, args.n_residual_hiddens, args.n_residual_layers, args.n_embeddings, args.embedding_dim,
                   args.beta, **ema_kw).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)       # main.py:59
+    if getattr(args, "hip_adam", False):
+        from vqvae_amd import optim as hip_optim
+        opt = hip_optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)   # main.py:59
     model.train()
     results = {"n_updates": 0, "recon_errors": [], "loss_vals": [], "perplexities": []}
     g = torch.Generator().manual_seed(1)

@@ -29,6 +29,11 @@ _PACKED_FIELDS = ["enc0", "enc0_b", "enc2", "enc2_b", "enc4", "enc4_b", "enc_res
                   "dec0", "dec0_b", "dec_res_w1", "dec_res_w2", "dec2", "dec2_b", "dec4", "dec4_b"]
 
 
+class VqvaeAdamGroup(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("flags", _i32), ("reserved", _i32)]
+
+
 class VqvaeRawWeights(C.Structure):
     _fields_ = [(n, _vp) for n in _RAW_FIELDS]
 
@@ -135,6 +140,12 @@ SIGNATURES = {
     "vqvae_pixelcnn_sample_f32": (_i32, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vqvae_pixelcnn_sample_ex_f32": (_i32, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _vp,
                                             _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_adam_chunk_elems": (_i32, []),
+    "vqvae_adam_plan_bytes": (_sz, [_i32, C.POINTER(_i64)]),
+    "vqvae_adam_plan_write": (_i32, [_i32, C.POINTER(_i64)] + [C.POINTER(_vp)] * 6 + [C.POINTER(_i32), _i32, _vp, _sz, C.POINTER(_i64)]),
+    "vqvae_adam_step_f32": (_i32, [_vp, _sz, _i32, _i64, C.POINTER(VqvaeAdamGroup), _i32, _i32, _vp, _vp]),
+    "vqvae_grad_norm_workspace_bytes": (_sz, [_i64]),
+    "vqvae_grad_norm_f32": (_i32, [_vp, _sz, _i32, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
