@@ -330,6 +330,29 @@ VQVAE_API int vqvae_vq_ema_update_f32(const float *z_e, const int64_t *idx, int6
                                       float *ema_cluster_size, float *ema_w, float *codebook,
                                       void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* k-means initialisation of the codebook (csrc/vq_kmeans.hip; its header is the numeric contract): a data-dependent start instead of
+ * uniform(-1/K, 1/K) (models/quantizer.py:26-27).  Both calls take z_e in the layout VQVAE_VQ_ROWMAJOR selects (no other flag); rows
+ * are the N = B H W rows in the quantizer's order.  One workspace size serves both.  No RNG of their own: the caller supplies K fp32
+ * uniforms in [0, 1).  No host sync, no atomics, no workgroup waits on another: bit-reproducible, the same bits in either layout.
+ * Envelope: 1 <= D <= 256, 1 <= K <= 16384, 1 <= N <= INT32_MAX (VQVAE_ERR_UNSUPPORTED outside it; the sizing call then returns 0).
+ *
+ * vqvae_vq_kmeans_seed_f32 -- k-means++ (Arthur & Vassilvitskii 2007): rows[0] = min(floor(u_0 N), N - 1); round k >= 1 keeps
+ *   w_n = min over the chosen centres of the fp64 squared distance (channels added in order) and picks the first row whose
+ *   inclusive prefix sum of w exceeds u_k T (T the total; blocks of 256 rows, groups of blocks, sequential scans: the order is
+ *   written in the source's header) with w_n > 0, so a copy of a chosen centre is never picked while T > 0; T = 0 (fewer distinct
+ *   rows than centres): rows[k] = min(floor(u_k N), N - 1).  codebook (K, D) out: codebook[k] = row rows[k] bit for bit;
+ *   rows (K) int64 out.  1 + 2 (K - 1) launches.
+ * vqvae_vq_kmeans_update_f32 -- one Lloyd mean update from the indices vqvae_vq_forward_f32 assigned: counts (K) int32 out = c_k;
+ *   codebook (K, D) in/out: c_k > 0: e_k = s_k / c_k (the EMA update's sorted fp64 sums, one fp64 division, one rounding); c_k = 0:
+ *   unchanged, or with uniforms (may be NULL) row min(floor(u_k N), N - 1) of z_e.  codebook must not alias z_e.              */
+VQVAE_API size_t vqvae_vq_kmeans_workspace_bytes(int64_t N, int K, int D);
+VQVAE_API int vqvae_vq_kmeans_seed_f32(const float *z_e, int64_t B, int D, int H, int W, int K, const float *uniforms, int flags,
+                                       float *codebook, int64_t *rows, void *workspace, size_t workspace_bytes,
+                                       vqvae_stream_t stream);
+VQVAE_API int vqvae_vq_kmeans_update_f32(const float *z_e, const int64_t *idx, int64_t B, int D, int H, int W, int K,
+                                         const float *uniforms, int flags, float *codebook, int32_t *counts,
+                                         void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* recon_loss = mean((x_hat - x)^2) / x_train_var; loss = recon_loss + embedding_loss (main.py:75-76).
  * out3 = {recon_loss, loss, perplexity}: the three values main.py:81-83 copies to the host one by one,
  * packed so that a step needs one D2H copy.  embedding_loss / perplexity are device scalars (NULL = 0);

@@ -8,6 +8,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
     python tools/train_checkpoint.py [--n_updates 5000] [--batch_size 32] [--out gpurun_out/trained]
                                      [--ema_decay 0.99 [--restart_threshold 1]]     (the EMA codebook; off by default)
                                      [--hip_adam]                                   (off by default: the committed checkpoints are torch's)
+                                     [--kmeans_init [BATCHES]]                      (off by default: k-means start of the codebook)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -51,6 +52,9 @@ def main():
     p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS)
     p.add_argument("--restart_threshold", type=float, default=argparse.SUPPRESS)
     p.add_argument("--hip_adam", action="store_true", default=argparse.SUPPRESS)        # (absent unless given, like the EMA options)
+    # opt-in k-means start of the codebook (VQVAE.init_codebook_) on the first BATCHES batches, before update 0
+    p.add_argument("--kmeans_init", type=int, nargs="?", const=1, default=argparse.SUPPRESS, metavar="BATCHES")
+    p.add_argument("--kmeans_iters", type=int, default=argparse.SUPPRESS)
     args = p.parse_args()
     ema_kw = {}
     if hasattr(args, "ema_decay"):
@@ -87,6 +91,14 @@ def main():
         opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)   # main.py:59
     model.train()
     results = {"n_updates": 0, "recon_errors": [], "loss_vals": [], "perplexities": []}
+    if getattr(args, "kmeans_init", 0) > 0:
+        # the batches the loop below is about to draw (the same generator seed; the loop's own generator starts afresh)
+        gi = torch.Generator().manual_seed(1)
+        sel = torch.cat([torch.randint(0, args.n_train, (args.batch_size,), generator=gi) for _ in range(args.kmeans_init)])
+        _, counts = model.init_codebook_(data[sel.to(dev)].contiguous(), iters=getattr(args, "kmeans_iters", 10),
+                                         generator=torch.Generator(device=dev).manual_seed(2))
+        say(f"# k-means init on {sel.numel()} images ({args.kmeans_init} batches): codes with rows {int((counts > 0).sum())} / "
+            f"{args.n_embeddings}, largest cluster {int(counts.max())} rows")
     g = torch.Generator().manual_seed(1)
     stats_dev = []
     t0 = time.time()

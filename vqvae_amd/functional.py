@@ -169,3 +169,101 @@ def vq_ema_update(z_e: torch.Tensor, idx: torch.Tensor, ema_cluster_size: torch.
             VQ_ROWMAJOR if rowmajor else 0, ema_cluster_size.data_ptr(), ema_w.data_ptr(), codebook.data_ptr(),
             workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
     return codebook
+
+
+def vq_kmeans_workspace(N: int, K: int, D: int, device) -> torch.Tensor:
+    """one workspace for vq_kmeans_seed and vq_kmeans_update at these sizes"""
+    n = _lib.load().vqvae_vq_kmeans_workspace_bytes(N, K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"k-means initialisation: N={N}, K={K}, D={D} not supported (1 <= K <= 16384, 1 <= D <= 256, "
+                                 "1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _kmeans_rows(z_e, rowmajor):
+    _check_dev("z_e", z_e)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    return z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+
+
+def vq_kmeans_seed(z_e: torch.Tensor, K: int, uniforms: torch.Tensor, *, rowmajor: bool = False,
+                   workspace: torch.Tensor | None = None):
+    """k-means++ seeding (vqvae_vq_kmeans_seed_f32) of a K-code codebook on the rows of z_e, driven by K fp32 uniforms in [0, 1):
+    -> (codebook (K, D) whose code k is row rows[k] of z_e bit for bit, rows (K,) int64).  z_e: (B,D,H,W), or (B,H,W,D) when
+    rowmajor.  The numeric contract is the header of csrc/vq_kmeans.hip."""
+    B, H, W, D = _kmeans_rows(z_e, rowmajor)
+    _check_dev("uniforms", uniforms)
+    uniforms = uniforms.contiguous()
+    if uniforms.numel() != K:
+        raise ValueError("uniforms must hold K values")
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_kmeans_workspace(B * H * W, K, D, dev)
+        codebook = torch.empty((K, D), dtype=torch.float32, device=dev)
+        rows = torch.empty((K,), dtype=torch.int64, device=dev)
+        _lib.check(_lib.load().vqvae_vq_kmeans_seed_f32(
+            z_e.data_ptr(), B, D, H, W, K, uniforms.data_ptr(), VQ_ROWMAJOR if rowmajor else 0, codebook.data_ptr(),
+            rows.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
+    return codebook, rows
+
+
+def vq_kmeans_update(z_e: torch.Tensor, idx: torch.Tensor, codebook: torch.Tensor, *, uniforms: torch.Tensor | None = None,
+                     rowmajor: bool = False, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """One Lloyd mean update (vqvae_vq_kmeans_update_f32) from the rows z_e and the indices the quantizer assigned them: every code
+    with rows becomes their mean, written into codebook (K, D) in place through its data pointer (no autograd version bump: the
+    caller owns that); a code without rows keeps its bits, or with uniforms (K fp32 in [0, 1)) takes row floor(u_k N) of z_e.
+    -> counts (K,) int32.  z_e: (B,D,H,W), or (B,H,W,D) when rowmajor."""
+    B, H, W, D = _kmeans_rows(z_e, rowmajor)
+    _check_dev("idx", idx, torch.int64)
+    _check_dev("codebook", codebook)
+    if not codebook.is_contiguous():
+        raise ValueError("codebook must be contiguous (it is written in place)")
+    K = codebook.shape[0]
+    if codebook.shape != (K, D) or idx.numel() != B * H * W:
+        raise ValueError("shape mismatch between z_e, idx and codebook")
+    if uniforms is not None:
+        _check_dev("uniforms", uniforms)
+        uniforms = uniforms.contiguous()
+        if uniforms.numel() != K:
+            raise ValueError("uniforms must hold K values")
+    z_e = z_e.contiguous()
+    idx = idx.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_kmeans_workspace(B * H * W, K, D, dev)
+        counts = torch.empty((K,), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().vqvae_vq_kmeans_update_f32(
+            z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, uniforms.data_ptr() if uniforms is not None else None,
+            VQ_ROWMAJOR if rowmajor else 0, codebook.data_ptr(), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(z_e)))
+    return counts
+
+
+def vq_kmeans(z_e: torch.Tensor, K: int, iters: int = 10, *, generator: torch.Generator | None = None, reseed_empty: bool = True,
+              rowmajor: bool = False, trace: list | None = None):
+    """k-means on the rows of z_e: k-means++ seeding, then `iters` rounds of assignment by the quantizer (vq_forward, indices only)
+    and the mean update.  -> (codebook (K, D), counts (K,) int32 of the last assignment; of no assignment, all zero, when iters = 0).
+    Uniforms come from torch.rand on the device (`generator`, or the default CUDA generator): K for the seeding and, with
+    reseed_empty, K per round for codes that lost every row.  Nothing synchronises with the host.  trace: a list that receives,
+    per round, (the codebook the round assigned against, its indices) -- for tests."""
+    B, H, W, D = _kmeans_rows(z_e, rowmajor)
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        ws = vq_kmeans_workspace(B * H * W, K, D, dev)
+        codebook, _ = vq_kmeans_seed(z_e, K, torch.rand(K, device=dev, generator=generator), rowmajor=rowmajor, workspace=ws)
+        counts = torch.zeros((K,), dtype=torch.int32, device=dev)
+        vws = vq_workspace(K, D, dev) if iters else None
+        for _ in range(iters):
+            _, _, _, idx, _ = vq_forward(z_e, codebook, 0.0, rowmajor=rowmajor, workspace=vws, prepared=False, want_zq=False)
+            if trace is not None:
+                trace.append((codebook.clone(), idx))
+            u = torch.rand(K, device=dev, generator=generator) if reseed_empty else None
+            counts = vq_kmeans_update(z_e, idx, codebook, uniforms=u, rowmajor=rowmajor, workspace=ws)
+    return codebook, counts

@@ -179,6 +179,17 @@ class VectorQuantizer(nn.Module):
         self.invalidate()
         return super()._apply(fn, *args, **kwargs)
 
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """Opt-in data-dependent start: the codebook becomes k-means (k-means++ seeding and `iters` Lloyd rounds on the HIP kernels,
+        functional.vq_kmeans) of the rows of z -- encoder outputs (B,D,H,W), or (B,H,W,D) when rowmajor -- instead of
+        uniform(-1/K, 1/K).  Written into `embedding.weight` by an in-place op: its `_version` moves, so the prepared and packed
+        codebook images re-key.  -> (codebook, counts of the last assignment)."""
+        _need_hip_f32(z, "init_codebook_")
+        codebook, counts = F_hip.vq_kmeans(z.detach(), self.n_e, iters, generator=generator, rowmajor=rowmajor)
+        self.embedding.weight.copy_(codebook)
+        return codebook, counts
+
     def forward(self, z):
         loss, z_q, perplexity, idx, _ = self.quantize(z)
         min_encodings = LazyOneHot(idx, self.n_e) if self.LAZY_MIN_ENCODINGS else F_hip.vq_onehot(idx, self.n_e)   # quantizer.py:55-57
@@ -228,6 +239,16 @@ class VectorQuantizerEMA(VectorQuantizer):
                             threshold=self.restart_threshold, uniforms=uniforms, rowmajor=rowmajor, workspace=ws)
         with torch.no_grad():
             w.copy_(new)
+
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """VectorQuantizer.init_codebook_, and the EMA state continues from the clusters: ema_cluster_size = counts,
+        ema_w = counts[:, None] * codebook."""
+        codebook, counts = super().init_codebook_(z, iters, generator, rowmajor=rowmajor)
+        c = counts.to(torch.float32)
+        self.ema_cluster_size.copy_(c)
+        self.ema_w.copy_(c[:, None] * codebook)
+        return codebook, counts
 
     def quantize(self, z, *, rowmajor=False, want_zq=True):
         """-> (beta * mse, z_q, perplexity, min_encoding_indices, hist) against the codebook as it was on entry; then, in training
@@ -602,6 +623,17 @@ class VQVAE(nn.Module):
             print('recon data shape:', x_hat.shape)
             assert False
         return embedding_loss, x_hat, perplexity
+
+    @torch.no_grad()
+    def init_codebook_(self, x, iters=10, generator=None):
+        """Opt-in: start the codebook on the data -- z_e of the images x from the encoder and pre_quantization_conv (HIP path, no
+        grad), then the quantizer's init_codebook_ (k-means++ seeding and `iters` Lloyd rounds).  Call it before the first update."""
+        from . import conv as C_hip
+        _need_hip_f32(x, "VQVAE.init_codebook_")
+        if C_hip.get_conv_backend() != "hip":
+            raise VqvaeHipError("VQVAE.init_codebook_ runs on the HIP conv backend: there is no fallback")
+        z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)        # row-major (B,H,W,D)
+        return self.vector_quantization.init_codebook_(z_e, iters, generator, rowmajor=True)
 
     # ---- "next" rows of SURVEY.md 8f-1: the index wire format -------------------
     def _c_workspace(self, L, cw, B, H, W, dev):
