@@ -353,6 +353,44 @@ VQVAE_API int vqvae_vq_kmeans_update_f32(const float *z_e, const int64_t *idx, i
                                          const float *uniforms, int flags, float *codebook, int32_t *counts,
                                          void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* Residual vector quantization (csrc/vq_residual.hip; its header is the numeric contract): Q codebooks E_0 .. E_{Q-1}, each (K, D),
+ * quantize the same latent position, stage q what stage q - 1 left over (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ):
+ *     r_0 = z;   idx_q = vqvae_vq_forward_f32's indices of r_q against E_q;   r_{q+1} = r_q - E_q[idx_q]
+ *     S = ((e_0 + e_1) + ...) in stage order;   z_q = z + (S - z);   loss = ((loss_0 + loss_1) + ...) on the device
+ * 1 <= Q <= 16; the quantizer's envelope (K <= 16384, D <= 256) and N <= INT32_MAX: VQVAE_ERR_UNSUPPORTED outside it, and the sizing
+ * calls then return 0.  `codebooks` is a HOST array of Q device pointers (read during the call only); with
+ * VQVAE_VQ_RESIDUAL_SHARED every stage uses codebooks[0] and only that entry is read.  No host sync, no allocation, no
+ * floating-point atomics; every launch on `stream` in one linear chain (capturable); the same bits in every run and either layout.
+ *
+ * forward:  flags = the quantizer's own (VQVAE_VQ_ROWMAJOR, VQVAE_VQ_CODEBOOK_PREPARED, the kernel-selection flags), passed to every
+ *   stage, | VQVAE_VQ_RESIDUAL_SHARED.  The workspace holds one prepared codebook image per distinct codebook and one residual map,
+ *   so VQVAE_VQ_CODEBOOK_PREPARED means: every stage's image is there from a previous call with the same codebooks and workspace.
+ *     idx (Q, N) int64 stage-major;  hist (Q, K) int32;  loss_stage, perplexity_stage (Q) fp32: each stage's quantizer outputs;
+ *     loss 1 fp32;  z_q like z_e, may be NULL;  residual_out = r_Q like z_e, may be NULL.
+ *   Launches: Q quantizer calls (index-only), Q - 1 advance kernels, one finish kernel.  Q = 1: the bits of vqvae_vq_forward_f32.
+ * decode:   indices (Q, N) -> z_q = S, (B,D,H,W) or rows with VQVAE_VQ_ROWMAJOR.  An index outside [0, K) never reads a codebook:
+ *   the D elements of its row become NaN (the rule of vqvae_vq_decode_indices_f32).
+ * backward: the gradients autograd derives when every stage is the reference quantizer and r_{q+1} = r_q - e_q.detach():
+ *     grad_z      = grad_zq + g * 2 / (N D) * sum_q (r_q - e_q)
+ *     grad_E_q[k] = g * 2 beta / (N D) * sum_{i: idx_q,i = k} (e_k - r_q,i)        shared: the stage results added in stage order
+ *   g = *grad_loss (NULL = 1), grad_zq may be NULL (= 0).  grad_z may be NULL; grad_codebooks (a HOST array of Q device pointers, one
+ *   when shared) may be NULL, and the workspace is needed only with it.  The codebook gradients come from the sorted segmented sum of
+ *   vqvae_vq_backward_f32 on each stage's re-materialised residual: fp64, fixed order.  flags: VQVAE_VQ_ROWMAJOR,
+ *   VQVAE_VQ_RESIDUAL_SHARED.                                                                                                   */
+#define VQVAE_VQ_RESIDUAL_SHARED 0x10000 /* the residual entries: one codebook for every stage */
+VQVAE_API size_t vqvae_vq_residual_workspace_bytes(int64_t N, int K, int D, int Q, int shared);
+VQVAE_API int vqvae_vq_residual_forward_f32(const float *z_e, const float *const *codebooks, int64_t B, int D, int H, int W, int K,
+                                            int Q, float beta, int flags, float *z_q, int64_t *idx, int32_t *hist,
+                                            float *loss_stage, float *perplexity_stage, float *loss, float *residual_out,
+                                            void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_vq_residual_decode_f32(const int64_t *idx, const float *const *codebooks, int64_t B, int D, int H, int W, int K,
+                                           int Q, int flags, float *z_q, vqvae_stream_t stream);
+VQVAE_API size_t vqvae_vq_residual_backward_workspace_bytes(int64_t N, int K, int D, int Q);
+VQVAE_API int vqvae_vq_residual_backward_f32(const float *z_e, const float *const *codebooks, const int64_t *idx,
+                                             const float *grad_zq, const float *grad_loss, int64_t B, int D, int H, int W, int K,
+                                             int Q, float beta, int flags, float *grad_z, float *const *grad_codebooks,
+                                             void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* recon_loss = mean((x_hat - x)^2) / x_train_var; loss = recon_loss + embedding_loss (main.py:75-76).
  * out3 = {recon_loss, loss, perplexity}: the three values main.py:81-83 copies to the host one by one,
  * packed so that a step needs one D2H copy.  embedding_loss / perplexity are device scalars (NULL = 0);

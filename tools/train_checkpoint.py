@@ -9,6 +9,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--ema_decay 0.99 [--restart_threshold 1]]     (the EMA codebook; off by default)
                                      [--hip_adam]                                   (off by default: the committed checkpoints are torch's)
                                      [--kmeans_init [BATCHES]]                      (off by default: k-means start of the codebook)
+                                     [--n_quantizers Q [--shared_codebook]]         (off by default: residual quantization, Q stages)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -55,8 +56,15 @@ def main():
     # opt-in k-means start of the codebook (VQVAE.init_codebook_) on the first BATCHES batches, before update 0
     p.add_argument("--kmeans_init", type=int, nargs="?", const=1, default=argparse.SUPPRESS, metavar="BATCHES")
     p.add_argument("--kmeans_iters", type=int, default=argparse.SUPPRESS)
+    # opt-in residual quantization (ResidualVectorQuantizer); absent unless given, like the EMA options
+    p.add_argument("--n_quantizers", type=int, default=argparse.SUPPRESS)
+    p.add_argument("--shared_codebook", action="store_true", default=argparse.SUPPRESS)
     args = p.parse_args()
     ema_kw = {}
+    if hasattr(args, "n_quantizers"):
+        ema_kw["n_quantizers"] = args.n_quantizers
+    if hasattr(args, "shared_codebook"):
+        ema_kw["shared_codebook"] = True
     if hasattr(args, "ema_decay"):
         ema_kw["ema_decay"] = args.ema_decay
     if hasattr(args, "restart_threshold"):
@@ -95,8 +103,9 @@ def main():
         # the batches the loop below is about to draw (the same generator seed; the loop's own generator starts afresh)
         gi = torch.Generator().manual_seed(1)
         sel = torch.cat([torch.randint(0, args.n_train, (args.batch_size,), generator=gi) for _ in range(args.kmeans_init)])
-        _, counts = model.init_codebook_(data[sel.to(dev)].contiguous(), iters=getattr(args, "kmeans_iters", 10),
-                                         generator=torch.Generator(device=dev).manual_seed(2))
+        init = model.init_codebook_(data[sel.to(dev)].contiguous(), iters=getattr(args, "kmeans_iters", 10),
+                                    generator=torch.Generator(device=dev).manual_seed(2))
+        counts = init[0][1] if isinstance(init, list) else init[1]              # (residual stages: stage 0's counts)
         say(f"# k-means init on {sel.numel()} images ({args.kmeans_init} batches): codes with rows {int((counts > 0).sum())} / "
             f"{args.n_embeddings}, largest cluster {int(counts.max())} rows")
     g = torch.Generator().manual_seed(1)

@@ -33,16 +33,7 @@ __global__ __launch_bounds__(256) void vqb_codebook_grad_kernel(const float *__r
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)K * D) return;
     const int k = (int)(e / D), c = (int)(e - (long long)k * D);
-    // four interleaved running sums (a code that owns many rows has many units: their loads are in flight together
-    // instead of one dependent add per load), combined in a fixed order
-    double z4[4] = {0.0, 0.0, 0.0, 0.0};
-    int u = unit_start[k];
-    const int u1 = unit_start[k + 1];
-    for (; u + 4 <= u1; u += 4)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) z4[j] += partial[(size_t)(u + j) * D + c];
-    for (int j = 0; u < u1; ++u, ++j) z4[j] += partial[(size_t)u * D + c];
-    const double zsum = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+    const double zsum = segsum_key_sum(unit_start, partial, k, c, D);
     const double cnt = (double)(offsets[k + 1] - offsets[k]);
     const double gl = g_loss ? (double)g_loss[0] : 1.0;
     grad_cb[e] = (float)(gl * scale * (cnt * (double)cb[e] - zsum));
@@ -193,14 +184,7 @@ __global__ __launch_bounds__(256) void vqe_update_kernel(const float *__restrict
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)K * D) return;
     const int k = (int)(e / D), c = (int)(e - (long long)k * D);
-    double z4[4] = {0.0, 0.0, 0.0, 0.0};
-    int u = unit_start[k];
-    const int u1 = unit_start[k + 1];
-    for (; u + 4 <= u1; u += 4)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) z4[j] += partial[(size_t)(u + j) * D + c];
-    for (int j = 0; u < u1; ++u, ++j) z4[j] += partial[(size_t)u * D + c];
-    const double s = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+    const double s = segsum_key_sum(unit_start, partial, k, c, D);
     const double m = decay * (double)ema_w[e] + (1.0 - decay) * s;
     const double Nk = nk[k];
     double ek;

@@ -73,6 +73,22 @@ inline ReducePlan segsum_reduce_plan(const SegsumPlan &s, long long n) {     // 
 hipError_t launch_segsum(const SegsumPlan &p, const float *src, const long long *idx, long long n, int nkeys, int C, int HW,
                          int rowmajor, char *ws, hipStream_t st);
 
+// A key's sum of channel c from its units' partials, in the ONE order every caller combines them (part of their numeric contracts:
+// vqvae_vq_backward_f32, vqvae_vq_ema_update_f32, vqvae_vq_kmeans_update_f32, vqvae_vq_residual_backward_f32): four interleaved
+// running sums over the units (a key that owns many rows has many units: their loads are in flight together instead of one
+// dependent add per load), then (s0 + s1) + (s2 + s3).
+__device__ __forceinline__ double segsum_key_sum(const int *__restrict__ unit_start, const double *__restrict__ partial, int k, int c,
+                                                 int C) {
+    double z4[4] = {0.0, 0.0, 0.0, 0.0};
+    int u = unit_start[k];
+    const int u1 = unit_start[k + 1];
+    for (; u + 4 <= u1; u += 4)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z4[j] += partial[(size_t)(u + j) * C + c];
+    for (int j = 0; u < u1; ++u, ++j) z4[j] += partial[(size_t)u * C + c];
+    return (z4[0] + z4[1]) + (z4[2] + z4[3]);
+}
+
 // ---- the second stage of the split reductions -------------------------------------------------------------------------------------
 // dw[ca][cb][tap] = sum_split partial[split][tap][ca][cb], eight interleaved sums combined in a fixed order
 void launch_split_reduce(const float *partial, int nsplit, int ntap, int CA, int CB, float *dw, hipStream_t st);

@@ -233,14 +233,7 @@ __global__ __launch_bounds__(256) void kmu_update_kernel(const float *__restrict
     const int cnt = offsets[k + 1] - offsets[k];
     if (c == 0) counts[k] = cnt;
     if (cnt > 0) {
-        double z4[4] = {0.0, 0.0, 0.0, 0.0};
-        int u = unit_start[k];
-        const int u1 = unit_start[k + 1];
-        for (; u + 4 <= u1; u += 4)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z4[j] += partial[(size_t)(u + j) * D + c];
-        for (int j = 0; u < u1; ++u, ++j) z4[j] += partial[(size_t)u * D + c];
-        const double s = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+        const double s = segsum_key_sum(unit_start, partial, k, c, D);
         codebook[e] = (float)(s / (double)cnt);
     } else if (uniforms) {
         codebook[e] = km_at(z, km_uniform_row(uniforms[k], N), c, D, HW, layout);

@@ -267,3 +267,111 @@ def vq_kmeans(z_e: torch.Tensor, K: int, iters: int = 10, *, generator: torch.Ge
             u = torch.rand(K, device=dev, generator=generator) if reseed_empty else None
             counts = vq_kmeans_update(z_e, idx, codebook, uniforms=u, rowmajor=rowmajor, workspace=ws)
     return codebook, counts
+
+
+# ---- residual vector quantization (csrc/vq_residual.hip) -------------------------------------------------------------------------
+VQ_RESIDUAL_SHARED = 0x10000
+
+
+def _ptr_array(tensors):
+    """the HOST array of device pointers the residual entries take (read during the call only)"""
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _residual_books(codebooks, shared):
+    """-> (contiguous (K, D) codebooks, one per distinct codebook; stage count, None when only the caller knows it)"""
+    if isinstance(codebooks, torch.Tensor):
+        codebooks = [codebooks] if codebooks.dim() == 2 else list(codebooks.unbind(0))
+    books = list(codebooks)
+    if not books:
+        raise ValueError("at least one codebook")
+    for i, c in enumerate(books):
+        _check_dev(f"codebooks[{i}]", c)
+        if c.dim() != 2 or c.shape != books[0].shape:
+            raise ValueError("every codebook must be (K, D) with the same K and D")
+    n = len(books)
+    if shared:                                    # one codebook and n_q, or the same codebook listed once per stage
+        books = books[:1]
+    return [c.contiguous() for c in books], (None if shared and n == 1 else n)
+
+
+def vq_residual_workspace(N: int, K: int, D: int, Q: int, device, *, shared: bool = False) -> torch.Tensor:
+    """workspace of vq_residual_forward: one prepared codebook image per distinct codebook and one residual map"""
+    n = _lib.load().vqvae_vq_residual_workspace_bytes(N, K, D, Q, 1 if shared else 0)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"residual quantizer: N={N}, K={K}, D={D}, Q={Q} not supported (1 <= Q <= 16, K <= 16384, D <= 256, "
+                                 "N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_residual_forward(z_e: torch.Tensor, codebooks, beta: float, *, rowmajor: bool = False, shared: bool = False,
+                        n_q: int | None = None, want_zq: bool = True, want_residual: bool = False,
+                        workspace: torch.Tensor | None = None, prepared: bool = False):
+    """Residual quantization (vqvae_vq_residual_forward_f32): stage q quantizes, with the reference quantizer, what stage q - 1
+    left over.  codebooks: a sequence of Q (K, D) tensors; with shared=True every stage uses the first (pass it Q times, or once
+    with n_q=Q).
+    z_e: (B,D,H,W), or (B,H,W,D) when rowmajor.
+    -> (loss 0-dim, z_q like z_e or None, perplexity (Q,), idx (Q, N) int64, hist (Q, K) int32, loss_stage (Q,)), and with
+    want_residual a seventh value, r_Q like z_e.  prepared: `workspace` holds every stage's codebook image from a previous call
+    with the same codebooks.  The numeric contract is the header of csrc/vq_residual.hip."""
+    _check_dev("z_e", z_e)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    books, Q = _residual_books(codebooks, shared)
+    if Q is None:
+        Q = 1 if n_q is None else int(n_q)
+    elif n_q is not None and n_q != Q:
+        raise ValueError("n_q differs from the number of codebooks")
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K, Dc = books[0].shape
+    if Dc != D:
+        raise ValueError(f"channel dim {D} != embedding dim {Dc}")
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    N = B * H * W
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_residual_workspace(N, K, D, Q, dev, shared=shared)
+            prepared = False
+        z_q = torch.empty_like(z_e) if want_zq else None
+        res = torch.empty_like(z_e) if want_residual else None
+        idx = torch.empty((Q, N), dtype=torch.int64, device=dev)
+        hist = torch.empty((Q, K), dtype=torch.int32, device=dev)
+        scal = torch.empty((2 * Q + 1,), dtype=torch.float32, device=dev)
+        flags = (VQ_ROWMAJOR if rowmajor else 0) | (VQ_CODEBOOK_PREPARED if prepared else 0) | (VQ_RESIDUAL_SHARED if shared else 0)
+        _lib.check(_lib.load().vqvae_vq_residual_forward_f32(
+            z_e.data_ptr(), _ptr_array(books), B, D, H, W, K, Q, float(beta), flags,
+            z_q.data_ptr() if want_zq else None, idx.data_ptr(), hist.data_ptr(), scal.data_ptr(), scal.data_ptr() + 4 * Q,
+            scal.data_ptr() + 8 * Q, res.data_ptr() if want_residual else None, workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(z_e)))
+    out = (scal[2 * Q], z_q, scal[Q:2 * Q], idx, hist, scal[:Q])
+    return out + (res,) if want_residual else out
+
+
+def vq_residual_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, rowmajor: bool = False, shared: bool = False,
+                       validate: bool = True) -> torch.Tensor:
+    """(Q, N) indices -> the sum of their code rows in stage order, (B,D,H,W) or (B,H,W,D) when rowmajor
+    (vqvae_vq_residual_decode_f32).  Indices outside [0, K) raise IndexError (one host sync; skipped with validate=False or while a
+    graph is captured: the kernel then writes NaN rows and never reads outside a codebook)."""
+    _check_dev("idx", idx, torch.int64)
+    books, nb = _residual_books(codebooks, shared)
+    K, D = books[0].shape
+    N = B * H * W
+    if idx.numel() % N or idx.numel() == 0:
+        raise ValueError("idx must hold Q*B*H*W indices")
+    Q = idx.numel() // N
+    if nb is not None and Q != nb:
+        raise ValueError(f"{Q} stages of indices for {nb} codebooks")
+    idx = idx.contiguous()
+    if validate and not torch.cuda.is_current_stream_capturing():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= K:
+            raise IndexError(f"index out of range in vq_residual_decode: [{lo}, {hi}] not within [0, {K})")
+    dev = idx.device
+    out = torch.empty((B, H, W, D) if rowmajor else (B, D, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().vqvae_vq_residual_decode_f32(
+            idx.data_ptr(), _ptr_array(books), B, D, H, W, K, Q, (VQ_ROWMAJOR if rowmajor else 0) | (VQ_RESIDUAL_SHARED if shared else 0),
+            out.data_ptr(), _stream_ptr(idx)))
+    return out

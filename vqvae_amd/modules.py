@@ -270,6 +270,104 @@ class VectorQuantizerEMA(VectorQuantizer):
         return out
 
 
+class ResidualVectorQuantizer(nn.Module):
+    """Residual quantization (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ): n_q codebooks quantize the same latent position, each
+    stage -- the reference's quantizer as written -- what the stage before it left over; z_q is z + (sum of the stages' codes - z)
+    and the loss the sum of the stages' losses (csrc/vq_residual.hip states the arithmetic).
+
+    Stage 0's codebook is `embedding` (VectorQuantizer's state_dict key: a reference checkpoint fills it); stages 1 .. n_q - 1 are
+    `residual_embeddings.{q-1}`, absent with shared_codebook, where every stage uses `embedding`.  Every codebook starts as
+    uniform(-1/K, 1/K), like the reference's."""
+
+    LAZY_MIN_ENCODINGS = True
+
+    def __init__(self, n_q, n_e, e_dim, beta, shared_codebook=False):
+        super().__init__()
+        if not 1 <= int(n_q) <= 16:
+            raise ValueError("n_q must be in [1, 16]")
+        self.n_q = int(n_q)
+        self.n_e = n_e
+        self.e_dim = e_dim
+        self.beta = beta
+        self.shared_codebook = bool(shared_codebook)
+        self.embedding = nn.Embedding(self.n_e, self.e_dim)
+        self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
+        if not self.shared_codebook:
+            self.residual_embeddings = nn.ModuleList(nn.Embedding(self.n_e, self.e_dim) for _ in range(self.n_q - 1))
+            for emb in self.residual_embeddings:
+                emb.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
+
+    def codebooks(self):
+        """the distinct codebooks in stage order (one when shared)"""
+        if self.shared_codebook:
+            return [self.embedding.weight]
+        return [self.embedding.weight] + [emb.weight for emb in self.residual_embeddings]
+
+    def invalidate(self):
+        """Forget the prepared codebook images (VectorQuantizer.invalidate: after a write through `.data`)."""
+        for slot in _cache.side(self).get("ws", {}).values():
+            slot[1] = None
+
+    def _workspace(self, N):
+        """-> (workspace, prepared, key, slot), one per (device, stream, N): VectorQuantizer._workspace with every stage's image"""
+        ws_ = self.codebooks()
+        w = ws_[0]
+        key = tuple((t.data_ptr(), t._version) for t in ws_) + (w.device,)
+        table = _cache.side(self).setdefault("ws", {})
+        skey = (str(w.device), torch.cuda.current_stream(w.device).cuda_stream if w.is_cuda else 0, N)
+        slot = _cache.lru_get(table, skey)
+        if slot is None:
+            slot = [F_hip.vq_residual_workspace(N, self.n_e, self.e_dim, self.n_q, w.device, shared=self.shared_codebook), None]
+            _cache.lru_put(table, skey, slot, 8)
+        return slot[0], slot[1] == key, key, slot
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (loss, z_q, perplexity (n_q,), idx (n_q, N), hist (n_q, K)); no one-hot."""
+        books = self.codebooks()
+        N = z.numel() // self.e_dim
+        ws, prepared, key, slot = self._workspace(N)
+        if not prepared:
+            slot[1] = None
+        if torch.is_grad_enabled() and (z.requires_grad or any(w.requires_grad for w in books)):
+            from .training import RVQStraightThrough           # HIP forward + HIP backward
+            out = RVQStraightThrough.apply(z, self.beta, rowmajor, self.shared_codebook, self.n_q, ws, prepared, *books)
+        else:
+            out = F_hip.vq_residual_forward(z, [w.detach() for w in books], self.beta, rowmajor=rowmajor,
+                                            shared=self.shared_codebook, n_q=self.n_q, workspace=ws, prepared=prepared,
+                                            want_zq=want_zq)
+        slot[1] = key
+        return out[:5]
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate()
+        return super()._apply(fn, *args, **kwargs)
+
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """Opt-in data-dependent start, stage by stage: E_q = k-means (functional.vq_kmeans) of the rows of r_q, then one assignment
+        against it and one advance r_{q+1} = r_q - E_q[idx_q], r_0 = z.  shared_codebook: k-means of z only.
+        -> [(codebook, counts of the last assignment)] per distinct codebook."""
+        _need_hip_f32(z, "init_codebook_")
+        r = z.detach().contiguous()
+        out = []
+        books = self.codebooks()
+        for q, w in enumerate(books):
+            codebook, counts = F_hip.vq_kmeans(r, self.n_e, iters, generator=generator, rowmajor=rowmajor)
+            w.copy_(codebook)
+            out.append((codebook, counts))
+            if q + 1 < len(books):
+                r = F_hip.vq_residual_forward(r, [codebook], 0.0, rowmajor=rowmajor, want_zq=False, want_residual=True)[6]
+        return out
+
+    def forward(self, z, *, rowmajor=False):
+        """The reference's 5-tuple shape: (loss, z_q, perplexity (n_q,), stage 0's min_encodings, idx (n_q, N)).  rowmajor: z and
+        z_q are (B,H,W,D), as VQVAE.forward hands them over."""
+        loss, z_q, perplexity, idx, _ = self.quantize(z, rowmajor=rowmajor)
+        idx0 = idx[0].reshape(-1, 1)
+        min_encodings = LazyOneHot(idx0, self.n_e) if self.LAZY_MIN_ENCODINGS else F_hip.vq_onehot(idx0, self.n_e)
+        return loss, z_q, perplexity, min_encodings, idx
+
+
 class ResidualLayer(nn.Module):
     """Parameter holder mirroring models/residual.py:8-29."""
 
@@ -370,11 +468,23 @@ class VQVAE(nn.Module):
     """Mirrors models/vqvae.py:10-44."""
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
-                 save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None):
+                 save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
+                 shared_codebook=False):
         super().__init__()
+        if n_quantizers < 1:
+            raise ValueError("n_quantizers must be >= 1")
+        if n_quantizers > 1 and ema_decay is not None:
+            raise ValueError("residual quantization (n_quantizers > 1) has no EMA codebook update: leave ema_decay unset")
+        if n_quantizers == 1 and shared_codebook:
+            raise ValueError("shared_codebook needs n_quantizers > 1")
         self.encoder = Encoder(3, h_dim, n_res_layers, res_h_dim)
         self.pre_quantization_conv = nn.Conv2d(h_dim, embedding_dim, kernel_size=1, stride=1)
-        if ema_decay is None:
+        if n_quantizers > 1:
+            if restart_threshold is not None:
+                raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
+            self.vector_quantization = ResidualVectorQuantizer(n_quantizers, n_embeddings, embedding_dim, beta,
+                                                               shared_codebook=shared_codebook)
+        elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
             self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta)
@@ -396,7 +506,7 @@ class VQVAE(nn.Module):
         _cache.drop(self, "c_weights")
         for mod in self.modules():
             conv_hip.invalidate(mod)
-            if isinstance(mod, VectorQuantizer):
+            if isinstance(mod, (VectorQuantizer, ResidualVectorQuantizer)):
                 mod.invalidate()
 
     # forward / encode / decode_indices follow vqvae_weights_range_check_f32's recommendation for the checkpoint (scheme_hint()) unless
@@ -600,11 +710,23 @@ class VQVAE(nn.Module):
             if not x.is_cuda or x.dtype != torch.float32:
                 raise VqvaeHipError("VQVAE.forward needs a CUDA(HIP) fp32 input: there is no CPU path")
             z_e = A_hip.encoder_forward_train(self.encoder, x, self.pre_quantization_conv)
-            embedding_loss, z_q, perplexity, _, _ = self.vector_quantization.quantize(z_e, rowmajor=True)
+            if isinstance(self.vector_quantization, ResidualVectorQuantizer):
+                # (through the module's __call__: forward hooks see z_e; the stages' mean perplexity is the scalar main.py:82 logs)
+                embedding_loss, z_q, perplexity, _, _ = self.vector_quantization(z_e, rowmajor=True)
+                perplexity = perplexity.mean()
+            else:
+                embedding_loss, z_q, perplexity, _, _ = self.vector_quantization.quantize(z_e, rowmajor=True)
             x_hat = A_hip.decoder_forward_train(self.decoder, z_q)
             return embedding_loss, x_hat, perplexity
         _require_forward_only(x, *self.parameters())
         vq = self.vector_quantization
+        if isinstance(vq, ResidualVectorQuantizer):
+            # residual stages: the per-layer path (the fused whole-path entries quantize once)
+            if C_hip.get_conv_backend() == "hip":
+                _need_hip_f32(x, "VQVAE.forward")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            embedding_loss, z_q, perplexity, _, _ = vq(z_e, rowmajor=True)
+            return embedding_loss, C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True), perplexity.mean()
         ema = isinstance(vq, VectorQuantizerEMA)
         # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it)
         if (C_hip.get_conv_backend() == "hip" and not verbose and x.is_cuda and x.dtype == torch.float32
@@ -655,6 +777,10 @@ class VQVAE(nn.Module):
         (vqvae_encode_f32): on the default shapes the encoder's last kernel quantizes its own z_e and only the indices are
         written -- no z_e, no z_q."""
         from . import _lib, conv as C_hip
+        if isinstance(self.vector_quantization, ResidualVectorQuantizer):
+            # (n_quantizers, N) int64, stage-major: the per-layer encoder, then the residual stages (indices only)
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
         if C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32:
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             # (VectorQuantizer's quantize: an EMA quantizer in training mode must not update from encode())
@@ -689,6 +815,17 @@ class VQVAE(nn.Module):
         entry never reads outside the codebook either way, a bad index shows as NaN pixels of its image (include/vqvae_hip.h)."""
         from . import _lib, conv as C_hip
         K = self.vector_quantization.n_e
+        if isinstance(self.vector_quantization, ResidualVectorQuantizer):
+            # n_quantizers * B * H * W indices, stage-major as encode() returns them: the sum of the stages' codes, then the decoder
+            vq = self.vector_quantization
+            if idx.numel() != vq.n_q * B * H * W:
+                raise ValueError(f"expected {vq.n_q * B * H * W} indices ({vq.n_q} stages), got {idx.numel()}")
+            idx = idx.contiguous().view(vq.n_q, -1).to(torch.int64)
+            if validate and (int(idx.min()) < 0 or int(idx.max()) >= K):
+                raise IndexError(f"code index out of range [0, {K})")
+            z_q = F_hip.vq_residual_decode(idx, [w.detach() for w in vq.codebooks()], B, H, W, rowmajor=True,
+                                           shared=vq.shared_codebook, validate=False)
+            return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
         if idx.numel() != B * H * W:
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
         if C_hip.get_conv_backend() != "hip" or not idx.is_cuda:

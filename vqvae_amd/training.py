@@ -169,3 +169,85 @@ def step_losses(embedding_loss, x_hat, perplexity, x, x_train_var):
     `stats[1].backward()` is `loss.backward()` of main.py:78; `stats.tolist()` is the single D2H copy
     that replaces the three `.cpu()` calls of main.py:81-83."""
     return _StepLosses.apply(x_hat, x, embedding_loss, perplexity, 1.0 / float(x_train_var))
+
+
+# ---- residual vector quantization (csrc/vq_residual.hip) -------------------------------------------------------------------------
+
+def vq_residual_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowmajor=False, shared=False, need_z=True,
+                         need_codebooks=True):
+    """Gradients of functional.vq_residual_forward (vqvae_vq_residual_backward_f32): what autograd derives when every stage is the
+    reference quantizer and r_{q+1} = r_q - e_q.detach().
+
+    z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.  idx: the forward's (Q, N) indices.  grad_loss: 0-dim device tensor or
+    None (= 1).  -> (grad_z or None, list of codebook gradients -- one per codebook, one in all when shared -- or None)."""
+    F_hip._check_dev("z_e", z_e)
+    F_hip._check_dev("idx", idx, torch.int64)
+    books, nb = F_hip._residual_books(codebooks, shared)
+    z_e = z_e.contiguous()
+    idx = idx.contiguous()
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K = books[0].shape[0]
+    N = B * H * W
+    if books[0].shape[1] != D or idx.numel() % N or idx.numel() == 0:
+        raise ValueError("shape mismatch between z_e, the codebooks and idx")
+    Q = idx.numel() // N
+    if nb is not None and nb != Q:
+        raise ValueError(f"{Q} stages of indices for {nb} codebooks")
+    if grad_zq is not None:
+        F_hip._check_dev("grad_zq", grad_zq)
+        grad_zq = grad_zq.contiguous()
+        if grad_zq.shape != z_e.shape:
+            raise ValueError("grad_zq must have z_e's shape")
+    if grad_loss is not None:
+        F_hip._check_dev("grad_loss", grad_loss)
+        grad_loss = grad_loss.reshape(1).contiguous()
+    if not (need_z or need_codebooks):
+        return None, None
+    dev = z_e.device
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        gz = torch.empty_like(z_e) if need_z else None
+        ge = [torch.empty_like(c) for c in books] if need_codebooks else None
+        ws = None
+        if need_codebooks:
+            n = L.vqvae_vq_residual_backward_workspace_bytes(N, K, D, Q)
+            if n == 0:
+                raise _lib.VqvaeHipError(f"residual VQ backward: N={N}, K={K}, D={D}, Q={Q} not supported")
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        _lib.check(L.vqvae_vq_residual_backward_f32(
+            z_e.data_ptr(), F_hip._ptr_array(books), idx.data_ptr(),
+            grad_zq.data_ptr() if grad_zq is not None else None,
+            grad_loss.data_ptr() if grad_loss is not None else None,
+            B, D, H, W, K, Q, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_RESIDUAL_SHARED if shared else 0),
+            gz.data_ptr() if gz is not None else None, F_hip._ptr_array(ge) if ge is not None else None,
+            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
+    return gz, ge
+
+
+class RVQStraightThrough(torch.autograd.Function):
+    """(z_e, E_0 .. ) -> (loss, z_q, perplexity (Q,), idx (Q, N), hist (Q, K), loss_stage (Q,)) of the residual quantizer: loss and
+    z_q differentiable (d z_q / d z = I), the rest not.  apply(z_e, beta, rowmajor, shared, n_q, workspace, prepared, *codebooks)."""
+
+    @staticmethod
+    def forward(ctx, z_e, beta, rowmajor, shared, n_q, workspace, prepared, *codebooks):
+        z = z_e.detach().contiguous()
+        books = [c.detach().contiguous() for c in codebooks]
+        loss, z_q, perplexity, idx, hist, loss_stage = F_hip.vq_residual_forward(
+            z, books, beta, rowmajor=rowmajor, shared=shared, n_q=n_q, workspace=workspace, prepared=prepared)
+        ctx.save_for_backward(z, idx, *books)
+        ctx.beta, ctx.rowmajor, ctx.shared = beta, rowmajor, shared
+        ctx.mark_non_differentiable(perplexity, idx, hist, loss_stage)
+        return loss, z_q, perplexity, idx, hist, loss_stage
+
+    @staticmethod
+    def backward(ctx, g_loss, g_zq, *_unused):
+        z, idx, *books = ctx.saved_tensors
+        need_z = ctx.needs_input_grad[0]
+        need_w = any(ctx.needs_input_grad[7:])
+        if g_loss is None:
+            g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
+        gz, ge = vq_residual_backward(z, books, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, shared=ctx.shared,
+                                      need_z=need_z, need_codebooks=need_w)
+        if ge is None:
+            ge = [None] * len(books)
+        return (gz, None, None, None, None, None, None) + tuple(ge)
