@@ -113,6 +113,8 @@ VQVAE_API int vqvae_calibration_mfma_f16(int iters, void *scratch, size_t scratc
 
 #define VQVAE_VQ_BWD_COMMITMENT 0x800 /* vqvae_vq_backward_f32 only: the gradient of VectorQuantizerEMA's loss beta * mean((z_q - z)^2)
                                         (grad_z only, scale 2 beta / (N D); grad_codebook must be NULL) */
+#define VQVAE_VQ_BWD_ROTATION   0x20000 /* vqvae_vq_backward_f32 only: grad_zq reaches grad_z through the rotation trick (arXiv 2410.06424)
+                                        instead of unchanged; grad_z must not be NULL, grad_codebook is what it is without the flag */
 
 #define VQVAE_VQ_UNFUSED        0x40 /* vqvae_forward_f32 only: run the quantizer as its own launch even where the encoder's last
                                         kernel would quantize its z_e in place (32x32 images, h_dim 128, K = 128 k <= 1024, D = 64: z_e is
@@ -305,7 +307,17 @@ VQVAE_API int vqvae_transpose_f32(const float *x, int64_t batch, int R, int C, f
  *   z_e / grad_zq / grad_z share the layout selected by VQVAE_VQ_ROWMAJOR.  Either output may be NULL.
  *   The codebook gradient uses no floating-point atomics: rows are stably sorted by code and summed in a
  *   fixed order in fp64, so it is bit-reproducible run to run.  Parity with torch autograd: rtol 1e-5.
- *   flags | VQVAE_VQ_BWD_COMMITMENT: grad_z = grad_zq + g * 2 beta (z - e_idx) / (N D) only (VectorQuantizerEMA's loss).   */
+ *   flags | VQVAE_VQ_BWD_COMMITMENT: grad_z = grad_zq + g * 2 beta (z - e_idx) / (N D) only (VectorQuantizerEMA's loss).
+ *   flags | VQVAE_VQ_BWD_ROTATION (alone or with VQVAE_VQ_BWD_COMMITMENT): grad_z = rot(grad_zq) + the same loss term, where for
+ *   each row e of z with code q = E[idx] and upstream row g, rot(g) = lam R^T g = lam [g - 2 r (r^T g) + 2 e^ (q^^T g)] with
+ *   e^ = e/||e||, q^ = q/||q||, r = (e^ + q^)/||e^ + q^||, lam = ||q||/||e||: the gradient of z~_q = sg[lam R] e (Fifty et al.,
+ *   arXiv 2410.06424), whose value is q.  Evaluated per row in fp64 from five dot products added in ascending channel order and
+ *   rounded to fp32 once (the exact operation order: csrc/vq_rotation.hip's header); the same bits in both layouts and in every
+ *   run.  Fallback rule: a row whose z is all zeros, whose code is all zeros, whose norms are not finite, or that is antipodal to
+ *   its code (||e^ + q^||^2 < 2^-20: the reflection axis is undefined) keeps grad_zq unchanged, as without the flag.  A NaN in
+ *   grad_zq or z stays in its own row.  grad_codebook is untouched by the flag; grad_zq == NULL gives the unflagged result
+ *   (rot(0) = 0) from the unflagged kernel; grad_z == NULL with the flag is VQVAE_ERR_NULL.  Without the flag the entry launches
+ *   exactly what it always did.                                                                                                 */
 VQVAE_API size_t vqvae_vq_backward_workspace_bytes(int64_t N, int K, int D);
 VQVAE_API int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t *idx,
                                     const float *grad_zq, const float *grad_loss,

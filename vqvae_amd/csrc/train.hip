@@ -10,6 +10,8 @@
 //                              added in a fixed order in fp64 by one workgroup, and a code's chunks are combined in a
 //                              fixed order -- the result is bit-reproducible from run to run, and the work is
 //                              proportional to the rows however skewed the code histogram is.
+//                              With VQVAE_VQ_BWD_ROTATION the g_zq term of dL/dz goes through the rotation trick instead
+//                              (vq_rotation.hip states the arithmetic and holds the kernel); nothing else changes.
 //   vqvae_vq_ema_update_f32    the codebook update of VectorQuantizerEMA (arXiv 1711.00937 Appendix A.1): the same sorted,
 //                              fixed-order fp64 per-code sums, then exponential moving averages of counts and sums and the
 //                              Laplace-smoothed normalisation (optionally restarting codes whose average count is below a
@@ -18,6 +20,7 @@
 //                              (one D2H copy per step instead of three).
 //   vqvae_recon_loss_backward_f32   d/dx_hat of mean((x_hat - x)^2) / var.
 #include "train_reduce.h"
+#include "vq_rotation.h"
 
 namespace vqvae {
 
@@ -223,8 +226,8 @@ int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t
                           const float *grad_loss, int64_t B, int D, int H, int W, int K, float beta, int flags,
                           float *grad_z, float *grad_codebook, void *workspace, size_t workspace_bytes,
                           vqvae_stream_t stream) {
-    const bool commitment = (flags & VQVAE_VQ_BWD_COMMITMENT) != 0;
-    if (!z_e || !codebook || !idx || (!grad_z && !grad_codebook) || (commitment && !grad_z)) return VQVAE_ERR_NULL;
+    const bool commitment = (flags & VQVAE_VQ_BWD_COMMITMENT) != 0, rotation = (flags & VQVAE_VQ_BWD_ROTATION) != 0;
+    if (!z_e || !codebook || !idx || (!grad_z && !grad_codebook) || ((commitment || rotation) && !grad_z)) return VQVAE_ERR_NULL;
     if (B < 1 || D < 1 || H < 1 || W < 1 || K < 1) return VQVAE_ERR_SHAPE;
     if (D > 256 || K > 16384 || (commitment && grad_codebook)) return VQVAE_ERR_UNSUPPORTED;
     const long long HW = (long long)H * W, N = (long long)B * HW;
@@ -234,7 +237,13 @@ int vqvae_vq_backward_f32(const float *z_e, const float *codebook, const int64_t
     const double nd = (double)N * (double)D;
     // the reference's z term is 2/(ND) (its commitment term carries no beta); the EMA quantizer's loss is beta * mse only
     const float gz_scale = commitment ? (float)(2.0 * (double)beta / nd) : (float)(2.0 / nd);
-    if (grad_z) {
+    if (grad_z && rotation && grad_zq) {
+        // the rotation-trick gradient (vq_rotation.hip); without an upstream gradient rot(0) = 0: the launch below
+        RotArgs a;
+        a.z = z_e; a.cb = codebook; a.idx = reinterpret_cast<const long long *>(idx); a.g_zq = grad_zq; a.g_loss = grad_loss;
+        a.N = N; a.D = D; a.HW = (int)HW; a.K = K; a.rowmajor = rowmajor; a.scale = gz_scale; a.out = grad_z;
+        launch_vq_rotation_gradz(a, st);
+    } else if (grad_z) {
         const long long total = N * D;
         const bool vec4 = rowmajor && (D & 3) == 0 &&
                           !((reinterpret_cast<uintptr_t>(z_e) | reinterpret_cast<uintptr_t>(codebook) | reinterpret_cast<uintptr_t>(grad_z) |

@@ -22,6 +22,7 @@ FWD_CONV_EXACT_FP32 = 0x2000
 FWD_DEBUG_ZE = 0x4000            # tests: the fused encoder+quantizer kernel also writes its z_e (include/vqvae_hip.h)
 VQ_UNITS32_8WAVES = 0x400
 VQ_BWD_COMMITMENT = 0x800        # vqvae_vq_backward_f32: grad_z of beta * mse only (VectorQuantizerEMA)
+VQ_BWD_ROTATION = 0x20000        # vqvae_vq_backward_f32: grad_zq reaches grad_z through the rotation trick (csrc/vq_rotation.hip)
 
 
 def _stream_ptr(t: torch.Tensor) -> int:

@@ -131,11 +131,14 @@ class VectorQuantizer(nn.Module):
 
     LAZY_MIN_ENCODINGS = True          # forward()'s fourth output: LazyOneHot (the (N, K) one-hot on first use) or the tensor itself
 
-    def __init__(self, n_e, e_dim, beta):
+    def __init__(self, n_e, e_dim, beta, *, rotation_trick=False):
         super().__init__()
         self.n_e = n_e
         self.e_dim = e_dim
         self.beta = beta
+        # opt-in: the decoder's gradient reaches the encoder through the rotation trick (arXiv 2410.06424; csrc/vq_rotation.hip)
+        # instead of unchanged.  A plain attribute: no parameter, no buffer, no state_dict key; the forward is the same.
+        self.rotation_trick = bool(rotation_trick)
         self.embedding = nn.Embedding(self.n_e, self.e_dim)
         self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)   # quantizer.py:27
 
@@ -168,7 +171,7 @@ class VectorQuantizer(nn.Module):
             slot[1] = None                                       # a failed launch must not leave a stale "prepared" image
         if torch.is_grad_enabled() and (z.requires_grad or w.requires_grad):
             from .training import VQStraightThrough          # HIP forward + HIP backward
-            out = VQStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared)
+            out = VQStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared, self.rotation_trick)
         else:
             out = F_hip.vq_forward(z, w.detach(), self.beta, rowmajor=rowmajor, workspace=ws,
                                    prepared=prepared, want_zq=want_zq)
@@ -211,8 +214,8 @@ class VectorQuantizerEMA(VectorQuantizer):
     `generator`, or the default CUDA generator, on every update).  None: no restart.  Under data parallelism each replica updates
     from its own shard; the statistics are not merged across ranks."""
 
-    def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None):
-        super().__init__(n_e, e_dim, beta)
+    def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, rotation_trick=False):
+        super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick)
         self.decay = float(decay)
         self.eps = float(eps)
         self.restart_threshold = None if restart_threshold is None else float(restart_threshold)
@@ -259,7 +262,7 @@ class VectorQuantizerEMA(VectorQuantizer):
             slot[1] = None
         if torch.is_grad_enabled() and z.requires_grad:
             from .training import VQEMAStraightThrough      # HIP forward + HIP commitment-only backward
-            out = VQEMAStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared)
+            out = VQEMAStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared, self.rotation_trick)
         else:
             mse, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w.detach(), 0.0, rowmajor=rowmajor, workspace=ws,
                                                                prepared=prepared, want_zq=want_zq)
@@ -469,8 +472,10 @@ class VQVAE(nn.Module):
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
-                 shared_codebook=False):
+                 shared_codebook=False, rotation_trick=False):
         super().__init__()
+        if n_quantizers > 1 and rotation_trick:
+            raise ValueError("rotation_trick is the one-stage quantizers' option: residual quantization (n_quantizers > 1) has none")
         if n_quantizers < 1:
             raise ValueError("n_quantizers must be >= 1")
         if n_quantizers > 1 and ema_decay is not None:
@@ -487,11 +492,11 @@ class VQVAE(nn.Module):
         elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
-            self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta)
+            self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta, rotation_trick=rotation_trick)
         else:
             # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
             self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,
-                                                          restart_threshold=restart_threshold)
+                                                          restart_threshold=restart_threshold, rotation_trick=rotation_trick)
         self.decoder = Decoder(embedding_dim, h_dim, n_res_layers, res_h_dim)
         if save_img_embedding_map:
             self.img_to_embedding_map = {i: [] for i in range(n_embeddings)}

@@ -22,14 +22,18 @@ def _sp(t):
 
 
 def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False, need_z=True, need_codebook=True,
-                commitment=False):
+                commitment=False, rotation=False):
     """Gradients of VectorQuantizer.forward (models/quantizer.py:63-67) w.r.t. z_e and the codebook.
 
     z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.  grad_loss: 0-dim device tensor or None (=1).
     commitment=True: the z gradient of VectorQuantizerEMA's loss beta * mse instead (no codebook gradient).
+    rotation=True: grad_zq reaches grad_z through the rotation trick (arXiv 2410.06424; csrc/vq_rotation.hip states the arithmetic
+    and its fallback rows) instead of unchanged; needs need_z.  The codebook gradient is the same either way.
     Returns (grad_z or None, grad_codebook or None)."""
     if commitment and need_codebook:
         raise ValueError("the commitment-only gradient has no codebook term")
+    if rotation and not need_z:
+        raise ValueError("the rotation trick changes grad_z only: need_z must be set")
     F_hip._check_dev("z_e", z_e)
     F_hip._check_dev("codebook", codebook)
     F_hip._check_dev("idx", idx, torch.int64)
@@ -66,7 +70,8 @@ def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False,
             z_e.data_ptr(), codebook.data_ptr(), idx.data_ptr(),
             grad_zq.data_ptr() if grad_zq is not None else None,
             grad_loss.data_ptr() if grad_loss is not None else None,
-            B, D, H, W, K, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0),
+            B, D, H, W, K, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0) |
+            (F_hip.VQ_BWD_ROTATION if rotation else 0),
             gz.data_ptr() if gz is not None else None, ge.data_ptr() if ge is not None else None,
             ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
     return gz, ge
@@ -74,16 +79,17 @@ def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False,
 
 class VQStraightThrough(torch.autograd.Function):
     """(z_e, codebook) -> (loss, z_q, perplexity, idx, hist) with the reference's gradient structure
-    [MEASURED in SURVEY.md 8b]: loss and z_q differentiable, perplexity / idx / hist not; d z_q / d z = I."""
+    [MEASURED in SURVEY.md 8b]: loss and z_q differentiable, perplexity / idx / hist not; d z_q / d z = I, or with rotation=True
+    the rotation trick's lam R^T per row (vq_backward's rotation).  The forward is the same either way."""
 
     @staticmethod
-    def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared):
+    def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared, rotation=False):
         z = z_e.detach().contiguous()
         w = codebook.detach().contiguous()
         loss, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w, beta, rowmajor=rowmajor, workspace=workspace,
                                                             prepared=prepared)
         ctx.save_for_backward(z, w, idx)
-        ctx.beta, ctx.rowmajor = beta, rowmajor
+        ctx.beta, ctx.rowmajor, ctx.rotation = beta, rowmajor, bool(rotation)
         ctx.mark_non_differentiable(perplexity, idx, hist)
         return loss, z_q, perplexity, idx, hist
 
@@ -94,22 +100,23 @@ class VQStraightThrough(torch.autograd.Function):
         if g_loss is None:
             g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
         gz, gw = vq_backward(z, w, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, need_z=need_z,
-                             need_codebook=need_w)
-        return gz, gw, None, None, None, None
+                             need_codebook=need_w, rotation=ctx.rotation and need_z)
+        return gz, gw, None, None, None, None, None
 
 
 class VQEMAStraightThrough(torch.autograd.Function):
     """VectorQuantizerEMA's forward under autograd: (z_e, codebook) -> (beta * mse, z_q, perplexity, idx, hist).  Only z_e gets a
     gradient (dz = g_zq + g 2 beta (z - e_idx) / (N D)); the codebook is moved by the EMA update, which writes it in place right
-    after this forward.  So the backward must not read the live weight: it keeps its own copy of the codebook it quantized with."""
+    after this forward.  So the backward must not read the live weight: it keeps its own copy of the codebook it quantized with.
+    rotation=True: g_zq goes through the rotation trick, as in VQStraightThrough."""
 
     @staticmethod
-    def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared):
+    def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared, rotation=False):
         z = z_e.detach().contiguous()
         w = codebook.detach().contiguous()
         mse, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w, 0.0, rowmajor=rowmajor, workspace=workspace, prepared=prepared)
         ctx.save_for_backward(z, w.clone(), idx)
-        ctx.beta, ctx.rowmajor = beta, rowmajor
+        ctx.beta, ctx.rowmajor, ctx.rotation = beta, rowmajor, bool(rotation)
         ctx.mark_non_differentiable(perplexity, idx, hist)
         return mse * beta, z_q, perplexity, idx, hist
 
@@ -120,8 +127,9 @@ class VQEMAStraightThrough(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if g_loss is None:
                 g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
-            gz, _ = vq_backward(z, w, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, need_codebook=False, commitment=True)
-        return gz, None, None, None, None, None
+            gz, _ = vq_backward(z, w, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, need_codebook=False, commitment=True,
+                                rotation=ctx.rotation)
+        return gz, None, None, None, None, None, None
 
 
 class _StepLosses(torch.autograd.Function):
