@@ -793,6 +793,11 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
 // Scales: the image's largest |x| is measured; the first layer's outputs are bounded by L1 * max|x| + max|b| (L1 = the
 // largest absolute row sum of its weights, in the header) -- a power of two up to ~8x above the true maximum, which costs
 // the second term's range three bits at the very bottom and nothing where it matters (see split8_h).
+// Both layers' biases lie behind their scale tables in LDS (profiles/ends_ab.txt): first_layer runs eight times per image and used to
+// wait out an L2 round trip for its 16 bias values each time, with no MFMA in flight.  hipcc: 256 registers, no scratch (12 B
+// before), 79 872 B of LDS = two workgroups per CU.  -DVQVAE_ENDS_NO_TABLES restores the global loads (tools/build_variant.py builds the
+// A/B arms).  Measured and NOT kept: the twelve patch gathers of a sub-position requested one sub-position ahead, under the second
+// chunk's stages (no spill once the request is unconditional, but the step was no faster: 0.9444 against 0.9423 ms).
 #ifndef EF_MINW
 #define EF_MINW 2
 #endif
@@ -811,7 +816,11 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
     __shared__ u32x4 As_all[4 * TILE4];
     __shared__ u32x4 Wb_all[2 * WBUF];
     __shared__ u32x4 W0s[2 * CIN * 2 * 64];                // first layer: [slice 2][ci][term 2] x 64 lanes
+#ifndef VQVAE_ENDS_NO_TABLES
+    __shared__ __attribute__((aligned(16))) float dw_s[2 * (64 + 128)];      // + both layers' biases behind the scales: [192, 256), [256, 384)
+#else
     __shared__ __attribute__((aligned(16))) float dw_s[64 + 128];
+#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     u32x4 *As = As_all + wave * TILE4;
@@ -840,6 +849,12 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
     for (int i = tid; i < 2 * CIN * 2 * 64; i += 256) W0s[i] = w0img[i];
     // both layers' per-output-channel weight scales 2^-kw[c]: first layer [0, 64), second [64, 192) (behind the W0s barrier)
     if (tid < C0 + C) dw_s[tid] = tid < C0 ? h2_dw(hdr0)[tid] : h2_dw(hdr2)[tid - C0];
+#ifndef VQVAE_ENDS_NO_TABLES
+    // ... and both layers' biases (a null pointer = zeros): the epilogues read them from here, not with vector global loads that wait
+    // out an L2 round trip with no MFMA in flight (eight first_layer calls per image and the final epilogue)
+    if (tid < C0 + C) dw_s[C0 + C + tid] = tid < C0 ? (bias0 ? bias0[tid] : 0.0f) : (bias2 ? bias2[tid - C0] : 0.0f);
+    const float *const bias0_s = dw_s + C0 + C, *const bias2_s = dw_s + 2 * C0 + C;
+#endif
     if (lane < 8) As[(lane >> 1) * PLANE + (lane & 1) * HP + PX] = u32x4{0, 0, 0, 0};       // padding pixels of the four planes
 
     // block-pixel bookkeeping: bit sub * 4 + tap of tapok = block offset ((tap >> 1) - (sub >> 1), (tap & 1) - (sub & 1)) is inside
@@ -949,9 +964,14 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
             prod3x2t(XB[0][ci][0], XB[0][ci][1], XB[1][ci][0], XB[1][ci][1], wp[ci * 128], wp[ci * 128 + 64], acc0[0], acc0[1]);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
+#ifndef VQVAE_ENDS_NO_TABLES
+            const f32x4 dv = h2_dw4(dw_s, sl * 32, g, h, d0);
+            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias0_s + sl * 32 + 8 * g + 4 * h);
+#else
             f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
             if (bias0) bv = *reinterpret_cast<const f32x4 *>(bias0 + sl * 32 + 8 * g + 4 * h);
             const f32x4 dv = h2_dw4(dw_s, sl * 32, g, h, d0);
+#endif
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1017,9 +1037,14 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
             float v[16];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+#ifndef VQVAE_ENDS_NO_TABLES
+                const f32x4 dv = h2_dw4(dw_s + C0, nt * 32, g, h, d2);
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias2_s + nt * 32 + 8 * g + 4 * h);
+#else
                 f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (bias2) bv = *reinterpret_cast<const f32x4 *>(bias2 + nt * 32 + 8 * g + 4 * h);
                 const f32x4 dv = h2_dw4(dw_s + C0, nt * 32, g, h, d2);
+#endif
 #pragma unroll
                 for (int q = 0; q < 4; q += 2) {
                     v[4 * g + q] = Y[mt][nt][4 * g + q];
@@ -1065,6 +1090,13 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
 //       wave-private 34 x 42 LDS tile per channel and read it back: 420 LDS operations per image, 28 % of a wave's time;
 //       scattered 4-byte read-modify-writes straight from the accumulator layout were measured first: 570 us instead of 330
 //       for the two separate kernels -- L2 request bound.)
+// Registers (profiles/ends_ab.txt): 128 accumulator registers in layer 1, T (128) behind it.  What hipcc spilled straight behind its
+// loads -- so that the loads' latency was waited out on the spot -- was a CONDITIONAL definition carried round the pass loop, not
+// pressure: pass 1's read-back quads, requested under `if (py > 0)`.  They are requested in both passes now, pass 0's with every lane
+// out of range (nothing is fetched).  The first layer's biases lie behind `dw_s` in LDS; the second layer's three biases and weight
+// scales and the image's recorded maximum are scalar loads at kernel entry.  Together: 4 spilled registers, 20 B of scratch, 1 static
+// scratch load (41 / 168 B / 25 before).  -DVQVAE_ENDS_NO_TAIL_REGS / -DVQVAE_ENDS_NO_TABLES restore the
+// earlier code.
 struct TailGeom {
     unsigned long long dym[4], dxm[4];             // 4 bits per tap: dy + 8, dx + 8 (ConvGeom) of each phase
 };
@@ -1089,14 +1121,33 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
     constexpr int WBUF = 16 * 64, NSTAGE = 34;             // per pass: 4 chunks x 4 tap pairs (16 pieces each) + the second layer's image
     __shared__ u32x4 As_all[4 * TILE4];
     __shared__ u32x4 Wb_all[2 * WBUF];
+#ifndef VQVAE_ENDS_NO_TABLES
+    // the first layer's per-output-channel weight scales 2^-kw[c] and, behind them, its biases (a null pointer = zeros): the phase
+    // epilogues read both from here (stage barriers precede every use), not with vector global loads at their start
+    __shared__ __attribute__((aligned(16))) float dw_s[2 * 64];
+    if (threadIdx.x < 128) dw_s[threadIdx.x] = threadIdx.x < 64 ? h2_dw(hdr2)[threadIdx.x] : (bias2 ? bias2[threadIdx.x - 64] : 0.0f);
+    // the second layer's three biases and weight scales 2^-kw4[co]: scalar loads at kernel entry
+    float b4_u[3], w4d_u[3];
+#pragma unroll
+    for (int co = 0; co < 3; ++co) {
+        b4_u[co] = bias4 ? bias4[co] : 0.0f;
+        w4d_u[co] = h2_dw(hdr4)[co];
+    }
+#else
     __shared__ __attribute__((aligned(16))) float dw_s[64];      // the first layer's per-output-channel weight scales 2^-kw[c]
     if (threadIdx.x < 64) dw_s[threadIdx.x] = h2_dw(hdr2)[threadIdx.x];      // (stage barriers precede every use)
+#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     u32x4 *As = As_all + wave * TILE4;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const long long img = (long long)blockIdx.x * 4 + wave;
     const bool img_ok = img < B;
+    // (the wave-uniform image index: scalar loads, and descriptors that hipcc does not wrap in a waterfall loop)
+    const long long img_u = (long long)blockIdx.x * 4 + wave_u;
+#ifndef VQVAE_ENDS_NO_TABLES
+    const int given = (in_amax && img_u < B) ? in_amax[img_u] : -1;         // the image's recorded maximum, requested at kernel entry
+#endif
 
     // (scalar source base + this lane's constant byte offset: no vector instruction and no address register per piece)
     const unsigned dma_lane = (unsigned)lane * 16u;
@@ -1127,7 +1178,6 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
     if (lane < 8) As[(lane >> 1) * PLANE + (lane & 1) * HP + PX] = u32x4{0, 0, 0, 0};       // padding pixels of the four planes
 
     // (built from the wave-uniform image index: with a lane-derived one hipcc wraps every access in a waterfall loop)
-    const long long img_u = (long long)blockIdx.x * 4 + wave_u;
     const auto ors = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)(img_u < B ? img_u : 0) * (CO * 1024), 0, img_u < B ? (unsigned)(CO * 4096) : 0u, 0x00020000);
     int spx[MT];
 #pragma unroll
@@ -1139,7 +1189,9 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
         for (int j = 0; j < 8; ++j) raw[j] = *reinterpret_cast<const f32x4 *>(src + 32 * cc + 4 * j);
     };
     float m = 0.0f;
+#ifdef VQVAE_ENDS_NO_TABLES
     const int given = (in_amax && img_ok) ? in_amax[img] : -1;
+#endif
     if (given >= 0) m = __int_as_float(given);
     else for (int cc = 0; cc < CPT; ++cc) {
         load_raw(cc);
@@ -1258,9 +1310,14 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
+#ifndef VQVAE_ENDS_NO_TABLES
+                    const f32x4 dv = h2_dw4(dw_s, nt * 32, g, h, d1);
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(dw_s + 64 + nt * 32 + 8 * g + 4 * h);
+#else
                     f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
                     if (bias2) bv = *reinterpret_cast<const f32x4 *>(bias2 + nt * 32 + 8 * g + 4 * h);
                     const f32x4 dv = h2_dw4(dw_s, nt * 32, g, h, d1);
+#endif
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1325,14 +1382,29 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int g = 0; g < 2; ++g)
+#ifndef VQVAE_ENDS_NO_TAIL_REGS
+                    // (pass 0 issues them too, every lane out of range: nothing is fetched.  Requested under `if (py > 0)` the quads are
+                    // conditional definitions, and the allocator spilled the channel ahead straight behind its loads)
+                    o[mt][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ors, py > 0 ? roff[mt][g] : kOobOffset, (unsigned)co * 4096u, 0));
+#else
                     o[mt][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ors, roff[mt][g], (unsigned)co * 4096u, 0));
+#endif
         };
-        if (py > 0) ov_load(0, ov[0]);
+#ifndef VQVAE_ENDS_NO_TAIL_REGS
+        constexpr bool ov_always = true;
+#else
+        constexpr bool ov_always = false;
+#endif
+        if (ov_always || py > 0) ov_load(0, ov[0]);
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
-            if (py > 0 && co + 1 < CO) ov_load(co + 1, ov[(co + 1) & 1]);
+            if ((ov_always || py > 0) && co + 1 < CO) ov_load(co + 1, ov[(co + 1) & 1]);
+#ifndef VQVAE_ENDS_NO_TABLES
+            const float bv = b4_u[co], w4d = w4d_u[co];         // the output channel's bias and own weight scale 2^-kw4[co] (wave-uniform)
+#else
             const float bv = bias4 ? bias4[co] : 0.0f;
             const float w4d = h2_dw(hdr4)[co];                  // the output channel's own weight scale 2^-kw4[co] (wave-uniform)
+#endif
             const float d40 = d4[0] * w4d, d41 = d4[1] * w4d;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
