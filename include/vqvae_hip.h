@@ -365,6 +365,22 @@ VQVAE_API int vqvae_vq_kmeans_update_f32(const float *z_e, const int64_t *idx, i
                                          const float *uniforms, int flags, float *codebook, int32_t *counts,
                                          void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* l2-normalisation of rows and its backward (csrc/vq_cosine.hip; its header is the numeric contract): what a cosine-similarity
+ * codebook (ViT-VQGAN, arXiv 2110.04627 section 3.2) puts in front of the quantizer, for encoder outputs and for codes.
+ *     forward:   d = max(||x||, eps) per row (fp64 sum of squares in channel order, fp64 sqrt, rounded to fp32, clamped by
+ *                (d < eps) ? eps : d);  y = x / d (one fp32 division);  denom (N) fp32 out = d
+ *     backward:  t = sum_c y_c g_c in fp64;  grad_x = (g - y t) / d in fp64, rounded once, where d > eps;  g / eps elsewhere
+ *   Rows and layouts are vqvae_vq_forward_f32's: N = B H W rows of D channels, (B,D,H,W) maps, or (N,D) rows with
+ *   VQVAE_VQ_ROWMAJOR (no other flag); a (K, D) codebook is the row-major case B = K, H = W = 1.  No workspace, no host sync, no
+ *   atomics, one launch on `stream`: bit-reproducible, the same bits in either layout.  eps: 1e-12 is torch.nn.functional.normalize's.
+ *   Envelope: 1 <= D <= 256, N <= INT32_MAX.  VQVAE_ERR_UNSUPPORTED outside it, for a pointer that is not 4-byte aligned and for an
+ *   output that overlaps an input (y and x; grad_x and y or grad_y).                                                               */
+VQVAE_API int vqvae_l2norm_forward_f32(const float *x, int64_t B, int D, int H, int W, float eps, int flags,
+                                       float *y, float *denom, vqvae_stream_t stream);
+VQVAE_API int vqvae_l2norm_backward_f32(const float *y, const float *denom, const float *grad_y,
+                                        int64_t B, int D, int H, int W, float eps, int flags,
+                                        float *grad_x, vqvae_stream_t stream);
+
 /* Residual vector quantization (csrc/vq_residual.hip; its header is the numeric contract): Q codebooks E_0 .. E_{Q-1}, each (K, D),
  * quantize the same latent position, stage q what stage q - 1 left over (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ):
  *     r_0 = z;   idx_q = vqvae_vq_forward_f32's indices of r_q against E_q;   r_{q+1} = r_q - E_q[idx_q]

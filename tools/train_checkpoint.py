@@ -11,6 +11,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--kmeans_init [BATCHES]]                      (off by default: k-means start of the codebook)
                                      [--n_quantizers Q [--shared_codebook]]         (off by default: residual quantization, Q stages)
                                      [--rotation_trick]                             (off by default: the rotation-trick gradient)
+                                     [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -62,8 +63,12 @@ def main():
     p.add_argument("--shared_codebook", action="store_true", default=argparse.SUPPRESS)
     # opt-in rotation-trick gradient through the quantizer (rotation_trick=True); absent unless given, like the EMA options
     p.add_argument("--rotation_trick", action="store_true", default=argparse.SUPPRESS)
+    # opt-in cosine-similarity codebook (cosine_sim=True: l2-normalised rows and codes); absent unless given, like the EMA options
+    p.add_argument("--cosine_sim", action="store_true", default=argparse.SUPPRESS)
     args = p.parse_args()
     ema_kw = {}
+    if hasattr(args, "cosine_sim"):
+        ema_kw["cosine_sim"] = True
     if hasattr(args, "rotation_trick"):
         ema_kw["rotation_trick"] = True
     if hasattr(args, "n_quantizers"):

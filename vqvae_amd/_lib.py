@@ -92,6 +92,8 @@ SIGNATURES = {
     "vqvae_vq_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vqvae_vq_kmeans_seed_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "vqvae_vq_kmeans_update_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_l2norm_forward_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "vqvae_l2norm_backward_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "vqvae_vq_residual_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
     "vqvae_vq_residual_forward_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

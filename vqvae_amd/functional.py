@@ -103,8 +103,9 @@ def vq_onehot(idx: torch.Tensor, K: int) -> torch.Tensor:
     return out
 
 
-def vq_decode_indices(idx: torch.Tensor, codebook: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
-    """indices -> z_q (B,D,H,W) (visualization.ipynb:358-365)."""
+def vq_decode_indices(idx: torch.Tensor, codebook: torch.Tensor, B: int, H: int, W: int, *, validate: bool = True) -> torch.Tensor:
+    """indices -> z_q (B,D,H,W) (visualization.ipynb:358-365).  validate=False: no range check (for indices that come from the
+    quantizer; the kernel never reads outside the codebook, a bad index shows as NaN rows)."""
     _check_dev("idx", idx, torch.int64)
     _check_dev("codebook", codebook)
     idx = idx.contiguous()
@@ -114,7 +115,7 @@ def vq_decode_indices(idx: torch.Tensor, codebook: torch.Tensor, B: int, H: int,
         raise ValueError("idx must hold B*H*W indices")
     # the reference's embedding lookup raises on an out-of-range index; the kernel cannot (it writes NaN), so the
     # check is done here -- one host sync, skipped while a graph is being captured
-    if not torch.cuda.is_current_stream_capturing():
+    if validate and not torch.cuda.is_current_stream_capturing():
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= K:
             raise IndexError(f"index out of range in decode_indices: [{lo}, {hi}] not within [0, {K})")
@@ -268,6 +269,52 @@ def vq_kmeans(z_e: torch.Tensor, K: int, iters: int = 10, *, generator: torch.Ge
             u = torch.rand(K, device=dev, generator=generator) if reseed_empty else None
             counts = vq_kmeans_update(z_e, idx, codebook, uniforms=u, rowmajor=rowmajor, workspace=ws)
     return codebook, counts
+
+
+# ---- l2-normalised rows: the cosine-similarity codebook (csrc/vq_cosine.hip) -----------------------------------------------------
+
+def _l2norm_dims(name, x, rowmajor):
+    """-> (B, D, H, W, rowmajor) of a 4-D map in the quantizer's layouts, or of a 2-D (K, D) tensor as K row-major rows"""
+    _check_dev(name, x)
+    if x.dim() == 2:
+        return x.shape[0], x.shape[1], 1, 1, True
+    if x.dim() != 4:
+        raise ValueError(f"{name} must be a 4-D map or a 2-D (K, D) tensor")
+    if rowmajor:
+        return x.shape[0], x.shape[3], x.shape[1], x.shape[2], True
+    return x.shape[0], x.shape[1], x.shape[2], x.shape[3], False
+
+
+def l2norm_rows(x: torch.Tensor, *, rowmajor: bool = False, eps: float = 1e-12):
+    """Every row divided by its l2 norm (vqvae_l2norm_forward_f32; torch.nn.functional.normalize along the channels):
+    -> (y like x, denom (N,) fp32 = max(||row||, eps)).  x: (B,D,H,W), (B,H,W,D) when rowmajor, or a 2-D (K, D) tensor -- a codebook,
+    rows as they stand.  The numeric contract is the header of csrc/vq_cosine.hip."""
+    B, D, H, W, rm = _l2norm_dims("x", x, rowmajor)
+    x = x.contiguous()
+    dev = x.device
+    with torch.cuda.device(dev):
+        y = torch.empty_like(x)
+        denom = torch.empty((B * H * W,), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().vqvae_l2norm_forward_f32(x.data_ptr(), B, D, H, W, float(eps), VQ_ROWMAJOR if rm else 0,
+                                                        y.data_ptr(), denom.data_ptr(), _stream_ptr(x)))
+    return y, denom
+
+
+def l2norm_rows_backward(y: torch.Tensor, denom: torch.Tensor, grad_y: torch.Tensor, *, rowmajor: bool = False,
+                         eps: float = 1e-12) -> torch.Tensor:
+    """grad_x of l2norm_rows from its outputs (y, denom) and grad_y (vqvae_l2norm_backward_f32): (g - y (y . g)) / denom per row, and
+    g / eps on rows where the clamp was active.  eps must be the forward's."""
+    B, D, H, W, rm = _l2norm_dims("y", y, rowmajor)
+    _check_dev("denom", denom)
+    _check_dev("grad_y", grad_y)
+    if grad_y.shape != y.shape or denom.numel() != B * H * W:
+        raise ValueError("shape mismatch between y, denom and grad_y")
+    y, denom, grad_y = y.contiguous(), denom.contiguous(), grad_y.contiguous()
+    with torch.cuda.device(y.device):
+        grad_x = torch.empty_like(y)
+        _lib.check(_lib.load().vqvae_l2norm_backward_f32(y.data_ptr(), denom.data_ptr(), grad_y.data_ptr(), B, D, H, W, float(eps),
+                                                         VQ_ROWMAJOR if rm else 0, grad_x.data_ptr(), _stream_ptr(y)))
+    return grad_x
 
 
 # ---- residual vector quantization (csrc/vq_residual.hip) -------------------------------------------------------------------------

@@ -131,7 +131,7 @@ class VectorQuantizer(nn.Module):
 
     LAZY_MIN_ENCODINGS = True          # forward()'s fourth output: LazyOneHot (the (N, K) one-hot on first use) or the tensor itself
 
-    def __init__(self, n_e, e_dim, beta, *, rotation_trick=False):
+    def __init__(self, n_e, e_dim, beta, *, rotation_trick=False, cosine_sim=False):
         super().__init__()
         self.n_e = n_e
         self.e_dim = e_dim
@@ -139,6 +139,10 @@ class VectorQuantizer(nn.Module):
         # opt-in: the decoder's gradient reaches the encoder through the rotation trick (arXiv 2410.06424; csrc/vq_rotation.hip)
         # instead of unchanged.  A plain attribute: no parameter, no buffer, no state_dict key; the forward is the same.
         self.rotation_trick = bool(rotation_trick)
+        # opt-in: the cosine-similarity codebook (ViT-VQGAN, arXiv 2110.04627 section 3.2; csrc/vq_cosine.hip): z and the codes are
+        # l2-normalised, then quantized exactly as without the option.  A plain attribute too; `embedding.weight` is stored
+        # un-normalised and normalised on use.
+        self.cosine_sim = bool(cosine_sim)
         self.embedding = nn.Embedding(self.n_e, self.e_dim)
         self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)   # quantizer.py:27
 
@@ -148,13 +152,40 @@ class VectorQuantizer(nn.Module):
         such a write.  `load_state_dict` and `.to()/.cuda()` call it for you."""
         for slot in _cache.side(self).get("ws", {}).values():
             slot[1] = None
+        _cache.drop(self, "cosine_codebook")
+
+    def _codebook_key(self):
+        w = self.embedding.weight
+        # (with cosine_sim the prepared image is the normalised codebook's: flipping the attribute re-keys)
+        return (w.data_ptr(), w._version, w.device) + (("cosine",) if self.cosine_sim else ())
+
+    def normalized_codebook(self):
+        """The l2-normalised codebook (K, D) that a cosine_sim quantizer searches and decodes with, without grad: computed once per
+        version of `embedding.weight` (keyed as the prepared codebook image is; invalidate() drops it)."""
+        w = self.embedding.weight
+        key = (w.data_ptr(), w._version, w.device)
+        hit = _cache.side(self).get("cosine_codebook")
+        if hit is None or hit[0] != key:
+            hit = (key, F_hip.l2norm_rows(w.detach())[0])
+            _cache.side(self)["cosine_codebook"] = hit
+        return hit[1]
+
+    def _cosine_operands(self, z, rowmajor):
+        """-> (z^, E^): the rows the quantizer runs on with cosine_sim.  While a graph is recorded both go through L2NormRows (the
+        gradients of z and of the codebook pass through the normalisation's backward); otherwise functional.l2norm_rows and the
+        cached E^."""
+        w = self.embedding.weight
+        if torch.is_grad_enabled() and (z.requires_grad or w.requires_grad):
+            from .training import L2NormRows
+            return L2NormRows.apply(z, rowmajor), (L2NormRows.apply(w) if w.requires_grad else self.normalized_codebook())
+        return F_hip.l2norm_rows(z, rowmajor=rowmajor)[0], self.normalized_codebook()
 
     def _workspace(self):
         """-> (workspace, prepared, key, slot): workspace holding the codebook's LDS images and the per-call scratch,
         ONE PER (device, stream) -- two forwards of one model on different streams must not share scratch -- re-prepared
         only when the embedding tensor changes.  The caller stores `key` in slot[1] once the launch has succeeded."""
         w = self.embedding.weight
-        key = (w.data_ptr(), w._version, w.device)
+        key = self._codebook_key()
         table = _cache.side(self).setdefault("ws", {})
         skey = (str(w.device), torch.cuda.current_stream(w.device).cuda_stream if w.is_cuda else 0)
         slot = _cache.lru_get(table, skey)
@@ -169,6 +200,8 @@ class VectorQuantizer(nn.Module):
         ws, prepared, key, slot = self._workspace()
         if not prepared:
             slot[1] = None                                       # a failed launch must not leave a stale "prepared" image
+        if self.cosine_sim:
+            z, w = self._cosine_operands(z, rowmajor)            # from here on: today's quantizer, on the unit rows
         if torch.is_grad_enabled() and (z.requires_grad or w.requires_grad):
             from .training import VQStraightThrough          # HIP forward + HIP backward
             out = VQStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared, self.rotation_trick)
@@ -187,8 +220,11 @@ class VectorQuantizer(nn.Module):
         """Opt-in data-dependent start: the codebook becomes k-means (k-means++ seeding and `iters` Lloyd rounds on the HIP kernels,
         functional.vq_kmeans) of the rows of z -- encoder outputs (B,D,H,W), or (B,H,W,D) when rowmajor -- instead of
         uniform(-1/K, 1/K).  Written into `embedding.weight` by an in-place op: its `_version` moves, so the prepared and packed
-        codebook images re-key.  -> (codebook, counts of the last assignment)."""
+        codebook images re-key.  cosine_sim: k-means of the l2-normalised rows (spherical k-means; the centroids are stored as
+        they come and normalised on use).  -> (codebook, counts of the last assignment)."""
         _need_hip_f32(z, "init_codebook_")
+        if self.cosine_sim:
+            z = F_hip.l2norm_rows(z.detach(), rowmajor=rowmajor)[0]
         codebook, counts = F_hip.vq_kmeans(z.detach(), self.n_e, iters, generator=generator, rowmajor=rowmajor)
         self.embedding.weight.copy_(codebook)
         return codebook, counts
@@ -214,8 +250,9 @@ class VectorQuantizerEMA(VectorQuantizer):
     `generator`, or the default CUDA generator, on every update).  None: no restart.  Under data parallelism each replica updates
     from its own shard; the statistics are not merged across ranks."""
 
-    def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, rotation_trick=False):
-        super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick)
+    def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, rotation_trick=False,
+                 cosine_sim=False):
+        super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim)
         self.decay = float(decay)
         self.eps = float(eps)
         self.restart_threshold = None if restart_threshold is None else float(restart_threshold)
@@ -255,11 +292,14 @@ class VectorQuantizerEMA(VectorQuantizer):
 
     def quantize(self, z, *, rowmajor=False, want_zq=True):
         """-> (beta * mse, z_q, perplexity, min_encoding_indices, hist) against the codebook as it was on entry; then, in training
-        mode, one EMA update of the codebook."""
+        mode, one EMA update of the codebook.  cosine_sim: all of it on the l2-normalised rows z^ and codes E^ -- the update runs
+        from z^ (restart rows are rows of z^), `embedding.weight` holds ema_w / N_k as without the option and is normalised on use."""
         w = self.embedding.weight
         ws, prepared, key, slot = self._workspace()
         if not prepared:
             slot[1] = None
+        if self.cosine_sim:
+            z, w = self._cosine_operands(z, rowmajor)
         if torch.is_grad_enabled() and z.requires_grad:
             from .training import VQEMAStraightThrough      # HIP forward + HIP commitment-only backward
             out = VQEMAStraightThrough.apply(z, w, self.beta, rowmajor, ws, prepared, self.rotation_trick)
@@ -472,8 +512,11 @@ class VQVAE(nn.Module):
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
-                 shared_codebook=False, rotation_trick=False):
+                 shared_codebook=False, rotation_trick=False, cosine_sim=False):
         super().__init__()
+        if n_quantizers > 1 and cosine_sim:
+            raise ValueError("cosine_sim is the one-stage quantizers' option: a per-stage normalisation of residual quantization "
+                             "(n_quantizers > 1) does not exist")
         if n_quantizers > 1 and rotation_trick:
             raise ValueError("rotation_trick is the one-stage quantizers' option: residual quantization (n_quantizers > 1) has none")
         if n_quantizers < 1:
@@ -492,11 +535,13 @@ class VQVAE(nn.Module):
         elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
-            self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta, rotation_trick=rotation_trick)
+            self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta, rotation_trick=rotation_trick,
+                                                       cosine_sim=cosine_sim)
         else:
             # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
             self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,
-                                                          restart_threshold=restart_threshold, rotation_trick=rotation_trick)
+                                                          restart_threshold=restart_threshold, rotation_trick=rotation_trick,
+                                                          cosine_sim=cosine_sim)
         self.decoder = Decoder(embedding_dim, h_dim, n_res_layers, res_h_dim)
         if save_img_embedding_map:
             self.img_to_embedding_map = {i: [] for i in range(n_embeddings)}
@@ -733,15 +778,23 @@ class VQVAE(nn.Module):
             embedding_loss, z_q, perplexity, _, _ = vq(z_e, rowmajor=True)
             return embedding_loss, C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True), perplexity.mean()
         ema = isinstance(vq, VectorQuantizerEMA)
-        # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it)
+        # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it; so does a
+        # cosine_sim quantizer, whose rows are normalised between the encoder and the search -- the fused whole-path entries
+        # quantize z_e as it stands)
         if (C_hip.get_conv_backend() == "hip" and not verbose and x.is_cuda and x.dtype == torch.float32
-                and not (ema and vq.training)):
+                and not (ema and vq.training) and not vq.cosine_sim):
             if ema:
                 mse, x_hat, perplexity = self._forward_c(x)
                 return mse * vq.beta, x_hat, perplexity
             return self._forward_c(x)                 # one ctypes call: vqvae_forward_f32
         # encoder + 1x1 pre-quantisation conv, activations kept row-major (B,H,W,C)
         z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+        if vq.cosine_sim and not verbose:
+            # Without a graph nothing needs the straight-through form z^ + (e^ - z^), whose value is the code e^ up to one rounding:
+            # the decoder takes the rows of E^ themselves, exactly as decode_indices does, so decode_indices(encode(x)) is this
+            # x_hat bit for bit.  (The training forward decodes z^ + (e^ - z^): the gradient needs it.)
+            embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
+            return embedding_loss, self._decode_codes(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2], validate=False), perplexity
         embedding_loss, z_q, perplexity, _, _ = self.vector_quantization.quantize(z_e, rowmajor=True)
         x_hat = C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
         if verbose:                                                    # models/vqvae.py:38-42
@@ -786,7 +839,11 @@ class VQVAE(nn.Module):
             # (n_quantizers, N) int64, stage-major: the per-layer encoder, then the residual stages (indices only)
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
-        if C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32:
+        if (C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32
+                or self.vector_quantization.cosine_sim):
+            # (cosine_sim: encoder -> l2norm_rows -> index-only quantizer, the training forward's indices bit for bit)
+            if self.vector_quantization.cosine_sim and C_hip.get_conv_backend() == "hip":
+                _need_hip_f32(x, "VQVAE.encode")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             # (VectorQuantizer's quantize: an EMA quantizer in training mode must not update from encode())
             _, _, _, idx, _ = VectorQuantizer.quantize(self.vector_quantization, z_e, rowmajor=True, want_zq=False)
@@ -811,6 +868,15 @@ class VQVAE(nn.Module):
             slot[1] = key
         return idx
 
+    def _decode_codes(self, idx, B, H, W, validate):
+        """cosine_sim: rows of the normalised codebook (vq_decode_indices(idx, E^); vqvae_decode_f32 would gather un-normalised
+        codes), then the decoder.  The no-grad forward and decode_indices both end here.  validate: raise on an index outside
+        [0, K) (one host sync)."""
+        from . import conv as C_hip
+        z_q = F_hip.vq_decode_indices(idx.contiguous().view(-1).to(torch.int64), self.vector_quantization.normalized_codebook(),
+                                      B, H, W, validate=validate)
+        return C_hip.decoder_forward(self.decoder, z_q.detach(), rowmajor_in=False)
+
     @torch.no_grad()
     def decode_indices(self, idx, B, H, W, fwd_flags=None, validate=True):
         """indices -> x_hat (visualization.ipynb:358-365 generate_samples) as ONE call (vqvae_decode_f32): on the default shapes
@@ -833,6 +899,8 @@ class VQVAE(nn.Module):
             return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
         if idx.numel() != B * H * W:
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
+        if self.vector_quantization.cosine_sim:
+            return self._decode_codes(idx, B, H, W, validate=validate)
         if C_hip.get_conv_backend() != "hip" or not idx.is_cuda:
             z_q = F_hip.vq_decode_indices(idx, self.vector_quantization.embedding.weight.detach(), B, H, W)
             return self.decoder(z_q)

@@ -132,6 +132,24 @@ class VQEMAStraightThrough(torch.autograd.Function):
         return gz, None, None, None, None, None, None
 
 
+class L2NormRows(torch.autograd.Function):
+    """x -> x / max(||row||, eps), forward and backward on the HIP kernels (functional.l2norm_rows / l2norm_rows_backward;
+    csrc/vq_cosine.hip): what the cosine-similarity codebook puts in front of the quantizer, for z_e and for the codebook.
+    apply(x, rowmajor=False, eps=1e-12); x: a 4-D map in the quantizer's layouts or a 2-D (K, D) tensor."""
+
+    @staticmethod
+    def forward(ctx, x, rowmajor=False, eps=1e-12):
+        y, denom = F_hip.l2norm_rows(x.detach(), rowmajor=rowmajor, eps=eps)
+        ctx.save_for_backward(y, denom)
+        ctx.rowmajor, ctx.eps = rowmajor, eps
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, denom = ctx.saved_tensors
+        return F_hip.l2norm_rows_backward(y, denom, g, rowmajor=ctx.rowmajor, eps=ctx.eps), None, None
+
+
 class _StepLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_hat, x, embedding_loss, perplexity, inv_var):
