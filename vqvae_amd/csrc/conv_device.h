@@ -273,10 +273,61 @@ __device__ __forceinline__ void prod3x2(const u32x4 &s1, const u32x4 &s2, const 
     accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(HF(t1), HF(w1), accB, 0, 0, 0);
 #undef HF
 }
-// largest value of the wave -> the power of two that puts it into [2^14, 2^15) (0 for an all-zero or non-finite image)
-__device__ __forceinline__ int wave_scale_exp(float m) {
+// A wave-wide butterfly (partner = lane ^ o, o = 32 .. 1) with the partner named IN the instruction: v_permlane32_swap_b32 for
+// o = 32, ds_swizzle_b32 (xor inside 32 lanes) below.  HIP's __shfl_xor is a ds_bpermute_b32, and its six lane-derived addresses
+// ((lane ^ o) << 2) are computed once at kernel entry and kept for every later reduction: in conv_res_pair8_h2_kernel they were the
+// values behind 57 of the forward instance's 76 scratch loads (profiles/mid_stream_ab.txt).  Same partners, same order, a
+// commutative operation per step: the same bits.
+template <int O>
+__device__ __forceinline__ unsigned swz_xor(unsigned v) {
+    static_assert(O == 16 || O == 8 || O == 4 || O == 2 || O == 1, "ds_swizzle's bit-mask mode stays inside 32 lanes");
+    return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (O << 10) | 0x1f);
+}
+template <int O>
+__device__ __forceinline__ double swz_xor_f64(double d) {              // (the two halves of lane ^ O's double)
+    const unsigned long long v = __builtin_bit_cast(unsigned long long, d);
+    return __builtin_bit_cast(double, ((unsigned long long)swz_xor<O>((unsigned)(v >> 32)) << 32) | swz_xor<O>((unsigned)v));
+}
+template <bool SWZ>
+__device__ __forceinline__ float wave_max_all(float m) {
+    if constexpr (SWZ) {
+        // (both results of the swap hold, for every lane, its own value and its partner's: one of each)
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+        m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+        m = fmaxf(m, __uint_as_float(swz_xor<16>(__float_as_uint(m))));
+        m = fmaxf(m, __uint_as_float(swz_xor<8>(__float_as_uint(m))));
+        m = fmaxf(m, __uint_as_float(swz_xor<4>(__float_as_uint(m))));
+        m = fmaxf(m, __uint_as_float(swz_xor<2>(__float_as_uint(m))));
+        m = fmaxf(m, __uint_as_float(swz_xor<1>(__float_as_uint(m))));
+    } else {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    }
+    return m;
+}
+// the sum of a double over the wave, in the butterfly's order (every lane ends with the same bits as with __shfl_xor)
+template <bool SWZ>
+__device__ __forceinline__ double wave_sum_all(double d) {
+    if constexpr (SWZ) {
+        const unsigned long long u = __builtin_bit_cast(unsigned long long, d);
+        const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)u, (unsigned)u, false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(u >> 32), (unsigned)(u >> 32), false, false);
+        d = __builtin_bit_cast(double, ((unsigned long long)hi[0] << 32) | lo[0]) + __builtin_bit_cast(double, ((unsigned long long)hi[1] << 32) | lo[1]);
+        d += swz_xor_f64<16>(d);
+        d += swz_xor_f64<8>(d);
+        d += swz_xor_f64<4>(d);
+        d += swz_xor_f64<2>(d);
+        d += swz_xor_f64<1>(d);
+    } else {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    }
+    return d;
+}
+// largest value of the wave -> the power of two that puts it into [2^14, 2^15) (0 for an all-zero or non-finite image)
+template <bool SWZ = false>
+__device__ __forceinline__ int wave_scale_exp(float m) {
+    m = wave_max_all<SWZ>(m);
     int e = 15;
     if (m > 0.0f && m < 3.0e38f) (void)__builtin_frexpf(m, &e);
     e = 15 - e;
@@ -295,9 +346,9 @@ __device__ __forceinline__ void publish_amax(int *out_amax, long long img, float
 
 // The same where exactly ONE wave ever produces image `img` (the one-wave-per-image kernels): a plain store, and the array
 // needs no -1 fill in front of the launch.
+template <bool SWZ = false>
 __device__ __forceinline__ void publish_amax_exclusive(int *out_amax, long long img, float om, int lane) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) om = fmaxf(om, __shfl_xor(om, o));
+    om = wave_max_all<SWZ>(om);
     if (lane == 0) out_amax[img] = __float_as_int(om);
 }
 

@@ -3,6 +3,15 @@
 #include "conv_host.h"
 
 namespace vqvae {
+// The butterfly reductions of this file's kernels (wave_scale_exp, publish_amax_exclusive, the loss partial, enc_front8's image
+// maximum) exchange through v_permlane32_swap / ds_swizzle, not through __shfl_xor's ds_bpermute and its six address registers
+// (conv_device.h: wave_max_all).  The quantizer's own ds_bpermutes (vq_unit.h: gather addresses, task tables) are not butterflies
+// and stay.  -DVQVAE_MID_SHFL_BPERMUTE restores __shfl_xor.
+#ifndef VQVAE_MID_SHFL_BPERMUTE
+constexpr bool kSwz = true;
+#else
+constexpr bool kSwz = false;
+#endif
 // ---------------------------------------------------------------------------
 // A 3x3 conv / 3x3 conv-transpose (stride 1) IN FRONT of a residual pair, all in one kernel (8x8 maps, two-term fp16
 // products): models/encoder.py:35-38 (conv 3x3 + ReLU -> ResidualStack) and models/decoder.py:28-30 (conv-transpose 3x3 ->
@@ -232,7 +241,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
             load_raw0(cc);
             fold_raw();
         }
-        const int kx = wave_scale_exp(img_ok ? m : 0.0f);
+        const int kx = wave_scale_exp<kSwz>(img_ok ? m : 0.0f);
         const float xs = __builtin_ldexpf(1.0f, kx), d0 = __builtin_ldexpf(1.0f, -kx);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -389,7 +398,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     // measured; a two-iteration loop around the body instead spills 275 registers
     auto layer = [&](auto LT, bool relu_after) __attribute__((always_inline)) {
         constexpr int LI = decltype(LT)::value;                // 0 or 1: stages 9 LI ..
-        const int kx = wave_scale_exp(img_ok ? ymax : 0.0f);
+        const int kx = wave_scale_exp<kSwz>(img_ok ? ymax : 0.0f);
         const float xscale = __builtin_ldexpf(1.0f, kx), d1 = __builtin_ldexpf(1.0f, -kx);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -428,7 +437,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                 for (int q = 0; q < 4; q += 2)
                     SCALE2_BIAS_RELU2(acc1[mt][4 * g + q], acc1[mt][4 * g + q + 1], dv[q], dv[q + 1], 0.0f, 0.0f, m);
         }
-        const int kh = wave_scale_exp(m);
+        const int kh = wave_scale_exp<kSwz>(m);
         const float hscale = __builtin_ldexpf(1.0f, kh), d2 = __builtin_ldexpf(1.0f, -kh);
         u32x4 H1[MT][2], Hb[MT][2];
 #pragma unroll
@@ -489,7 +498,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     };
     layer(std::integral_constant<int, 0>{}, true);         // the second layer's in-place ReLU is applied by its producer
     layer(std::integral_constant<int, 1>{}, relu_out);
-    if (out_amax && img_ok) publish_amax_exclusive(out_amax, img, ymax, lane);
+    if (out_amax && img_ok) publish_amax_exclusive<kSwz>(out_amax, img, ymax, lane);
 
     // one transposed 32-pixel x 32-channel tile -> rows of `ld` floats at dst (pixel-major), whole 128-byte lines per
     // eight lanes: registers -> wave-private LDS tile [pixel][36] -> linear 16-byte reads
@@ -507,7 +516,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
     };
     const long long wbase = img * PX;
     if constexpr (NT3 > 0) {
-        const int kx3 = wave_scale_exp(img_ok ? ymax : 0.0f);
+        const int kx3 = wave_scale_exp<kSwz>(img_ok ? ymax : 0.0f);
         const float xs3 = __builtin_ldexpf(1.0f, kx3), d3 = __builtin_ldexpf(1.0f, -kx3);
         f32x16 acc3[MT][NT3];
 #pragma unroll
@@ -703,8 +712,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                                              vq.idx + (size_t)(img_ok ? img : 0) * PX, vq_hist_s);
             // loss partial and histogram of the workgroup (fixed order: run-to-run bitwise loss / perplexity)
             double dacc = img_ok ? (double)sacc : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o);
+            dacc = wave_sum_all<kSwz>(dacc);
             if (lane == 0) vq_red_s[wave_u] = dacc;
             __syncthreads();                        // (DECHEAD: and every wave has its z_q rows out of the weight buffers)
             if (tid == 0) {
@@ -736,7 +744,7 @@ __global__ __launch_bounds__(CRP_NW * 64, CRP_MINW) void conv_res_pair8_h2_kerne
                 front(std::true_type{});
                 layer(std::integral_constant<int, 0>{}, true);
                 layer(std::integral_constant<int, 1>{}, (dh.flags & kFlagReluOut) != 0);
-                if (dh.out_amax && img_ok) publish_amax_exclusive(dh.out_amax, img, ymax, lane);
+                if (dh.out_amax && img_ok) publish_amax_exclusive<kSwz>(dh.out_amax, img, ymax, lane);
                 if (img_ok) {
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
@@ -880,13 +888,12 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
         const f32x4 v = *reinterpret_cast<const f32x4 *>(ximg + 4 * lane + 256 * j);
         xm = fmaxf(xm, fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w))));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xm = fmaxf(xm, __shfl_xor(xm, o));
-    const int kx0 = wave_scale_exp(img_ok ? xm : 0.0f);
+    xm = wave_max_all<kSwz>(xm);
+    const int kx0 = wave_scale_exp<kSwz>(img_ok ? xm : 0.0f);
     const float xs0 = __builtin_ldexpf(1.0f, kx0), d0 = __builtin_ldexpf(1.0f, -kx0);       // (x the weight rows' 2^-kw[c] at the use)
     float bm = bias0 ? __builtin_fabsf(bias0[lane]) : 0.0f;                                 // C0 = 64 channels
     const float bound = (__int_as_float(hdr0[1]) * xm + bm) * 1.0001f;
-    const int k1 = wave_scale_exp(img_ok ? bound : 0.0f);                                     // (reduces bm over the wave)
+    const int k1 = wave_scale_exp<kSwz>(img_ok ? bound : 0.0f);                                     // (reduces bm over the wave)
     const float xs1 = __builtin_ldexpf(1.0f, k1), d2 = __builtin_ldexpf(1.0f, -k1);
 
     f32x16 Y[MT][NT];
@@ -1066,7 +1073,7 @@ __global__ __launch_bounds__(256, EF_MINW) void enc_front8_h2_kernel(const float
                 }
             }
         }
-    if (out_amax && img_ok) publish_amax_exclusive(out_amax, img, ymax, lane);
+    if (out_amax && img_ok) publish_amax_exclusive<kSwz>(out_amax, img, ymax, lane);
     (void)C0;
 }
 
@@ -1199,7 +1206,7 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
         for (int j = 0; j < 8; ++j)
             m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(raw[j].x), __builtin_fabsf(raw[j].y)), fmaxf(__builtin_fabsf(raw[j].z), __builtin_fabsf(raw[j].w))));
     }
-    const int kx = wave_scale_exp(img_ok ? m : 0.0f);
+    const int kx = wave_scale_exp<kSwz>(img_ok ? m : 0.0f);
     const float xs = __builtin_ldexpf(1.0f, kx), d1 = __builtin_ldexpf(1.0f, -kx);      // (x the weight rows' 2^-kw[c] at the use)
     load_raw(0);
 
@@ -1324,7 +1331,7 @@ __global__ __launch_bounds__(256, DT_MINW) void dec_tail8_h2_kernel(const float 
                         for (int q = 0; q < 4; q += 2)
                             SCALE2_BIAS_RELU2(acc[px][mt][nt][4 * g + q], acc[px][mt][nt][4 * g + q + 1], dv[q], dv[q + 1], bv[q], bv[q + 1], um);
                 }
-            const int ku = wave_scale_exp(img_ok ? um : 0.0f);
+            const int ku = wave_scale_exp<kSwz>(img_ok ? um : 0.0f);
             const float us = __builtin_ldexpf(1.0f, ku);
             d4[px] = __builtin_ldexpf(1.0f, -ku);
             u32x4 U1[MT][NT][2], U2[MT][NT][2];
