@@ -381,6 +381,33 @@ VQVAE_API int vqvae_l2norm_backward_f32(const float *y, const float *denom, cons
                                         int64_t B, int D, int H, int W, float eps, int flags,
                                         float *grad_x, vqvae_stream_t stream);
 
+/* Finite scalar quantization (csrc/vq_fsq.hip; its header is the numeric contract): the quantizer without a learned codebook
+ * (arXiv 2309.15505; vector-quantize-pytorch's FSQ and its `bound`).  A row is projected to d = n_levels channels (w_in (d, D), b_in
+ * (d)), channel j is bounded with tanh and rounded to one of levels[j] values, and projected back (w_out (D, d), b_out (D)); the
+ * projections run inside the kernels, all in fp64 with one rounding per output.  The implicit codebook has K = prod levels[j] entries.
+ *     forward:   z_q (may be NULL; then w_out / b_out may be too), idx (N) int64 in [0, K), first level least significant;
+ *                hist (K) int32 counts (may be NULL), perplexity = exp(-sum p log(p + 1e-10)) (may be NULL, needs hist)
+ *     decode:    idx -> z_q; an index outside [0, K) writes a NaN row and reads nothing out of range
+ *     backward:  grad_zq -> grad_z (straight-through rounding, through tanh and both projections) and the four parameter gradients,
+ *                fp64 sums over the rows in an order that depends on N alone (blocks of 256 rows in row order, then the blocks in
+ *                order): the same bits in both layouts and in every run.  Every gradient pointer may be NULL (not all); `workspace`
+ *                (vqvae_fsq_backward_workspace_bytes; 0 = outside the envelope) is needed for the parameter gradients only.
+ *   `levels` is a HOST array, read during the call.  Rows and layouts are vqvae_vq_forward_f32's; the only flag is
+ *   VQVAE_VQ_ROWMAJOR.  No host sync, no allocation, every launch on `stream` in one chain: capturable.
+ *   Envelope: 1 <= n_levels <= 8, 2 <= levels[j] <= 256, K <= 65536, 1 <= D <= 256, N <= INT32_MAX.  VQVAE_ERR_UNSUPPORTED outside
+ *   it, for a pointer that is not 4-byte aligned (idx, workspace: 8-byte) and for an output that overlaps an input.                */
+VQVAE_API int vqvae_fsq_forward_f32(const float *z_e, const float *w_in, const float *b_in, const float *w_out, const float *b_out,
+                                    const int *levels, int n_levels, int64_t B, int D, int H, int W, int flags,
+                                    float *z_q, int64_t *idx, int32_t *hist, float *perplexity, vqvae_stream_t stream);
+VQVAE_API int vqvae_fsq_decode_indices_f32(const int64_t *idx, const float *w_out, const float *b_out, const int *levels,
+                                           int n_levels, int64_t B, int D, int H, int W, int flags, float *z_q,
+                                           vqvae_stream_t stream);
+VQVAE_API size_t vqvae_fsq_backward_workspace_bytes(int64_t N, int D, int n_levels);
+VQVAE_API int vqvae_fsq_backward_f32(const float *z_e, const float *grad_zq, const float *w_in, const float *b_in,
+                                     const float *w_out, const int *levels, int n_levels, int64_t B, int D, int H, int W, int flags,
+                                     float *grad_z, float *grad_w_in, float *grad_b_in, float *grad_w_out, float *grad_b_out,
+                                     void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* Residual vector quantization (csrc/vq_residual.hip; its header is the numeric contract): Q codebooks E_0 .. E_{Q-1}, each (K, D),
  * quantize the same latent position, stage q what stage q - 1 left over (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ):
  *     r_0 = z;   idx_q = vqvae_vq_forward_f32's indices of r_q against E_q;   r_{q+1} = r_q - E_q[idx_q]

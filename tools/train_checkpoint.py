@@ -12,6 +12,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--n_quantizers Q [--shared_codebook]]         (off by default: residual quantization, Q stages)
                                      [--rotation_trick]                             (off by default: the rotation-trick gradient)
                                      [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
+                                     [--fsq_levels 8,5,5,5 --n_embeddings 1000]     (off by default: finite scalar quantization)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -65,8 +66,12 @@ def main():
     p.add_argument("--rotation_trick", action="store_true", default=argparse.SUPPRESS)
     # opt-in cosine-similarity codebook (cosine_sim=True: l2-normalised rows and codes); absent unless given, like the EMA options
     p.add_argument("--cosine_sim", action="store_true", default=argparse.SUPPRESS)
+    # opt-in finite scalar quantization (fsq_levels=(8, 5, 5, 5): no codebook; --n_embeddings must be the levels' product); absent unless given
+    p.add_argument("--fsq_levels", type=lambda v: tuple(int(l) for l in v.split(",")), default=argparse.SUPPRESS, metavar="L0,L1,..")
     args = p.parse_args()
     ema_kw = {}
+    if hasattr(args, "fsq_levels"):
+        ema_kw["fsq_levels"] = args.fsq_levels
     if hasattr(args, "cosine_sim"):
         ema_kw["cosine_sim"] = True
     if hasattr(args, "rotation_trick"):

@@ -423,3 +423,92 @@ def vq_residual_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, 
             idx.data_ptr(), _ptr_array(books), B, D, H, W, K, Q, (VQ_ROWMAJOR if rowmajor else 0) | (VQ_RESIDUAL_SHARED if shared else 0),
             out.data_ptr(), _stream_ptr(idx)))
     return out
+
+
+# ---- finite scalar quantization (csrc/vq_fsq.hip) --------------------------------------------------------------------------------
+
+def _fsq_levels(levels):
+    """-> (levels tuple, the HOST int array the entries read during the call, K); ValueError outside the kernels' envelope"""
+    import ctypes
+    lv = tuple(int(l) for l in levels)
+    K = 1
+    for l in lv:
+        K *= l
+    if not 1 <= len(lv) <= 8 or any(not 2 <= l <= 256 for l in lv) or K > 65536:
+        raise ValueError(f"FSQ levels {lv}: 1 to 8 levels, each in [2, 256], with a product of at most 65536")
+    return lv, (ctypes.c_int * len(lv))(*lv), K
+
+
+def _fsq_params(D, d, **params):
+    """contiguous fp32 device tensors of nn.Linear's shapes for the names given: w_in (d, D), b_in (d), w_out (D, d), b_out (D)"""
+    shapes = {"w_in": (d, D), "b_in": (d,), "w_out": (D, d), "b_out": (D,)}
+    out = []
+    for name, t in params.items():
+        _check_dev(name, t)
+        if tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{name} must be {shapes[name]}, got {tuple(t.shape)}")
+        out.append(t.contiguous())
+    return out
+
+
+def fsq_forward(z_e: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, levels, *,
+                rowmajor: bool = False, want_zq: bool = True, want_hist: bool = True):
+    """Finite scalar quantization (vqvae_fsq_forward_f32; arXiv 2309.15505): rows of z_e -> project_in -> tanh bound -> round to
+    levels[j] values per channel -> project_out, all inside one kernel.  z_e: (B,D,H,W), or (B,H,W,D) when rowmajor; w_in (d, D),
+    b_in (d), w_out (D, d), b_out (D) as nn.Linear holds them.
+    -> (z_q like z_e or None, perplexity 0-dim or None, idx (N,1) int64 in [0, prod levels), hist (K,) int32 or None).
+    The numeric contract is the header of csrc/vq_fsq.hip."""
+    _check_dev("z_e", z_e)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    lv, c_lv, K = _fsq_levels(levels)
+    w_in, b_in, w_out, b_out = _fsq_params(D, len(lv), w_in=w_in, b_in=b_in, w_out=w_out, b_out=b_out)
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        z_q = torch.empty_like(z_e) if want_zq else None
+        idx = torch.empty((B * H * W, 1), dtype=torch.int64, device=dev)
+        hist = torch.empty((K,), dtype=torch.int32, device=dev) if want_hist else None
+        ppl = torch.empty((), dtype=torch.float32, device=dev) if want_hist else None
+        _lib.check(_lib.load().vqvae_fsq_forward_f32(
+            z_e.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), c_lv, len(lv), B, D, H, W,
+            VQ_ROWMAJOR if rowmajor else 0, z_q.data_ptr() if want_zq else None, idx.data_ptr(),
+            hist.data_ptr() if want_hist else None, ppl.data_ptr() if want_hist else None, _stream_ptr(z_e)))
+    return z_q, ppl, idx, hist
+
+
+def fsq_decode_indices(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, levels, B: int, H: int, W: int, *,
+                       rowmajor: bool = False, validate: bool = True) -> torch.Tensor:
+    """indices -> z_q (B,D,H,W), or (B,H,W,D) when rowmajor (vqvae_fsq_decode_indices_f32): the forward's z_q of the same indices,
+    bit for bit.  Indices outside [0, prod levels) raise IndexError (one host sync; skipped with validate=False or while a graph is
+    captured: the kernel then writes NaN rows and reads nothing out of range)."""
+    _check_dev("idx", idx, torch.int64)
+    lv, c_lv, K = _fsq_levels(levels)
+    _check_dev("w_out", w_out)
+    if w_out.dim() != 2:
+        raise ValueError("w_out must be (D, d)")
+    D = w_out.shape[0]
+    w_out, b_out = _fsq_params(D, len(lv), w_out=w_out, b_out=b_out)
+    if idx.numel() != B * H * W:
+        raise ValueError("idx must hold B*H*W indices")
+    idx = idx.contiguous()
+    if validate and not torch.cuda.is_current_stream_capturing():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= K:
+            raise IndexError(f"index out of range in fsq_decode_indices: [{lo}, {hi}] not within [0, {K})")
+    dev = idx.device
+    out = torch.empty((B, H, W, D) if rowmajor else (B, D, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().vqvae_fsq_decode_indices_f32(idx.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), c_lv, len(lv), B, D, H, W,
+                                                            VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), _stream_ptr(idx)))
+    return out
+
+
+def fsq_backward_workspace(N: int, D: int, n_levels: int, device) -> torch.Tensor:
+    """workspace of training.fsq_backward's parameter gradients: one fp64 record per block of 256 rows"""
+    n = _lib.load().vqvae_fsq_backward_workspace_bytes(N, D, n_levels)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"FSQ backward: N={N}, D={D}, {n_levels} levels not supported (1 <= D <= 256, 1 to 8 levels, "
+                                 "1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)

@@ -411,6 +411,63 @@ class ResidualVectorQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
+class FiniteScalarQuantizer(nn.Module):
+    """Finite scalar quantization (arXiv 2309.15505; vector-quantize-pytorch's FSQ): the quantizer without a learned codebook.  A
+    latent row is projected to d = len(levels) channels (`project_in`), channel j is bounded with tanh and rounded to one of levels[j]
+    values, and the codes are projected back (`project_out`); the implicit codebook has n_e = prod levels entries and every latent
+    position still gets one integer index.  No commitment loss, no dead codes, no EMA state: the loss is a zero.  Both projections run
+    inside the HIP kernels (csrc/vq_fsq.hip states the arithmetic); the state is the two nn.Linear layers and nothing else."""
+
+    LAZY_MIN_ENCODINGS = True
+
+    def __init__(self, levels, dim):
+        super().__init__()
+        self.levels, _, self.n_e = F_hip._fsq_levels(levels)
+        if not 1 <= int(dim) <= 256:
+            raise ValueError("dim must be in [1, 256]")
+        self.e_dim = int(dim)
+        self.project_in = nn.Linear(self.e_dim, len(self.levels))
+        self.project_out = nn.Linear(len(self.levels), self.e_dim)
+
+    def _params(self):
+        return (self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias)
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (zero loss, z_q, perplexity, indices (N,1), hist); no one-hot.  z: (B,D,H,W), or (B,H,W,D) when rowmajor."""
+        _need_hip_f32(z, "FiniteScalarQuantizer")
+        params = self._params()
+        if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in params)):
+            from .training import FSQStraightThrough           # HIP forward + HIP backward
+            z_q, perplexity, idx, hist = FSQStraightThrough.apply(z, *params, self.levels, rowmajor)
+        else:
+            z_q, perplexity, idx, hist = F_hip.fsq_forward(z, *[p.detach() for p in params], self.levels, rowmajor=rowmajor,
+                                                           want_zq=want_zq)
+        return torch.zeros((), dtype=torch.float32, device=z.device), z_q, perplexity, idx, hist
+
+    def codes(self):
+        """the (K, d) implicit codebook: row k holds the d codes q_j / (L_j // 2) of index k (first level least significant)"""
+        dev = self.project_in.weight.device
+        lv = torch.tensor(self.levels, dtype=torch.int64, device=dev)
+        basis = torch.cumprod(torch.cat([lv.new_ones(1), lv[:-1]]), 0)
+        hw = lv // 2
+        q = (torch.arange(self.n_e, dtype=torch.int64, device=dev)[:, None] // basis[None, :]) % lv[None, :] - hw[None, :]
+        return (q.to(torch.float64) / hw.to(torch.float64)[None, :]).to(torch.float32)
+
+    @torch.no_grad()
+    def codebook(self):
+        """the (K, dim) decoded rows: what decode_indices writes for every index (functional.fsq_decode_indices)"""
+        w, b = self.project_out.weight, self.project_out.bias
+        _need_hip_f32(w, "FiniteScalarQuantizer.codebook")
+        idx = torch.arange(self.n_e, dtype=torch.int64, device=w.device)
+        return F_hip.fsq_decode_indices(idx, w.detach(), b.detach(), self.levels, self.n_e, 1, 1, rowmajor=True,
+                                        validate=False).reshape(self.n_e, self.e_dim)
+
+    def forward(self, z):
+        loss, z_q, perplexity, idx, _ = self.quantize(z)
+        min_encodings = LazyOneHot(idx, self.n_e) if self.LAZY_MIN_ENCODINGS else F_hip.vq_onehot(idx, self.n_e)
+        return loss, z_q, perplexity, min_encodings, idx
+
+
 class ResidualLayer(nn.Module):
     """Parameter holder mirroring models/residual.py:8-29."""
 
@@ -512,8 +569,18 @@ class VQVAE(nn.Module):
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
-                 shared_codebook=False, rotation_trick=False, cosine_sim=False):
+                 shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None):
         super().__init__()
+        if fsq_levels is not None:
+            # finite scalar quantization has no codebook: nothing that trains, restarts, stacks, rotates towards or normalises one
+            for name, on in (("ema_decay", ema_decay is not None), ("restart_threshold", restart_threshold is not None),
+                             ("n_quantizers > 1", n_quantizers != 1), ("shared_codebook", shared_codebook),
+                             ("rotation_trick", rotation_trick), ("cosine_sim", cosine_sim)):
+                if on:
+                    raise ValueError(f"fsq_levels (finite scalar quantization) has no learned codebook: {name} does not apply")
+            fsq_levels, _, k = F_hip._fsq_levels(fsq_levels)
+            if k != n_embeddings:
+                raise ValueError(f"n_embeddings must be the product of fsq_levels ({k}), got {n_embeddings}")
         if n_quantizers > 1 and cosine_sim:
             raise ValueError("cosine_sim is the one-stage quantizers' option: a per-stage normalisation of residual quantization "
                              "(n_quantizers > 1) does not exist")
@@ -527,7 +594,9 @@ class VQVAE(nn.Module):
             raise ValueError("shared_codebook needs n_quantizers > 1")
         self.encoder = Encoder(3, h_dim, n_res_layers, res_h_dim)
         self.pre_quantization_conv = nn.Conv2d(h_dim, embedding_dim, kernel_size=1, stride=1)
-        if n_quantizers > 1:
+        if fsq_levels is not None:
+            self.vector_quantization = FiniteScalarQuantizer(fsq_levels, embedding_dim)       # (beta: accepted, unused)
+        elif n_quantizers > 1:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
             self.vector_quantization = ResidualVectorQuantizer(n_quantizers, n_embeddings, embedding_dim, beta,
@@ -582,6 +651,8 @@ class VQVAE(nn.Module):
         """-> (VqvaeWeights, keep-alive tensors): every layer packed once per weight version into ONE buffer by
         vqvae_weights_pack_f32; rebuilt when any parameter's (data_ptr, _version) or the quantizer's beta changes, or invalidate_caches() ran."""
         from . import _lib
+        if isinstance(self.vector_quantization, FiniteScalarQuantizer):
+            raise VqvaeHipError("the fused whole-path entries have no finite scalar quantizer: FSQ models run layer by layer")
         params = dict(self.named_parameters(remove_duplicate=False))
         n_res = self.encoder.conv_stack[5].n_res_layers
         tensors = {}
@@ -777,6 +848,13 @@ class VQVAE(nn.Module):
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             embedding_loss, z_q, perplexity, _, _ = vq(z_e, rowmajor=True)
             return embedding_loss, C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True), perplexity.mean()
+        if isinstance(vq, FiniteScalarQuantizer):
+            # the per-layer path too; the indices are decoded by the helper decode_indices uses: decode_indices(encode(x)) is this
+            # x_hat bit for bit
+            _need_hip_f32(x, "VQVAE.forward")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
+            return embedding_loss, self._decode_fsq(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2], validate=False), perplexity
         ema = isinstance(vq, VectorQuantizerEMA)
         # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it; so does a
         # cosine_sim quantizer, whose rows are normalised between the encoder and the search -- the fused whole-path entries
@@ -809,6 +887,8 @@ class VQVAE(nn.Module):
         """Opt-in: start the codebook on the data -- z_e of the images x from the encoder and pre_quantization_conv (HIP path, no
         grad), then the quantizer's init_codebook_ (k-means++ seeding and `iters` Lloyd rounds).  Call it before the first update."""
         from . import conv as C_hip
+        if isinstance(self.vector_quantization, FiniteScalarQuantizer):
+            raise VqvaeHipError("finite scalar quantization has no codebook to initialise")
         _need_hip_f32(x, "VQVAE.init_codebook_")
         if C_hip.get_conv_backend() != "hip":
             raise VqvaeHipError("VQVAE.init_codebook_ runs on the HIP conv backend: there is no fallback")
@@ -837,6 +917,10 @@ class VQVAE(nn.Module):
         from . import _lib, conv as C_hip
         if isinstance(self.vector_quantization, ResidualVectorQuantizer):
             # (n_quantizers, N) int64, stage-major: the per-layer encoder, then the residual stages (indices only)
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
+        if isinstance(self.vector_quantization, FiniteScalarQuantizer):
+            _need_hip_f32(x, "VQVAE.encode")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
         if (C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32
@@ -877,6 +961,15 @@ class VQVAE(nn.Module):
                                       B, H, W, validate=validate)
         return C_hip.decoder_forward(self.decoder, z_q.detach(), rowmajor_in=False)
 
+    def _decode_fsq(self, idx, B, H, W, validate):
+        """fsq_levels: the indices' rows (functional.fsq_decode_indices), then the decoder.  The no-grad forward and decode_indices
+        both end here."""
+        from . import conv as C_hip
+        vq = self.vector_quantization
+        z_q = F_hip.fsq_decode_indices(idx.contiguous().view(-1).to(torch.int64), vq.project_out.weight.detach(),
+                                       vq.project_out.bias.detach(), vq.levels, B, H, W, rowmajor=True, validate=validate)
+        return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
+
     @torch.no_grad()
     def decode_indices(self, idx, B, H, W, fwd_flags=None, validate=True):
         """indices -> x_hat (visualization.ipynb:358-365 generate_samples) as ONE call (vqvae_decode_f32): on the default shapes
@@ -899,6 +992,8 @@ class VQVAE(nn.Module):
             return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
         if idx.numel() != B * H * W:
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
+        if isinstance(self.vector_quantization, FiniteScalarQuantizer):
+            return self._decode_fsq(idx, B, H, W, validate=validate)
         if self.vector_quantization.cosine_sim:
             return self._decode_codes(idx, B, H, W, validate=validate)
         if C_hip.get_conv_backend() != "hip" or not idx.is_cuda:

@@ -4,6 +4,8 @@
   * `VQStraightThrough`     autograd.Function pairing the fused HIP forward with that backward, so
                             `main.py:74-79` (loss.backward()) works with the HIP quantizer; the convs
                             must then run on the "torch" backend (their backward is torch's)
+  * `fsq_backward`,
+    `FSQStraightThrough`    finite scalar quantization's gradients (vqvae_fsq_backward_f32) and its autograd pairing
   * `step_losses`           `recon_loss`, `loss` and `perplexity` of main.py:75-76,81-83 in one fused
                             reduction, returned as ONE 3-element device tensor (one D2H copy per step)
 
@@ -277,3 +279,59 @@ class RVQStraightThrough(torch.autograd.Function):
         if ge is None:
             ge = [None] * len(books)
         return (gz, None, None, None, None, None, None) + tuple(ge)
+
+
+# ---- finite scalar quantization (csrc/vq_fsq.hip) --------------------------------------------------------------------------------
+
+def fsq_backward(z_e, grad_zq, w_in, b_in, w_out, levels, *, rowmajor=False, need_z=True, need_params=True):
+    """Gradients of functional.fsq_forward's z_q (vqvae_fsq_backward_f32): rounding is straight-through, tanh and both projections
+    are differentiated; t is recomputed from z_e.  z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.
+    -> (grad_z or None, (grad_w_in, grad_b_in, grad_w_out, grad_b_out) or None).  The parameter gradients are fp64 sums in a fixed
+    order: the same bits in both layouts and in every run."""
+    F_hip._check_dev("z_e", z_e)
+    F_hip._check_dev("grad_zq", grad_zq)
+    if z_e.dim() != 4 or grad_zq.shape != z_e.shape:
+        raise ValueError("z_e must be 4-D and grad_zq must have its shape")
+    if not (need_z or need_params):
+        return None, None
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    lv, c_lv, _ = F_hip._fsq_levels(levels)
+    d = len(lv)
+    w_in, b_in, w_out = F_hip._fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out)
+    z_e, grad_zq = z_e.contiguous(), grad_zq.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        gz = torch.empty_like(z_e) if need_z else None
+        gp = ws = None
+        if need_params:
+            gp = (torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out), torch.empty((D,), dtype=torch.float32, device=dev))
+            ws = F_hip.fsq_backward_workspace(B * H * W, D, d, dev)
+        p = [t.data_ptr() for t in gp] if gp is not None else [None] * 4
+        _lib.check(_lib.load().vqvae_fsq_backward_f32(
+            z_e.data_ptr(), grad_zq.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), c_lv, d, B, D, H, W,
+            F_hip.VQ_ROWMAJOR if rowmajor else 0, gz.data_ptr() if need_z else None, *p,
+            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
+    return gz, gp
+
+
+class FSQStraightThrough(torch.autograd.Function):
+    """(z_e, w_in, b_in, w_out, b_out) -> (z_q, perplexity, idx, hist) of finite scalar quantization: z_q differentiable with respect
+    to z_e and the four parameters, the rest not.  apply(z_e, w_in, b_in, w_out, b_out, levels, rowmajor)."""
+
+    @staticmethod
+    def forward(ctx, z_e, w_in, b_in, w_out, b_out, levels, rowmajor):
+        z = z_e.detach().contiguous()
+        params = [t.detach().contiguous() for t in (w_in, b_in, w_out, b_out)]
+        z_q, perplexity, idx, hist = F_hip.fsq_forward(z, *params, levels, rowmajor=rowmajor)
+        ctx.save_for_backward(z, *params[:3])
+        ctx.levels, ctx.rowmajor = tuple(levels), rowmajor
+        ctx.mark_non_differentiable(perplexity, idx, hist)
+        return z_q, perplexity, idx, hist
+
+    @staticmethod
+    def backward(ctx, g_zq, *_unused):
+        z, w_in, b_in, w_out = ctx.saved_tensors
+        need_z, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
+        gz, gp = fsq_backward(z, g_zq, w_in, b_in, w_out, ctx.levels, rowmajor=ctx.rowmajor, need_z=need_z, need_params=need_p)
+        gp = gp if gp is not None else (None,) * 4
+        return (gz,) + tuple(g if n else None for g, n in zip(gp, ctx.needs_input_grad[1:5])) + (None, None)
