@@ -58,6 +58,12 @@ inline unsigned grid_of(long long total, long long cap = 65536) {
     return (unsigned)g;
 }
 
+// Every clear in a chain that may be captured is this kernel launch, not hipMemsetAsync.  Captured memsets of 400 and of 4000 bytes
+// (the histogram at K = 100 and at K = 1000) came back from a graph replay with other bytes than the fill value in them, while every
+// kernel of those chains replayed as captured.  p: 4-byte aligned; bytes: a multiple of 4; every byte becomes
+// `byte`.  -> hipSuccess (0) or the launch's error.  (vq_exact.hip)
+int fill_bytes_async(void *p, int byte, size_t bytes, hipStream_t st);
+
 // Sum of one fp64 value per thread of a 256-thread workgroup through red[256], by a fixed tree (o = 128 ... 1).  Every thread of
 // the workgroup must call it; the total is left in red[0].
 __device__ __forceinline__ void block_sum_f64(double *red, int tid, double v) {

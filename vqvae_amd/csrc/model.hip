@@ -338,7 +338,7 @@ static int encoder_run(const VqvaeWeights *w, const float *x, int64_t B, int H, 
     if (!am) {
         am = static_cast<int *>(c.raw(amax_bytes(d, B)));
         // (no fill where every array that is read has a one-wave-per-image producer with plain stores: p.fused)
-        if (am && !p.fused && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
+        if (am && !p.fused && fill_bytes_async(am, 0xFF, amax_bytes(d, B), st) != 0) am = nullptr;
     }
     int *am0 = am, *am1 = am ? am + B : nullptr, *am2 = am ? am + 2 * B : nullptr;     // conv_in, enc2, enc4 (+ residual layers)
     const int h = d->h_dim, cf = p.cf;
@@ -418,7 +418,7 @@ static int decoder_run(const VqvaeWeights *w, const float *z_q, int64_t B, int h
     int *am = am_given;                                                       // optional, see encoder_run
     if (!am) {
         am = static_cast<int *>(c.raw(amax_bytes(d, B)));
-        if (am && !p.fused && hipMemsetAsync(am, 0xFF, amax_bytes(d, B), st) != hipSuccess) am = nullptr;
+        if (am && !p.fused && fill_bytes_async(am, 0xFF, amax_bytes(d, B), st) != 0) am = nullptr;
     }
     const int h = d->h_dim, cf = p.cf;
     int rc;
@@ -538,7 +538,7 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
     // is cleared by the encoder's last kernel
     const FwdPlan p = fwd_plan(d, H, W, vq_flags);
     if (p.cf < 0) return VQVAE_ERR_UNSUPPORTED;
-    if (!p.fused && hipMemsetAsync(am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (!p.fused && fill_bytes_async(am2, 0xFF, 2 * amax_bytes(d, B), st) != 0) return VQVAE_ERR_WORKSPACE;
     int *am_dec = reinterpret_cast<int *>(reinterpret_cast<char *>(am2) + amax_bytes(d, B));
     int rc;
     bool hist_zeroed = false;
@@ -603,7 +603,7 @@ int vqvae_encode_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, in
     const FwdPlan p = fwd_plan(d, H, W, vq_flags);
     if (p.cf < 0) return VQVAE_ERR_UNSUPPORTED;
     const size_t acts_bytes = 2 * align_up(f.act * sizeof(float), 256);
-    if (!p.fused && hipMemsetAsync(f.am2, 0xFF, 2 * amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (!p.fused && fill_bytes_async(f.am2, 0xFF, 2 * amax_bytes(d, B), st) != 0) return VQVAE_ERR_WORKSPACE;
     int rc;
     bool hist_zeroed = false;
     if (p.vq_fuse && !(vq_flags & kVqFormFlags)) {
@@ -638,7 +638,7 @@ int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t acts_bytes = 2 * align_up(f.act * sizeof(float), 256);
     int *am_dec = reinterpret_cast<int *>(reinterpret_cast<char *>(f.am2) + amax_bytes(d, B));
-    if (!p.fused && hipMemsetAsync(am_dec, 0xFF, amax_bytes(d, B), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (!p.fused && fill_bytes_async(am_dec, 0xFF, amax_bytes(d, B), st) != 0) return VQVAE_ERR_WORKSPACE;
     if (p.dec_front)
         return decoder_run(w, w->codebook, B, h4, w4, x_hat, f.acts, acts_bytes, st, p, am_dec, false, f.hid, idx);
     // other shapes: the codebook rows of every position into the workspace's z_q (row-major), then the decoder
@@ -671,7 +671,7 @@ int vqvae_forward_begin_f32(const VqvaeWeights *w, int64_t B, int H, int W, int 
     if (!fwd_plan(d, H, W, vq_flags).vq_fuse) return VQVAE_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = vq_prepare_impl(w->codebook, d->n_embeddings, d->embedding_dim, vq_flags, f.vqws, f.vqws_bytes, st)) != 0) return rc;
-    if (hipMemsetAsync(f.hist, 0, (size_t)d->n_embeddings * sizeof(int32_t), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (fill_bytes_async(f.hist, 0, (size_t)d->n_embeddings * sizeof(int32_t), st) != 0) return VQVAE_ERR_WORKSPACE;
     {
         std::lock_guard<std::mutex> lk(g_parts_mu);
         g_parts[workspace] = PartsRecord{B, H, W, vq_flags, vq_workspace, {}};      // (a begin without an end is simply replaced)

@@ -404,13 +404,29 @@ __global__ __launch_bounds__(256) void vq_decode_indices_kernel(const long long 
 }
 
 // ---------------------------------------------------------------------------
+// the clear of every capturable chain (common.h: fill_bytes_async)
+__global__ __launch_bounds__(256) void fill_words_kernel(unsigned *__restrict__ p, unsigned long long n, unsigned v) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+        p[i] = v;
+}
+
+int fill_bytes_async(void *p, int byte, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return 0;
+    if (!p || (bytes & 3) || (reinterpret_cast<uintptr_t>(p) & 3)) return (int)hipErrorInvalidValue;
+    const unsigned long long n = bytes / 4;
+    hipLaunchKernelGGL(fill_words_kernel, dim3(grid_of((long long)n, 1024)), dim3(256), 0, st, static_cast<unsigned *>(p), n,
+                       ((unsigned)byte & 0xFFu) * 0x01010101u);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // codebook images and bound statistics into the workspace (every kernel family's)
 template <int D>
 static int launch_vq_prepare(const float *cb, int K, char *ws, hipStream_t st) {
     const VqPlan p = vq_plan(K, D);
     int *wflags = reinterpret_cast<int *>(ws + p.off_flags);
-    hipError_t e;
-    if ((e = hipMemsetAsync(wflags, 0, 256 + kVqTicketBytes, st)) != hipSuccess) return (int)e;
+    int e;
+    if ((e = fill_bytes_async(wflags, 0, 256 + kVqTicketBytes, st)) != 0) return e;
     const int kmax = p.K_pad > p.K32 ? p.K_pad : p.K32;
     hipLaunchKernelGGL(vq_prepare_kernel<D>, dim3((kmax + 63) / 64), dim3(64), 0, st, cb, K, p.KC, p.K_pad,
                        reinterpret_cast<float *>(ws + p.off_ee), reinterpret_cast<float *>(ws + p.off_img), wflags, p.K32,
@@ -432,9 +448,9 @@ static int launch_vq(VqRoute route, const float *z, const float *cb, long long N
     float *img = reinterpret_cast<float *>(ws + p.off_img);
     double *partials = reinterpret_cast<double *>(ws + p.off_partials);
 
-    hipError_t e;
+    int e;
     // (hist_zeroed: the kernel in front of this one in the stream has cleared it -- vqvae_forward_f32's fused path)
-    if (!hist_zeroed && (e = hipMemsetAsync(hist, 0, sizeof(int) * (size_t)K, st)) != hipSuccess) return (int)e;
+    if (!hist_zeroed && (e = fill_bytes_async(hist, 0, sizeof(int) * (size_t)K, st)) != 0) return e;
     if (!(flags & VQVAE_VQ_CODEBOOK_PREPARED)) {
         const int rc = launch_vq_prepare<D>(cb, K, ws, st);
         if (rc != 0) return rc;

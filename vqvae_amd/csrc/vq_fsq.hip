@@ -96,13 +96,6 @@ __global__ __launch_bounds__(kFsqBlockRows) void fsq_param_finalize_kernel(const
     fsq_param_finalize_body(partials, nblocks, D, d, g_w_in, g_b_in, g_w_out, g_b_out);
 }
 
-// hist = 0 in front of the forward.  A kernel, not hipMemsetAsync: a captured memset of K * 4 bytes (4000 for levels (8, 5, 5, 5)) came
-// back from a graph replay with other values than zero in it, while every kernel of the chain replayed as captured.
-__global__ __launch_bounds__(256) void fsq_zero_hist_kernel(int *hist, int K) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k < K) hist[k] = 0;
-}
-
 __global__ __launch_bounds__(256) void fsq_perplexity_kernel(const int *hist, int K, long long N, float *perplexity) {
     __shared__ double red[256];
     const int tid = threadIdx.x;
@@ -243,7 +236,9 @@ int vqvae_fsq_forward_f32(const float *z_e, const float *w_in, const float *b_in
     a.z = z_e; a.w_in = w_in; a.b_in = b_in; a.w_out = z_q ? w_out : nullptr; a.b_out = z_q ? b_out : nullptr;
     a.out = z_q; a.idx = reinterpret_cast<long long *>(idx); a.hist = hist;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hist) hipLaunchKernelGGL(fsq_zero_hist_kernel, dim3((unsigned)((a.K + 255) / 256)), dim3(256), 0, st, hist, a.K);
+    // hist = 0 in front of the forward, by a kernel (common.h: fill_bytes_async): a captured hipMemsetAsync of its K * 4 bytes (4000 for
+    // levels (8, 5, 5, 5)) came back from a graph replay with other values than zero in it
+    if (hist && (rc = fill_bytes_async(hist, 0, (size_t)a.K * 4, st)) != 0) return rc;
     launch_fsq_forward(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
     if (perplexity) hipLaunchKernelGGL(fsq_perplexity_kernel, dim3(1), dim3(256), 0, st, hist, a.K, a.N, perplexity);
     return (int)hipGetLastError();

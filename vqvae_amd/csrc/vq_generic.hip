@@ -624,9 +624,9 @@ int launch_vq_generic(const float *z, const float *cb, long long N, int HW, int 
         float *ee = reinterpret_cast<float *>(ws), *eeimg = reinterpret_cast<float *>(ws + p.off_eeimg), *aimg = reinterpret_cast<float *>(ws + p.off_aimg);
         int *flags = reinterpret_cast<int *>(ws + p.off_flags);
         double *partials = reinterpret_cast<double *>(ws + p.off_partials);
-        if (!hist_zeroed && hipMemsetAsync(hist, 0, (size_t)K * sizeof(int), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+        if (!hist_zeroed && fill_bytes_async(hist, 0, (size_t)K * sizeof(int), st) != 0) return VQVAE_ERR_WORKSPACE;
         if (!prepared) {
-            if (hipMemsetAsync(flags, 0, 256, st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+            if (fill_bytes_async(flags, 0, 256, st) != 0) return VQVAE_ERR_WORKSPACE;
             hipLaunchKernelGGL(vq_anyd_prepare_kernel, dim3((unsigned)((p.ntile * 32 + 63) / 64)), dim3(64), 0, st, cb, K, D, p.Q, p.ntile, ee, eeimg,
                                aimg, flags);
         }
@@ -650,13 +650,13 @@ int launch_vq_generic(const float *z, const float *cb, long long N, int HW, int 
     }
     float *ee = reinterpret_cast<float *>(ws);
     double *partials = reinterpret_cast<double *>(ws + align_up((size_t)K * 4, 256));
-    if (!hist_zeroed && hipMemsetAsync(hist, 0, (size_t)K * sizeof(int), st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+    if (!hist_zeroed && fill_bytes_async(hist, 0, (size_t)K * sizeof(int), st) != 0) return VQVAE_ERR_WORKSPACE;
     if (!prepared) {
         // the whole prepared image, not only ||e||^2: a later call with VQVAE_VQ_CODEBOOK_PREPARED on this workspace may run
         // vq_anyd_kernel, which reads the flags, the ee image and the A-operand image (ee itself: the same sum, the same bits)
         const AnydPlan p = anyd_plan(K, D);
         int *flags = reinterpret_cast<int *>(ws + p.off_flags);
-        if (hipMemsetAsync(flags, 0, 256, st) != hipSuccess) return VQVAE_ERR_WORKSPACE;
+        if (fill_bytes_async(flags, 0, 256, st) != 0) return VQVAE_ERR_WORKSPACE;
         hipLaunchKernelGGL(vq_anyd_prepare_kernel, dim3((unsigned)((p.ntile * 32 + 63) / 64)), dim3(64), 0, st, cb, K, D, p.Q, p.ntile, ee,
                            reinterpret_cast<float *>(ws + p.off_eeimg), reinterpret_cast<float *>(ws + p.off_aimg), flags);
     } else {
