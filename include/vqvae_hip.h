@@ -446,6 +446,43 @@ VQVAE_API int vqvae_vq_residual_backward_f32(const float *z_e, const float *cons
                                              int Q, float beta, int flags, float *grad_z, float *const *grad_codebooks,
                                              void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* Grouped (product) vector quantization (csrc/vq_grouped.hip; its header is the numeric contract): the D channels of a row are cut
+ * into G groups of d = D / G channels, group g is quantized against its own (K, d) codebook E_g (wav2vec 2.0's groups; heads with a
+ * codebook each).  A position carries G indices:
+ *     slab_g = the channels [g d, (g + 1) d) of every row, dense, in the layout of the input
+ *     idx_g, hist_g, loss_g, perplexity_g = vqvae_vq_forward_f32's outputs for (slab_g, E_g, beta)
+ *     z_q[row][g d + c] = z + (E_g[idx_g[row]][c] - z);   loss = ((loss_0 + loss_1) + ...) / (float)G on the device
+ * 1 <= G <= 16, D % G == 0, 1 <= D <= 256, K <= 16384, N <= INT32_MAX: VQVAE_ERR_UNSUPPORTED outside it, and the sizing calls then
+ * return 0.  The same error for a pointer that is not 4-byte aligned (idx, workspace: 8-byte) and for an output that overlaps an
+ * input.  `codebooks` is a HOST array of G device pointers (read during the call only).  No host sync, no allocation, no
+ * floating-point atomics; every launch on `stream` in one linear chain (capturable); the same bits in every run.
+ *
+ * forward:  flags = the quantizer's own (VQVAE_VQ_ROWMAJOR, VQVAE_VQ_CODEBOOK_PREPARED, the kernel-selection flags), passed to every
+ *   group.  The workspace holds one prepared codebook image per group and the G slabs, so VQVAE_VQ_CODEBOOK_PREPARED means: every
+ *   group's image is there from a previous call with the same codebooks and workspace.
+ *     idx (G, N) int64 group-major;  hist (G, K) int32;  loss_group, perplexity_group (G) fp32: each group's quantizer outputs;
+ *     loss 1 fp32;  z_q like z_e, may be NULL;  slabs_out, may be NULL: the G slabs one after the other, (G, B, d, H, W) or (G, N, d)
+ *     with VQVAE_VQ_ROWMAJOR -- what vqvae_vq_ema_update_f32 and the k-means entries take per group.
+ *   Launches: one split kernel, G quantizer calls (index-only), one finish kernel.  G = 1: the bits of vqvae_vq_forward_f32.
+ * decode:   indices (G, N) -> z_q[row][g d + c] = E_g[idx_g[row]][c], (B,D,H,W) or rows with VQVAE_VQ_ROWMAJOR.  An index outside
+ *   [0, K) never reads a codebook: the d elements of that group's segment become NaN, and only those.
+ * backward: per group the gradients of vqvae_vq_backward_f32 on (slab_g, E_g, idx_g, grad_zq's channels, g / (float)G), written into
+ *   grad_z's channels of the group and grad_codebooks[g] (a HOST array of G device pointers; may be NULL, and the workspace is
+ *   needed only with it).  g = *grad_loss (NULL = 1), grad_zq may be NULL (= 0), grad_z may be NULL.  flags: VQVAE_VQ_ROWMAJOR,
+ *   VQVAE_VQ_BWD_COMMITMENT (grad_z of beta * mse only; with grad_codebooks: VQVAE_ERR_UNSUPPORTED).                            */
+VQVAE_API size_t vqvae_vq_grouped_workspace_bytes(int64_t N, int K, int D, int G);
+VQVAE_API int vqvae_vq_grouped_forward_f32(const float *z_e, const float *const *codebooks, int64_t B, int D, int H, int W, int K,
+                                           int G, float beta, int flags, float *z_q, int64_t *idx, int32_t *hist,
+                                           float *loss_group, float *perplexity_group, float *loss, float *slabs_out,
+                                           void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_vq_grouped_decode_f32(const int64_t *idx, const float *const *codebooks, int64_t B, int D, int H, int W, int K,
+                                          int G, int flags, float *z_q, vqvae_stream_t stream);
+VQVAE_API size_t vqvae_vq_grouped_backward_workspace_bytes(int64_t N, int K, int D, int G);
+VQVAE_API int vqvae_vq_grouped_backward_f32(const float *z_e, const float *const *codebooks, const int64_t *idx,
+                                            const float *grad_zq, const float *grad_loss, int64_t B, int D, int H, int W, int K,
+                                            int G, float beta, int flags, float *grad_z, float *const *grad_codebooks,
+                                            void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* recon_loss = mean((x_hat - x)^2) / x_train_var; loss = recon_loss + embedding_loss (main.py:75-76).
  * out3 = {recon_loss, loss, perplexity}: the three values main.py:81-83 copies to the host one by one,
  * packed so that a step needs one D2H copy.  embedding_loss / perplexity are device scalars (NULL = 0);

@@ -13,6 +13,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--rotation_trick]                             (off by default: the rotation-trick gradient)
                                      [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
                                      [--fsq_levels 8,5,5,5 --n_embeddings 1000]     (off by default: finite scalar quantization)
+                                     [--codebook_groups G]                          (off by default: grouped quantization, G codebooks)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
 <out>/<tag>_log.txt (the reference's log line every --log_interval updates + the range guard's per-layer spreads along the way;
@@ -33,10 +34,11 @@ import torch
 
 from tests import synthdata
 from vqvae_amd import conv, training as T
-from vqvae_amd.modules import VQVAE
+from vqvae_amd.modules import GroupedVectorQuantizer, VQVAE
 
 
-def main():
+def parse(argv=None):
+    """-> (args, the keyword options of VQVAE that were given: every opt-in option is absent from both unless named)"""
     p = argparse.ArgumentParser()
     p.add_argument("--batch_size", type=int, default=32)           # main.py:17-27's defaults
     p.add_argument("--n_updates", type=int, default=5000)
@@ -68,8 +70,12 @@ def main():
     p.add_argument("--cosine_sim", action="store_true", default=argparse.SUPPRESS)
     # opt-in finite scalar quantization (fsq_levels=(8, 5, 5, 5): no codebook; --n_embeddings must be the levels' product); absent unless given
     p.add_argument("--fsq_levels", type=lambda v: tuple(int(l) for l in v.split(",")), default=argparse.SUPPRESS, metavar="L0,L1,..")
-    args = p.parse_args()
+    # opt-in grouped (product) quantization (codebook_groups=G: G codebooks of embedding_dim / G channels); absent unless given
+    p.add_argument("--codebook_groups", type=int, default=argparse.SUPPRESS, metavar="G")
+    args = p.parse_args(argv)
     ema_kw = {}
+    if hasattr(args, "codebook_groups"):
+        ema_kw["codebook_groups"] = args.codebook_groups
     if hasattr(args, "fsq_levels"):
         ema_kw["fsq_levels"] = args.fsq_levels
     if hasattr(args, "cosine_sim"):
@@ -84,7 +90,11 @@ def main():
         ema_kw["ema_decay"] = args.ema_decay
     if hasattr(args, "restart_threshold"):
         ema_kw["restart_threshold"] = args.restart_threshold
+    return args, ema_kw
 
+
+def main(argv=None):
+    args, ema_kw = parse(argv)
     dev = torch.device("cuda:0")
     conv.set_conv_backend("hip")
     os.makedirs(args.out, exist_ok=True)
@@ -113,6 +123,8 @@ def main():
     else:
         opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)   # main.py:59
     model.train()
+    # grouped models run layer by layer: the range guard and the product schemes belong to the fused whole-path entries they do not use
+    whole_path = not isinstance(model.vector_quantization, GroupedVectorQuantizer)
     results = {"n_updates": 0, "recon_errors": [], "loss_vals": [], "perplexities": []}
     if getattr(args, "kmeans_init", 0) > 0:
         # the batches the loop below is about to draw (the same generator seed; the loop's own generator starts afresh)
@@ -142,18 +154,22 @@ def main():
             results["loss_vals"] += block[:, 1].tolist()
             results["perplexities"] += block[:, 2].tolist()
             results["n_updates"] = i
-            model.eval()
-            with torch.no_grad():
-                rec, spreads = model.scheme_hint()
-            model.train()
+            guard = "per-layer path"
+            if whole_path:
+                model.eval()
+                with torch.no_grad():
+                    rec, spreads = model.scheme_hint()
+                model.train()
+                guard = f"flags={rec:#x} max spread {max(spreads):.2f} binades"
             say(f"Update # {i} Recon Error: {block[:, 0].mean():.5f} Loss {block[:, 1].mean():.5f} Perplexity: {block[:, 2].mean():.3f}"
-                f"   | guard: flags={rec:#x} max spread {max(spreads):.2f} binades   [{time.time() - t0:.1f} s]")
+                f"   | guard: {guard}   [{time.time() - t0:.1f} s]")
     torch.cuda.synchronize()
     say(f"# {args.n_updates} updates in {time.time() - t0:.1f} s")
 
     model.eval()
-    rec, spreads = model.scheme_hint()
-    say(f"# final guard: flags={rec:#x}; per-layer input-channel spreads (binades): {[round(s, 2) for s in spreads]}")
+    if whole_path:
+        rec, spreads = model.scheme_hint()
+        say(f"# final guard: flags={rec:#x}; per-layer input-channel spreads (binades): {[round(s, 2) for s in spreads]}")
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     torch.save({"model": sd, "results": results, "hyperparameters": vars(args)}, os.path.join(args.out, f"{args.tag}.pth"))
     np.savez_compressed(os.path.join(args.out, f"{args.tag}_state.npz"), **{k: v.numpy() for k, v in sd.items()})
@@ -161,6 +177,17 @@ def main():
     # a first look at the checkpoint through the product path: validation images, all three product schemes
     from vqvae_amd import functional as F_hip
     xv = synthdata.normalised(4096, args.data_seed + 1).to(dev)
+    if not whole_path:
+        # the per-layer path: the eval forward, and the index wire format back through the decoder (the same x_hat, bit for bit)
+        with torch.no_grad():
+            loss, x_hat, ppl = model(xv)
+            idx = model.encode(xv)
+            same = torch.equal(model.decode_indices(idx, xv.shape[0], xv.shape[2] // 4, xv.shape[3] // 4), x_hat)
+        say(f"# eval[per-layer]: embedding_loss={loss.item():.6g} mean perplexity={ppl.item():.4f} distinct codes per group="
+            f"{[g.unique().numel() for g in idx]} recon mse/var={((x_hat - xv) ** 2).mean().item() / x_train_var:.5f} "
+            f"decode_indices(encode(x)) is x_hat: {same}")
+        log.close()
+        return
     with torch.no_grad():
         out = {}
         for name, fl in (("guard", None), ("fp16x2", 0), ("bf16x3", F_hip.FWD_CONV_BF16_SPLIT), ("fp32", F_hip.FWD_CONV_EXACT_FP32)):

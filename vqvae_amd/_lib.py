@@ -105,6 +105,13 @@ SIGNATURES = {
     "vqvae_vq_residual_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "vqvae_vq_residual_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
                                               _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_vq_grouped_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "vqvae_vq_grouped_forward_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_vq_grouped_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "vqvae_vq_grouped_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "vqvae_vq_grouped_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
+                                             _vp, _vp, _vp, _sz, _vp]),
     "vqvae_recon_loss_workspace_bytes": (_sz, []),
     "vqvae_recon_loss_f32": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vqvae_recon_loss_backward_f32": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),

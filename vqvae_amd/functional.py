@@ -425,6 +425,97 @@ def vq_residual_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, 
     return out
 
 
+# ---- grouped (product) vector quantization (csrc/vq_grouped.hip) -----------------------------------------------------------------
+
+def _grouped_books(codebooks):
+    """-> contiguous (K, d) codebooks, one per group"""
+    if isinstance(codebooks, torch.Tensor):
+        codebooks = [codebooks] if codebooks.dim() == 2 else list(codebooks.unbind(0))
+    books = list(codebooks)
+    if not 1 <= len(books) <= 16:
+        raise ValueError("1 to 16 codebooks, one per group")
+    for i, c in enumerate(books):
+        _check_dev(f"codebooks[{i}]", c)
+        if c.dim() != 2 or c.shape != books[0].shape:
+            raise ValueError("every codebook must be (K, d) with the same K and d")
+    return [c.contiguous() for c in books]
+
+
+def vq_grouped_workspace(N: int, K: int, D: int, G: int, device) -> torch.Tensor:
+    """workspace of vq_grouped_forward: one prepared codebook image per group and the G slabs"""
+    n = _lib.load().vqvae_vq_grouped_workspace_bytes(N, K, D, G)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"grouped quantizer: N={N}, K={K}, D={D}, G={G} not supported (1 <= G <= 16, D % G == 0, K <= 16384, "
+                                 "D <= 256, N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_grouped_forward(z_e: torch.Tensor, codebooks, beta: float, *, rowmajor: bool = False, want_zq: bool = True,
+                       want_slabs: bool = False, workspace: torch.Tensor | None = None, prepared: bool = False):
+    """Grouped (product) quantization (vqvae_vq_grouped_forward_f32): the D channels of a row are cut into G = len(codebooks) groups of
+    d = D / G channels, group g is quantized by the reference quantizer against codebooks[g], a (K, d) tensor.
+    z_e: (B,D,H,W), or (B,H,W,D) when rowmajor.
+    -> (loss 0-dim: the mean of the group losses, z_q like z_e or None, perplexity (G,), idx (G, N) int64, hist (G, K) int32,
+    loss_group (G,)), and with want_slabs a seventh value: the G slabs, (G,B,d,H,W) or (G,B,H,W,d) when rowmajor -- slab g holds the
+    group's channels of every row, dense.  prepared: `workspace` holds every group's codebook image from a previous call with the
+    same codebooks.  The numeric contract is the header of csrc/vq_grouped.hip."""
+    _check_dev("z_e", z_e)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    books = _grouped_books(codebooks)
+    G = len(books)
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K, d = books[0].shape
+    if d * G != D:
+        raise ValueError(f"channel dim {D} != {G} groups of embedding dim {d}")
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    N = B * H * W
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_grouped_workspace(N, K, D, G, dev)
+            prepared = False
+        z_q = torch.empty_like(z_e) if want_zq else None
+        slabs = torch.empty((G, B, H, W, d) if rowmajor else (G, B, d, H, W), dtype=torch.float32, device=dev) if want_slabs else None
+        idx = torch.empty((G, N), dtype=torch.int64, device=dev)
+        hist = torch.empty((G, K), dtype=torch.int32, device=dev)
+        scal = torch.empty((2 * G + 1,), dtype=torch.float32, device=dev)
+        flags = (VQ_ROWMAJOR if rowmajor else 0) | (VQ_CODEBOOK_PREPARED if prepared else 0)
+        _lib.check(_lib.load().vqvae_vq_grouped_forward_f32(
+            z_e.data_ptr(), _ptr_array(books), B, D, H, W, K, G, float(beta), flags,
+            z_q.data_ptr() if want_zq else None, idx.data_ptr(), hist.data_ptr(), scal.data_ptr(), scal.data_ptr() + 4 * G,
+            scal.data_ptr() + 8 * G, slabs.data_ptr() if want_slabs else None, workspace.data_ptr(), workspace.numel(),
+            _stream_ptr(z_e)))
+    out = (scal[2 * G], z_q, scal[G:2 * G], idx, hist, scal[:G])
+    return out + (slabs,) if want_slabs else out
+
+
+def vq_grouped_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, rowmajor: bool = False,
+                      validate: bool = True) -> torch.Tensor:
+    """(G, N) indices -> their code rows side by side, (B,D,H,W) or (B,H,W,D) when rowmajor (vqvae_vq_grouped_decode_f32).  Indices
+    outside [0, K) raise IndexError (one host sync; skipped with validate=False or while a graph is captured: the kernel then writes
+    NaN into that group's channels of the row and never reads outside a codebook)."""
+    _check_dev("idx", idx, torch.int64)
+    books = _grouped_books(codebooks)
+    G = len(books)
+    K, d = books[0].shape
+    N = B * H * W
+    if idx.numel() != G * N:
+        raise ValueError(f"idx must hold G*B*H*W = {G * N} indices, group-major")
+    idx = idx.contiguous()
+    if validate and not torch.cuda.is_current_stream_capturing():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= K:
+            raise IndexError(f"index out of range in vq_grouped_decode: [{lo}, {hi}] not within [0, {K})")
+    dev = idx.device
+    D = G * d
+    out = torch.empty((B, H, W, D) if rowmajor else (B, D, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().vqvae_vq_grouped_decode_f32(
+            idx.data_ptr(), _ptr_array(books), B, D, H, W, K, G, VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), _stream_ptr(idx)))
+    return out
+
+
 # ---- finite scalar quantization (csrc/vq_fsq.hip) --------------------------------------------------------------------------------
 
 def _fsq_levels(levels):

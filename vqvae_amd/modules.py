@@ -411,6 +411,175 @@ class ResidualVectorQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
+class GroupedVectorQuantizer(nn.Module):
+    """Grouped (product) quantization (wav2vec 2.0's groups, arXiv 2006.11477; vector-quantize-pytorch's heads with
+    separate_codebook_per_head): the e_dim channels of a latent row are cut into n_g groups of d = e_dim / n_g channels and every
+    group is quantized -- by the reference's quantizer as written -- against its own (n_e, d) codebook.  A position carries n_g
+    indices; z_q holds the groups' codes side by side (straight-through: z + (e - z)) and the loss is the mean of the groups'
+    losses, which is the reference's loss formula on the whole rows (csrc/vq_grouped.hip states the arithmetic).
+
+    Group 0's codebook is `embedding` (VectorQuantizer's state_dict key, of shape (n_e, d)); groups 1 .. n_g - 1 are
+    `group_embeddings.{g-1}`.  Every codebook starts as uniform(-1/K, 1/K), drawn in group order."""
+
+    LAZY_MIN_ENCODINGS = True
+
+    def __init__(self, n_g, n_e, e_dim, beta):
+        super().__init__()
+        if not 1 <= int(n_g) <= 16:
+            raise ValueError("n_g must be in [1, 16]")
+        if int(e_dim) % int(n_g):
+            raise ValueError(f"e_dim ({e_dim}) must be a multiple of the number of groups ({n_g})")
+        self.n_g = int(n_g)
+        self.n_e = n_e
+        self.e_dim = int(e_dim)
+        self.g_dim = self.e_dim // self.n_g
+        self.beta = beta
+        self.embedding = nn.Embedding(self.n_e, self.g_dim)
+        self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
+        self.group_embeddings = nn.ModuleList(nn.Embedding(self.n_e, self.g_dim) for _ in range(self.n_g - 1))
+        for emb in self.group_embeddings:
+            emb.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
+
+    def codebooks(self):
+        """the codebooks in group order"""
+        return [self.embedding.weight] + [emb.weight for emb in self.group_embeddings]
+
+    def invalidate(self):
+        """Forget the prepared codebook images (VectorQuantizer.invalidate: after a write through `.data`)."""
+        for slot in _cache.side(self).get("ws", {}).values():
+            slot[1] = None
+
+    def _workspace(self, N):
+        """-> (workspace, prepared, key, slot), one per (device, stream, N): VectorQuantizer._workspace with every group's image"""
+        books = self.codebooks()
+        w = books[0]
+        key = tuple((t.data_ptr(), t._version) for t in books) + (w.device,)
+        table = _cache.side(self).setdefault("ws", {})
+        skey = (str(w.device), torch.cuda.current_stream(w.device).cuda_stream if w.is_cuda else 0, N)
+        slot = _cache.lru_get(table, skey)
+        if slot is None:
+            slot = [F_hip.vq_grouped_workspace(N, self.n_e, self.e_dim, self.n_g, w.device), None]
+            _cache.lru_put(table, skey, slot, 8)
+        return slot[0], slot[1] == key, key, slot
+
+    def _run(self, z, rowmajor, want_zq, *, commitment=False, want_slabs=False):
+        """-> (loss, z_q, perplexity, idx, hist, loss_group, slabs or None) through the autograd pairing where a graph is recorded"""
+        _need_hip_f32(z, type(self).__name__)
+        books = self.codebooks()
+        N = z.numel() // self.e_dim
+        ws, prepared, key, slot = self._workspace(N)
+        if not prepared:
+            slot[1] = None
+        if torch.is_grad_enabled() and (z.requires_grad or any(w.requires_grad for w in books)):
+            from .training import GroupedStraightThrough       # HIP forward + HIP backward
+            out = GroupedStraightThrough.apply(z, self.beta, rowmajor, commitment, want_slabs, ws, prepared, *books)
+        else:
+            out = F_hip.vq_grouped_forward(z, [w.detach() for w in books], 0.0 if commitment else self.beta, rowmajor=rowmajor,
+                                           want_zq=want_zq, want_slabs=want_slabs, workspace=ws, prepared=prepared)
+            if commitment:
+                out = (out[0] * self.beta,) + out[1:5] + (out[5] * self.beta,) + out[6:]
+            if not want_slabs:
+                out = out + (None,)
+        slot[1] = key
+        return out
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (loss, z_q, perplexity (n_g,), idx (n_g, N), hist (n_g, K)); no one-hot."""
+        return self._run(z, rowmajor, want_zq)[:5]
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _slabs(self, z, rowmajor):
+        """the G dense slabs of z as the forward's split kernel writes them: (G,B,d,H,W), or (G,B,H,W,d) when rowmajor"""
+        return F_hip.vq_grouped_forward(z.detach(), [w.detach() for w in self.codebooks()], 0.0, rowmajor=rowmajor, want_zq=False,
+                                        want_slabs=True)[6]
+
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """Opt-in data-dependent start, group by group: E_g = k-means (functional.vq_kmeans: k-means++ seeding and `iters` Lloyd
+        rounds) of the group's slab of z.  -> [(codebook, counts of the last assignment)] in group order."""
+        _need_hip_f32(z, "init_codebook_")
+        out = []
+        for w, slab in zip(self.codebooks(), self._slabs(z, rowmajor)):
+            codebook, counts = F_hip.vq_kmeans(slab, self.n_e, iters, generator=generator, rowmajor=rowmajor)
+            w.copy_(codebook)
+            out.append((codebook, counts))
+        return out
+
+    def forward(self, z, *, rowmajor=False):
+        """The reference's 5-tuple shape: (loss, z_q, perplexity (n_g,), group 0's min_encodings, idx (n_g, N)).  rowmajor: z and
+        z_q are (B,H,W,D), as VQVAE.forward hands them over."""
+        loss, z_q, perplexity, idx, _ = self.quantize(z, rowmajor=rowmajor)
+        idx0 = idx[0].reshape(-1, 1)
+        min_encodings = LazyOneHot(idx0, self.n_e) if self.LAZY_MIN_ENCODINGS else F_hip.vq_onehot(idx0, self.n_e)
+        return loss, z_q, perplexity, min_encodings, idx
+
+
+class GroupedVectorQuantizerEMA(GroupedVectorQuantizer):
+    """GroupedVectorQuantizer whose codebooks follow exponential moving averages (VectorQuantizerEMA, per group) instead of a
+    gradient.
+
+    State: the codebooks (Parameters with requires_grad=False, GroupedVectorQuantizer's keys) and the buffers `ema_cluster_size`
+    (n_g, K) = N_k per group (initially 0) and `ema_w` (n_g, K, d) = m_k (initially the initial codebooks).  Every forward in
+    training mode -- with or without grad -- runs one update per group (vqvae_vq_ema_update_f32) from that forward's slab and
+    indices, then copies the new codebooks in place.  Eval mode never updates.  The forward's outputs are those of the codebooks
+    BEFORE the update; the loss is beta * the mean over the groups of the group's mse, and the codebooks get no gradient.
+
+    restart_threshold: as VectorQuantizerEMA's, per group: one torch.rand(K) per group and update, drawn in group order."""
+
+    def __init__(self, n_g, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None):
+        super().__init__(n_g, n_e, e_dim, beta)
+        self.decay = float(decay)
+        self.eps = float(eps)
+        self.restart_threshold = None if restart_threshold is None else float(restart_threshold)
+        self.generator = generator
+        for w in self.codebooks():
+            w.requires_grad_(False)
+        self.register_buffer("ema_cluster_size", torch.zeros(self.n_g, n_e))
+        self.register_buffer("ema_w", torch.stack([w.detach().clone() for w in self.codebooks()]))
+
+    def _ema_update(self, slabs, idx, rowmajor):
+        books = self.codebooks()
+        dev = books[0].device
+        N = idx.shape[1]
+        wkey = (str(dev), torch.cuda.current_stream(dev).cuda_stream, N)
+        table = _cache.side(self).setdefault("ema_ws", {})
+        ws = _cache.lru_get(table, wkey)
+        if ws is None:
+            ws = F_hip.vq_ema_workspace(N, self.n_e, self.g_dim, dev)
+            _cache.lru_put(table, wkey, ws, 4)
+        for g, w in enumerate(books):
+            uniforms = None
+            if self.restart_threshold is not None:
+                uniforms = torch.rand(self.n_e, device=dev, generator=self.generator)
+            new = torch.empty_like(w, memory_format=torch.contiguous_format)
+            F_hip.vq_ema_update(slabs[g], idx[g], self.ema_cluster_size[g], self.ema_w[g], new, self.decay, self.eps,
+                                threshold=self.restart_threshold, uniforms=uniforms, rowmajor=rowmajor, workspace=ws)
+            with torch.no_grad():
+                w.copy_(new)
+
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """GroupedVectorQuantizer.init_codebook_, and the EMA state continues from the clusters: ema_cluster_size[g] = counts,
+        ema_w[g] = counts[:, None] * codebook."""
+        out = super().init_codebook_(z, iters, generator, rowmajor=rowmajor)
+        for g, (codebook, counts) in enumerate(out):
+            c = counts.to(torch.float32)
+            self.ema_cluster_size[g].copy_(c)
+            self.ema_w[g].copy_(c[:, None] * codebook)
+        return out
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (beta * mean of the groups' mse, z_q, perplexity (n_g,), idx (n_g, N), hist (n_g, K)) against the codebooks as they
+        were on entry; then, in training mode, one EMA update per group from the slabs the forward wrote."""
+        out = self._run(z, rowmajor, want_zq, commitment=True, want_slabs=self.training)
+        if self.training:
+            self._ema_update(out[6], out[3], rowmajor)
+        return out[:5]
+
+
 class FiniteScalarQuantizer(nn.Module):
     """Finite scalar quantization (arXiv 2309.15505; vector-quantize-pytorch's FSQ): the quantizer without a learned codebook.  A
     latent row is projected to d = len(levels) channels (`project_in`), channel j is bounded with tanh and rounded to one of levels[j]
@@ -569,8 +738,18 @@ class VQVAE(nn.Module):
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
-                 shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None):
+                 shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1):
         super().__init__()
+        if codebook_groups != 1:
+            # grouped (product) quantization: every group is the plain or the EMA quantizer on its channels, nothing else
+            if not 1 <= int(codebook_groups) <= 16:
+                raise ValueError("codebook_groups must be in [1, 16]")
+            for name, on in (("n_quantizers > 1", n_quantizers != 1), ("shared_codebook", shared_codebook),
+                             ("rotation_trick", rotation_trick), ("cosine_sim", cosine_sim), ("fsq_levels", fsq_levels is not None)):
+                if on:
+                    raise ValueError(f"codebook_groups > 1 (grouped quantization) does not combine with {name}")
+            if embedding_dim % int(codebook_groups):
+                raise ValueError(f"embedding_dim ({embedding_dim}) must be a multiple of codebook_groups ({codebook_groups})")
         if fsq_levels is not None:
             # finite scalar quantization has no codebook: nothing that trains, restarts, stacks, rotates towards or normalises one
             for name, on in (("ema_decay", ema_decay is not None), ("restart_threshold", restart_threshold is not None),
@@ -594,7 +773,16 @@ class VQVAE(nn.Module):
             raise ValueError("shared_codebook needs n_quantizers > 1")
         self.encoder = Encoder(3, h_dim, n_res_layers, res_h_dim)
         self.pre_quantization_conv = nn.Conv2d(h_dim, embedding_dim, kernel_size=1, stride=1)
-        if fsq_levels is not None:
+        if codebook_groups != 1:
+            if ema_decay is None:
+                if restart_threshold is not None:
+                    raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
+                self.vector_quantization = GroupedVectorQuantizer(codebook_groups, n_embeddings, embedding_dim, beta)
+            else:
+                self.vector_quantization = GroupedVectorQuantizerEMA(codebook_groups, n_embeddings, embedding_dim, beta,
+                                                                     decay=ema_decay, eps=ema_eps,
+                                                                     restart_threshold=restart_threshold)
+        elif fsq_levels is not None:
             self.vector_quantization = FiniteScalarQuantizer(fsq_levels, embedding_dim)       # (beta: accepted, unused)
         elif n_quantizers > 1:
             if restart_threshold is not None:
@@ -625,7 +813,7 @@ class VQVAE(nn.Module):
         _cache.drop(self, "c_weights")
         for mod in self.modules():
             conv_hip.invalidate(mod)
-            if isinstance(mod, (VectorQuantizer, ResidualVectorQuantizer)):
+            if isinstance(mod, (VectorQuantizer, ResidualVectorQuantizer, GroupedVectorQuantizer)):
                 mod.invalidate()
 
     # forward / encode / decode_indices follow vqvae_weights_range_check_f32's recommendation for the checkpoint (scheme_hint()) unless
@@ -653,6 +841,8 @@ class VQVAE(nn.Module):
         from . import _lib
         if isinstance(self.vector_quantization, FiniteScalarQuantizer):
             raise VqvaeHipError("the fused whole-path entries have no finite scalar quantizer: FSQ models run layer by layer")
+        if isinstance(self.vector_quantization, GroupedVectorQuantizer):
+            raise VqvaeHipError("the fused whole-path entries quantize whole rows: grouped models run layer by layer")
         params = dict(self.named_parameters(remove_duplicate=False))
         n_res = self.encoder.conv_stack[5].n_res_layers
         tensors = {}
@@ -831,8 +1021,9 @@ class VQVAE(nn.Module):
             if not x.is_cuda or x.dtype != torch.float32:
                 raise VqvaeHipError("VQVAE.forward needs a CUDA(HIP) fp32 input: there is no CPU path")
             z_e = A_hip.encoder_forward_train(self.encoder, x, self.pre_quantization_conv)
-            if isinstance(self.vector_quantization, ResidualVectorQuantizer):
-                # (through the module's __call__: forward hooks see z_e; the stages' mean perplexity is the scalar main.py:82 logs)
+            if isinstance(self.vector_quantization, (ResidualVectorQuantizer, GroupedVectorQuantizer)):
+                # (through the module's __call__: forward hooks see z_e; the stages' or groups' mean perplexity is the scalar
+                # main.py:82 logs)
                 embedding_loss, z_q, perplexity, _, _ = self.vector_quantization(z_e, rowmajor=True)
                 perplexity = perplexity.mean()
             else:
@@ -848,6 +1039,13 @@ class VQVAE(nn.Module):
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             embedding_loss, z_q, perplexity, _, _ = vq(z_e, rowmajor=True)
             return embedding_loss, C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True), perplexity.mean()
+        if isinstance(vq, GroupedVectorQuantizer):
+            # groups: the per-layer path too.  Without a graph the decoder takes the code rows themselves, through the helper
+            # decode_indices uses: decode_indices(encode(x)) is this x_hat bit for bit.  (The training forward decodes z + (e - z).)
+            _need_hip_f32(x, "VQVAE.forward")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
+            return embedding_loss, self._decode_grouped(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2]), perplexity.mean()
         if isinstance(vq, FiniteScalarQuantizer):
             # the per-layer path too; the indices are decoded by the helper decode_indices uses: decode_indices(encode(x)) is this
             # x_hat bit for bit
@@ -919,6 +1117,11 @@ class VQVAE(nn.Module):
             # (n_quantizers, N) int64, stage-major: the per-layer encoder, then the residual stages (indices only)
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
+        if isinstance(self.vector_quantization, GroupedVectorQuantizer):
+            # (codebook_groups, N) int64, group-major; never an EMA update (GroupedVectorQuantizer's own quantize)
+            _need_hip_f32(x, "VQVAE.encode")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            return GroupedVectorQuantizer.quantize(self.vector_quantization, z_e, rowmajor=True, want_zq=False)[3]
         if isinstance(self.vector_quantization, FiniteScalarQuantizer):
             _need_hip_f32(x, "VQVAE.encode")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
@@ -961,6 +1164,14 @@ class VQVAE(nn.Module):
                                       B, H, W, validate=validate)
         return C_hip.decoder_forward(self.decoder, z_q.detach(), rowmajor_in=False)
 
+    def _decode_grouped(self, idx, B, H, W):
+        """codebook_groups: the (G, N) indices' code rows side by side (functional.vq_grouped_decode), then the decoder.  The no-grad
+        forward and decode_indices both end here."""
+        from . import conv as C_hip
+        vq = self.vector_quantization
+        z_q = F_hip.vq_grouped_decode(idx, [w.detach() for w in vq.codebooks()], B, H, W, rowmajor=True, validate=False)
+        return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
+
     def _decode_fsq(self, idx, B, H, W, validate):
         """fsq_levels: the indices' rows (functional.fsq_decode_indices), then the decoder.  The no-grad forward and decode_indices
         both end here."""
@@ -990,6 +1201,15 @@ class VQVAE(nn.Module):
             z_q = F_hip.vq_residual_decode(idx, [w.detach() for w in vq.codebooks()], B, H, W, rowmajor=True,
                                            shared=vq.shared_codebook, validate=False)
             return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
+        if isinstance(self.vector_quantization, GroupedVectorQuantizer):
+            # codebook_groups * B * H * W indices, group-major as encode() returns them
+            vq = self.vector_quantization
+            if idx.numel() != vq.n_g * B * H * W:
+                raise ValueError(f"expected {vq.n_g * B * H * W} indices ({vq.n_g} groups), got {idx.numel()}")
+            idx = idx.contiguous().view(vq.n_g, -1).to(torch.int64)
+            if validate and (int(idx.min()) < 0 or int(idx.max()) >= K):
+                raise IndexError(f"code index out of range [0, {K})")
+            return self._decode_grouped(idx, B, H, W)
         if idx.numel() != B * H * W:
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
         if isinstance(self.vector_quantization, FiniteScalarQuantizer):

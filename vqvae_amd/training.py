@@ -4,6 +4,8 @@
   * `VQStraightThrough`     autograd.Function pairing the fused HIP forward with that backward, so
                             `main.py:74-79` (loss.backward()) works with the HIP quantizer; the convs
                             must then run on the "torch" backend (their backward is torch's)
+  * `vq_grouped_backward`,
+    `GroupedStraightThrough` grouped (product) quantization's gradients (vqvae_vq_grouped_backward_f32) and its autograd pairing
   * `fsq_backward`,
     `FSQStraightThrough`    finite scalar quantization's gradients (vqvae_fsq_backward_f32) and its autograd pairing
   * `step_losses`           `recon_loss`, `loss` and `perplexity` of main.py:75-76,81-83 in one fused
@@ -276,6 +278,98 @@ class RVQStraightThrough(torch.autograd.Function):
             g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
         gz, ge = vq_residual_backward(z, books, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, shared=ctx.shared,
                                       need_z=need_z, need_codebooks=need_w)
+        if ge is None:
+            ge = [None] * len(books)
+        return (gz, None, None, None, None, None, None) + tuple(ge)
+
+
+# ---- grouped (product) vector quantization (csrc/vq_grouped.hip) -----------------------------------------------------------------
+
+def vq_grouped_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowmajor=False, need_z=True, need_codebooks=True,
+                        commitment=False):
+    """Gradients of functional.vq_grouped_forward (vqvae_vq_grouped_backward_f32): per group those of vq_backward on the group's
+    channels with the upstream loss gradient grad_loss / G.
+
+    z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.  idx: the forward's (G, N) indices.  grad_loss: 0-dim device tensor or
+    None (= 1).  commitment=True: the z gradient of the EMA form's loss, beta * the mean of the groups' mse (no codebook gradients).
+    -> (grad_z or None, list of G codebook gradients or None)."""
+    if commitment and need_codebooks:
+        raise ValueError("the commitment-only gradient has no codebook term")
+    F_hip._check_dev("z_e", z_e)
+    F_hip._check_dev("idx", idx, torch.int64)
+    books = F_hip._grouped_books(codebooks)
+    G = len(books)
+    z_e = z_e.contiguous()
+    idx = idx.contiguous()
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K, d = books[0].shape
+    N = B * H * W
+    if d * G != D or idx.numel() != G * N:
+        raise ValueError("shape mismatch between z_e, the codebooks and idx")
+    if grad_zq is not None:
+        F_hip._check_dev("grad_zq", grad_zq)
+        grad_zq = grad_zq.contiguous()
+        if grad_zq.shape != z_e.shape:
+            raise ValueError("grad_zq must have z_e's shape")
+    if grad_loss is not None:
+        F_hip._check_dev("grad_loss", grad_loss)
+        grad_loss = grad_loss.reshape(1).contiguous()
+    if not (need_z or need_codebooks):
+        return None, None
+    dev = z_e.device
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        gz = torch.empty_like(z_e) if need_z else None
+        ge = [torch.empty_like(c) for c in books] if need_codebooks else None
+        ws = None
+        if need_codebooks:
+            n = L.vqvae_vq_grouped_backward_workspace_bytes(N, K, D, G)
+            if n == 0:
+                raise _lib.VqvaeHipError(f"grouped VQ backward: N={N}, K={K}, D={D}, G={G} not supported")
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        _lib.check(L.vqvae_vq_grouped_backward_f32(
+            z_e.data_ptr(), F_hip._ptr_array(books), idx.data_ptr(),
+            grad_zq.data_ptr() if grad_zq is not None else None,
+            grad_loss.data_ptr() if grad_loss is not None else None,
+            B, D, H, W, K, G, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0),
+            gz.data_ptr() if gz is not None else None, F_hip._ptr_array(ge) if ge is not None else None,
+            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
+    return gz, ge
+
+
+class GroupedStraightThrough(torch.autograd.Function):
+    """(z_e, E_0 .. E_{G-1}) -> (loss, z_q, perplexity (G,), idx (G, N), hist (G, K), loss_group (G,), slabs or None) of the grouped
+    quantizer: loss and z_q differentiable (d z_q / d z = I), the rest not.
+    apply(z_e, beta, rowmajor, commitment, want_slabs, workspace, prepared, *codebooks).  commitment: the EMA form -- the forward runs
+    with beta 0 and returns beta * the mean of the groups' mse, only z_e gets a gradient, and the backward keeps its own copies of
+    the codebooks (the EMA update writes the live ones right after the forward)."""
+
+    @staticmethod
+    def forward(ctx, z_e, beta, rowmajor, commitment, want_slabs, workspace, prepared, *codebooks):
+        z = z_e.detach().contiguous()
+        books = [c.detach().contiguous() for c in codebooks]
+        out = F_hip.vq_grouped_forward(z, books, 0.0 if commitment else beta, rowmajor=rowmajor, want_slabs=want_slabs,
+                                       workspace=workspace, prepared=prepared)
+        loss, z_q, perplexity, idx, hist, loss_group = out[:6]
+        slabs = out[6] if want_slabs else None
+        if commitment:
+            loss, loss_group = loss * beta, loss_group * beta
+            books = [c.clone() for c in books]
+        ctx.save_for_backward(z, idx, *books)
+        ctx.beta, ctx.rowmajor, ctx.commitment = beta, rowmajor, bool(commitment)
+        # (one call: a second one would replace the first's list)
+        ctx.mark_non_differentiable(perplexity, idx, hist, loss_group, *([slabs] if slabs is not None else []))
+        return loss, z_q, perplexity, idx, hist, loss_group, slabs
+
+    @staticmethod
+    def backward(ctx, g_loss, g_zq, *_unused):
+        z, idx, *books = ctx.saved_tensors
+        need_z = ctx.needs_input_grad[0]
+        need_w = any(ctx.needs_input_grad[7:]) and not ctx.commitment
+        if g_loss is None:
+            g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
+        gz, ge = vq_grouped_backward(z, books, idx, g_zq, g_loss, ctx.beta, rowmajor=ctx.rowmajor, need_z=need_z,
+                                     need_codebooks=need_w, commitment=ctx.commitment)
         if ge is None:
             ge = [None] * len(books)
         return (gz, None, None, None, None, None, None) + tuple(ge)
