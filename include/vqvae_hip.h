@@ -408,6 +408,41 @@ VQVAE_API int vqvae_fsq_backward_f32(const float *z_e, const float *grad_zq, con
                                      float *grad_z, float *grad_w_in, float *grad_b_in, float *grad_w_out, float *grad_b_out,
                                      void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* Lookup-free quantization (csrc/vq_lfq.hip; its header is the numeric contract): the codebook is {-1, +1}^d, K = 2^d (MAGVIT-v2,
+ * arXiv 2310.05737 section 3.1; vector-quantize-pytorch's LFQ).  A row is projected to d channels (w_in (d, D), b_in (d)), every
+ * channel keeps its sign (c_j = +1 where y_j > 0, else -1), and the signs are projected back (w_out (D, d), b_out (D)); the
+ * projections run inside the kernels in fp64 with one rounding per output.  beta weighs the commitment term, entropy_weight the
+ * entropy penalty, diversity_gamma the codebook entropy inside it; inv_temperature (the library's 100) scales the logits.
+ *     workspace_bytes: one size for forward and backward; 0 = outside the envelope.
+ *     forward:   z_q (may be NULL; then w_out / b_out may be too), idx (N) int64 in [0, K), FIRST channel LEAST significant;
+ *                hist (K) int32 counts (may be NULL), perplexity = exp(-sum p log(p + 1e-10)) (may be NULL, needs hist);
+ *                losses (4) fp32 = (loss, commitment C, per-sample entropy P, codebook entropy H), loss = beta C + w_e (P - gamma H),
+ *                and avg (K) fp64, the batch-averaged code distribution.  losses and avg may be NULL together: then no entropy work
+ *                runs and no workspace is needed.  The sums over the rows are fp64 in an order that depends on (N, K) alone: every
+ *                output has the same bits in both layouts and in every run.  No (N, K) array is formed.
+ *     decode:    idx -> z_q; an index outside [0, K) writes a NaN row.
+ *     backward:  from grad_zq (NULL = 0) and g = *grad_loss (device scalar, NULL = 1) to grad_z (straight-through rounding) and the
+ *                four parameter gradients (fp64 sums: blocks of 256 rows in row order, then the blocks in order).  avg is the
+ *                forward's; with avg NULL the loss contributes nothing.  Every gradient pointer may be NULL (not all); the
+ *                workspace is always needed.
+ *   Rows and layouts are vqvae_vq_forward_f32's; the only flag is VQVAE_VQ_ROWMAJOR.  No host sync, no allocation, every launch on
+ *   `stream` in one chain, every clear a kernel: capturable.
+ *   Envelope: 1 <= d <= 16, 1 <= D <= 256, N <= INT32_MAX.  VQVAE_ERR_UNSUPPORTED outside it, for a pointer that is not 4-byte
+ *   aligned (idx, avg, workspace: 8-byte) and for an output that overlaps an input.                                              */
+VQVAE_API size_t vqvae_lfq_workspace_bytes(int64_t N, int D, int d);
+VQVAE_API int vqvae_lfq_forward_f32(const float *z_e, const float *w_in, const float *b_in, const float *w_out, const float *b_out,
+                                    int d, int64_t B, int D, int H, int W, int flags, float beta, float entropy_weight,
+                                    float diversity_gamma, float inv_temperature, float *z_q, int64_t *idx, int32_t *hist,
+                                    float *perplexity, float *losses, double *avg, void *workspace, size_t workspace_bytes,
+                                    vqvae_stream_t stream);
+VQVAE_API int vqvae_lfq_decode_indices_f32(const int64_t *idx, const float *w_out, const float *b_out, int d, int64_t B, int D,
+                                           int H, int W, int flags, float *z_q, vqvae_stream_t stream);
+VQVAE_API int vqvae_lfq_backward_f32(const float *z_e, const float *grad_zq, const float *grad_loss, const double *avg,
+                                     const float *w_in, const float *b_in, const float *w_out, int d, int64_t B, int D, int H, int W,
+                                     int flags, float beta, float entropy_weight, float diversity_gamma, float inv_temperature,
+                                     float *grad_z, float *grad_w_in, float *grad_b_in, float *grad_w_out, float *grad_b_out,
+                                     void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* Residual vector quantization (csrc/vq_residual.hip; its header is the numeric contract): Q codebooks E_0 .. E_{Q-1}, each (K, D),
  * quantize the same latent position, stage q what stage q - 1 left over (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ):
  *     r_0 = z;   idx_q = vqvae_vq_forward_f32's indices of r_q against E_q;   r_{q+1} = r_q - E_q[idx_q]

@@ -13,6 +13,8 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--rotation_trick]                             (off by default: the rotation-trick gradient)
                                      [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
                                      [--fsq_levels 8,5,5,5 --n_embeddings 1000]     (off by default: finite scalar quantization)
+                                     [--lookup_free --n_embeddings 1024 [--lfq_entropy_weight 0.1 --lfq_diversity_gamma 1 --lfq_inv_temperature 100]]
+                                                                                    (off by default: lookup-free quantization)
                                      [--codebook_groups G]                          (off by default: grouped quantization, G codebooks)
 
 Writes <out>/<tag>.pth in the reference's checkpoint layout (utils.py:109-113: {'model', 'results', 'hyperparameters'}),
@@ -34,7 +36,7 @@ import torch
 
 from tests import synthdata
 from vqvae_amd import conv, training as T
-from vqvae_amd.modules import GroupedVectorQuantizer, VQVAE
+from vqvae_amd.modules import GroupedVectorQuantizer, LookupFreeQuantizer, VQVAE
 
 
 def parse(argv=None):
@@ -72,8 +74,19 @@ def parse(argv=None):
     p.add_argument("--fsq_levels", type=lambda v: tuple(int(l) for l in v.split(",")), default=argparse.SUPPRESS, metavar="L0,L1,..")
     # opt-in grouped (product) quantization (codebook_groups=G: G codebooks of embedding_dim / G channels); absent unless given
     p.add_argument("--codebook_groups", type=int, default=argparse.SUPPRESS, metavar="G")
+    # opt-in lookup-free quantization (lookup_free=True: the codebook is {-1, +1}^log2(n_embeddings); --beta weighs its commitment term);
+    # absent unless given
+    p.add_argument("--lookup_free", action="store_true", default=argparse.SUPPRESS)
+    p.add_argument("--lfq_entropy_weight", type=float, default=argparse.SUPPRESS)
+    p.add_argument("--lfq_diversity_gamma", type=float, default=argparse.SUPPRESS)
+    p.add_argument("--lfq_inv_temperature", type=float, default=argparse.SUPPRESS)
     args = p.parse_args(argv)
     ema_kw = {}
+    if hasattr(args, "lookup_free"):
+        ema_kw["lookup_free"] = True
+    for name in ("lfq_entropy_weight", "lfq_diversity_gamma", "lfq_inv_temperature"):
+        if hasattr(args, name):
+            ema_kw[name] = getattr(args, name)
     if hasattr(args, "codebook_groups"):
         ema_kw["codebook_groups"] = args.codebook_groups
     if hasattr(args, "fsq_levels"):
@@ -124,7 +137,8 @@ def main(argv=None):
         opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, amsgrad=True)   # main.py:59
     model.train()
     # grouped models run layer by layer: the range guard and the product schemes belong to the fused whole-path entries they do not use
-    whole_path = not isinstance(model.vector_quantization, GroupedVectorQuantizer)
+    # (and so do lookup-free models)
+    whole_path = not isinstance(model.vector_quantization, (GroupedVectorQuantizer, LookupFreeQuantizer))
     results = {"n_updates": 0, "recon_errors": [], "loss_vals": [], "perplexities": []}
     if getattr(args, "kmeans_init", 0) > 0:
         # the batches the loop below is about to draw (the same generator seed; the loop's own generator starts afresh)
@@ -184,7 +198,7 @@ def main(argv=None):
             idx = model.encode(xv)
             same = torch.equal(model.decode_indices(idx, xv.shape[0], xv.shape[2] // 4, xv.shape[3] // 4), x_hat)
         say(f"# eval[per-layer]: embedding_loss={loss.item():.6g} mean perplexity={ppl.item():.4f} distinct codes per group="
-            f"{[g.unique().numel() for g in idx]} recon mse/var={((x_hat - xv) ** 2).mean().item() / x_train_var:.5f} "
+            f"{[g.unique().numel() for g in (idx if isinstance(model.vector_quantization, GroupedVectorQuantizer) else [idx])]} recon mse/var={((x_hat - xv) ** 2).mean().item() / x_train_var:.5f} "
             f"decode_indices(encode(x)) is x_hat: {same}")
         log.close()
         return

@@ -603,3 +603,84 @@ def fsq_backward_workspace(N: int, D: int, n_levels: int, device) -> torch.Tenso
         raise _lib.VqvaeHipError(f"FSQ backward: N={N}, D={D}, {n_levels} levels not supported (1 <= D <= 256, 1 to 8 levels, "
                                  "1 <= N < 2^31)")
     return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+# ---- lookup-free quantization (csrc/vq_lfq.hip) ----------------------------------------------------------------------------------
+
+def _lfq_bits(n_e):
+    """-> d = log2 n_e; ValueError unless n_e is a power of two in [2, 65536]"""
+    n_e = int(n_e)
+    if n_e < 2 or n_e > 65536 or n_e & (n_e - 1):
+        raise ValueError(f"lookup-free quantization needs a power of two in [2, 65536] codes, got {n_e}")
+    return n_e.bit_length() - 1
+
+
+def lfq_workspace(N: int, D: int, d: int, device) -> torch.Tensor:
+    """workspace of lfq_forward's losses and of training.lfq_backward (vqvae_lfq_workspace_bytes: one size for both)"""
+    n = _lib.load().vqvae_lfq_workspace_bytes(N, D, d)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"LFQ: N={N}, D={D}, d={d} not supported (1 <= D <= 256, 1 <= d <= 16, 1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def lfq_forward(z_e: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, n_e: int, *,
+                beta: float = 0.25, entropy_weight: float = 0.1, diversity_gamma: float = 1.0, inv_temperature: float = 100.0,
+                rowmajor: bool = False, want_zq: bool = True, want_hist: bool = True, want_loss: bool = True, workspace=None):
+    """Lookup-free quantization (vqvae_lfq_forward_f32; MAGVIT-v2, arXiv 2310.05737): rows of z_e -> project_in -> sign -> project_out
+    inside one kernel, and the commitment and entropy losses from the factorised softmax (no (N, K) array).  z_e: (B,D,H,W), or
+    (B,H,W,D) when rowmajor; w_in (d, D), b_in (d), w_out (D, d), b_out (D) as nn.Linear holds them, d = log2 n_e.
+    -> (z_q like z_e or None, perplexity 0-dim or None, idx (N,1) int64 in [0, n_e) with the FIRST channel least significant,
+        hist (K,) int32 or None, losses (4,) fp32 = (loss, commitment, per-sample entropy, codebook entropy) or None,
+        avg (K,) fp64 or None).  The numeric contract is the header of csrc/vq_lfq.hip."""
+    _check_dev("z_e", z_e)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    d = _lfq_bits(n_e)
+    w_in, b_in, w_out, b_out = _fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out, b_out=b_out)
+    z_e = z_e.contiguous()
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        z_q = torch.empty_like(z_e) if want_zq else None
+        idx = torch.empty((B * H * W, 1), dtype=torch.int64, device=dev)
+        hist = torch.empty((n_e,), dtype=torch.int32, device=dev) if want_hist else None
+        ppl = torch.empty((), dtype=torch.float32, device=dev) if want_hist else None
+        losses = avg = ws = None
+        if want_loss:
+            losses = torch.empty((4,), dtype=torch.float32, device=dev)
+            avg = torch.empty((n_e,), dtype=torch.float64, device=dev)
+            ws = workspace if workspace is not None else lfq_workspace(B * H * W, D, d, dev)
+        _lib.check(_lib.load().vqvae_lfq_forward_f32(
+            z_e.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), d, B, D, H, W,
+            VQ_ROWMAJOR if rowmajor else 0, beta, entropy_weight, diversity_gamma, inv_temperature,
+            z_q.data_ptr() if want_zq else None, idx.data_ptr(), hist.data_ptr() if want_hist else None,
+            ppl.data_ptr() if want_hist else None, losses.data_ptr() if want_loss else None, avg.data_ptr() if want_loss else None,
+            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream_ptr(z_e)))
+    return z_q, ppl, idx, hist, losses, avg
+
+
+def lfq_decode_indices(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, n_e: int, B: int, H: int, W: int, *,
+                       rowmajor: bool = False, validate: bool = True) -> torch.Tensor:
+    """indices -> z_q (B,D,H,W), or (B,H,W,D) when rowmajor (vqvae_lfq_decode_indices_f32): the forward's z_q of the same indices,
+    bit for bit.  Indices outside [0, n_e) raise IndexError (one host sync; skipped with validate=False or while a graph is
+    captured: the kernel then writes NaN rows)."""
+    _check_dev("idx", idx, torch.int64)
+    d = _lfq_bits(n_e)
+    _check_dev("w_out", w_out)
+    if w_out.dim() != 2:
+        raise ValueError("w_out must be (D, d)")
+    D = w_out.shape[0]
+    w_out, b_out = _fsq_params(D, d, w_out=w_out, b_out=b_out)
+    if idx.numel() != B * H * W:
+        raise ValueError("idx must hold B*H*W indices")
+    idx = idx.contiguous()
+    if validate and not torch.cuda.is_current_stream_capturing():
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= n_e:
+            raise IndexError(f"index out of range in lfq_decode_indices: [{lo}, {hi}] not within [0, {n_e})")
+    dev = idx.device
+    out = torch.empty((B, H, W, D) if rowmajor else (B, D, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().vqvae_lfq_decode_indices_f32(idx.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), d, B, D, H, W,
+                                                            VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), _stream_ptr(idx)))
+    return out

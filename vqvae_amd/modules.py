@@ -637,6 +637,77 @@ class FiniteScalarQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
+class LookupFreeQuantizer(nn.Module):
+    """Lookup-free quantization (MAGVIT-v2, arXiv 2310.05737 section 3.1; vector-quantize-pytorch's LFQ): the codebook is
+    {-1, +1}^d with d = log2 n_e.  A latent row is projected to d channels (`project_in`), every channel keeps its sign, and the signs
+    are projected back (`project_out`); every latent position still gets one integer index (first channel least significant).
+    loss = beta * commitment + entropy_weight * (per-sample entropy - diversity_gamma * codebook entropy), computed by the HIP kernels
+    from the factorised softmax (csrc/vq_lfq.hip states the arithmetic), in training and in eval mode.  The state is the two
+    nn.Linear layers and nothing else."""
+
+    LAZY_MIN_ENCODINGS = True
+
+    def __init__(self, n_e, dim, beta, *, entropy_weight=0.1, diversity_gamma=1.0, inv_temperature=100.0):
+        super().__init__()
+        self.bits = F_hip._lfq_bits(n_e)
+        if not 1 <= int(dim) <= 256:
+            raise ValueError("dim must be in [1, 256]")
+        self.n_e, self.e_dim, self.beta = int(n_e), int(dim), beta
+        self.entropy_weight, self.diversity_gamma, self.inv_temperature = entropy_weight, diversity_gamma, inv_temperature
+        self.project_in = nn.Linear(self.e_dim, self.bits)
+        self.project_out = nn.Linear(self.bits, self.e_dim)
+        self.last_losses = None                      # (loss, commitment, per-sample entropy, codebook entropy) of the latest call
+
+    def _params(self):
+        return (self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias)
+
+    def _weights(self):
+        return (float(self.beta), float(self.entropy_weight), float(self.diversity_gamma), float(self.inv_temperature))
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True, want_loss=True):
+        """-> (loss (a zero without want_loss), z_q, perplexity, indices (N,1), hist); no one-hot.  z: (B,D,H,W), or (B,H,W,D) when
+        rowmajor."""
+        _need_hip_f32(z, "LookupFreeQuantizer")
+        params = self._params()
+        if want_loss and torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in params)):
+            from .training import LFQStraightThrough           # HIP forward + HIP backward
+            z_q, loss, perplexity, idx, hist, losses, _ = LFQStraightThrough.apply(z, *params, self.n_e, self._weights(), rowmajor)
+        else:
+            beta, we, gamma, inv_t = self._weights()
+            z_q, perplexity, idx, hist, losses, _ = F_hip.lfq_forward(
+                z, *[p.detach() for p in params], self.n_e, beta=beta, entropy_weight=we, diversity_gamma=gamma, inv_temperature=inv_t,
+                rowmajor=rowmajor, want_zq=want_zq, want_loss=want_loss)
+            loss = losses[0] if want_loss else torch.zeros((), dtype=torch.float32, device=z.device)
+        if want_loss:
+            self.last_losses = losses
+        return loss, z_q, perplexity, idx, hist
+
+    def codes(self):
+        """the (K, d) implicit codebook: row k holds +1 where bit j of k is set, -1 where not (first channel least significant)"""
+        dev = self.project_in.weight.device
+        k = torch.arange(self.n_e, dtype=torch.int64, device=dev)[:, None]
+        j = torch.arange(self.bits, dtype=torch.int64, device=dev)[None, :]
+        return (((k >> j) & 1) * 2 - 1).to(torch.float32)
+
+    def decode(self, idx, B, H, W, *, rowmajor=True, validate=True):
+        """indices -> z_q rows (functional.lfq_decode_indices)"""
+        return F_hip.lfq_decode_indices(idx.contiguous().view(-1).to(torch.int64), self.project_out.weight.detach(),
+                                        self.project_out.bias.detach(), self.n_e, B, H, W, rowmajor=rowmajor, validate=validate)
+
+    @torch.no_grad()
+    def codebook(self):
+        """the (K, dim) decoded rows: what decode_indices writes for every index"""
+        w = self.project_out.weight
+        _need_hip_f32(w, "LookupFreeQuantizer.codebook")
+        idx = torch.arange(self.n_e, dtype=torch.int64, device=w.device)
+        return self.decode(idx, self.n_e, 1, 1, validate=False).reshape(self.n_e, self.e_dim)
+
+    def forward(self, z):
+        loss, z_q, perplexity, idx, _ = self.quantize(z)
+        min_encodings = LazyOneHot(idx, self.n_e) if self.LAZY_MIN_ENCODINGS else F_hip.vq_onehot(idx, self.n_e)
+        return loss, z_q, perplexity, min_encodings, idx
+
+
 class ResidualLayer(nn.Module):
     """Parameter holder mirroring models/residual.py:8-29."""
 
@@ -738,8 +809,18 @@ class VQVAE(nn.Module):
 
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
-                 shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1):
+                 shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1,
+                 lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0):
         super().__init__()
+        if lookup_free:
+            # lookup-free quantization: the codebook is {-1, +1}^d; beta weighs its commitment term
+            for name, on in (("ema_decay", ema_decay is not None), ("restart_threshold", restart_threshold is not None),
+                             ("n_quantizers > 1", n_quantizers != 1), ("shared_codebook", shared_codebook),
+                             ("rotation_trick", rotation_trick), ("cosine_sim", cosine_sim), ("fsq_levels", fsq_levels is not None),
+                             ("codebook_groups > 1", codebook_groups != 1)):
+                if on:
+                    raise ValueError(f"lookup_free (lookup-free quantization) has no learned codebook: {name} does not apply")
+            F_hip._lfq_bits(n_embeddings)
         if codebook_groups != 1:
             # grouped (product) quantization: every group is the plain or the EMA quantizer on its channels, nothing else
             if not 1 <= int(codebook_groups) <= 16:
@@ -784,6 +865,9 @@ class VQVAE(nn.Module):
                                                                      restart_threshold=restart_threshold)
         elif fsq_levels is not None:
             self.vector_quantization = FiniteScalarQuantizer(fsq_levels, embedding_dim)       # (beta: accepted, unused)
+        elif lookup_free:
+            self.vector_quantization = LookupFreeQuantizer(n_embeddings, embedding_dim, beta, entropy_weight=lfq_entropy_weight,
+                                                           diversity_gamma=lfq_diversity_gamma, inv_temperature=lfq_inv_temperature)
         elif n_quantizers > 1:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
@@ -841,6 +925,8 @@ class VQVAE(nn.Module):
         from . import _lib
         if isinstance(self.vector_quantization, FiniteScalarQuantizer):
             raise VqvaeHipError("the fused whole-path entries have no finite scalar quantizer: FSQ models run layer by layer")
+        if isinstance(self.vector_quantization, LookupFreeQuantizer):
+            raise VqvaeHipError("the fused whole-path entries have no lookup-free quantizer: LFQ models run layer by layer")
         if isinstance(self.vector_quantization, GroupedVectorQuantizer):
             raise VqvaeHipError("the fused whole-path entries quantize whole rows: grouped models run layer by layer")
         params = dict(self.named_parameters(remove_duplicate=False))
@@ -1046,8 +1132,8 @@ class VQVAE(nn.Module):
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
             return embedding_loss, self._decode_grouped(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2]), perplexity.mean()
-        if isinstance(vq, FiniteScalarQuantizer):
-            # the per-layer path too; the indices are decoded by the helper decode_indices uses: decode_indices(encode(x)) is this
+        if isinstance(vq, (FiniteScalarQuantizer, LookupFreeQuantizer)):
+            # the per-layer path too (an LFQ model's loss is computed here as well, as in training); the indices are decoded by the helper decode_indices uses: decode_indices(encode(x)) is this
             # x_hat bit for bit
             _need_hip_f32(x, "VQVAE.forward")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
@@ -1087,6 +1173,8 @@ class VQVAE(nn.Module):
         from . import conv as C_hip
         if isinstance(self.vector_quantization, FiniteScalarQuantizer):
             raise VqvaeHipError("finite scalar quantization has no codebook to initialise")
+        if isinstance(self.vector_quantization, LookupFreeQuantizer):
+            raise VqvaeHipError("lookup-free quantization has no codebook to initialise")
         _need_hip_f32(x, "VQVAE.init_codebook_")
         if C_hip.get_conv_backend() != "hip":
             raise VqvaeHipError("VQVAE.init_codebook_ runs on the HIP conv backend: there is no fallback")
@@ -1126,6 +1214,10 @@ class VQVAE(nn.Module):
             _need_hip_f32(x, "VQVAE.encode")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False)[3]
+        if isinstance(self.vector_quantization, LookupFreeQuantizer):
+            _need_hip_f32(x, "VQVAE.encode")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False, want_loss=False)[3]
         if (C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32
                 or self.vector_quantization.cosine_sim):
             # (cosine_sim: encoder -> l2norm_rows -> index-only quantizer, the training forward's indices bit for bit)
@@ -1173,10 +1265,12 @@ class VQVAE(nn.Module):
         return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
 
     def _decode_fsq(self, idx, B, H, W, validate):
-        """fsq_levels: the indices' rows (functional.fsq_decode_indices), then the decoder.  The no-grad forward and decode_indices
-        both end here."""
+        """fsq_levels / lookup_free: the indices' rows (functional.fsq_decode_indices / lfq_decode_indices), then the decoder.  The
+        no-grad forward and decode_indices both end here."""
         from . import conv as C_hip
         vq = self.vector_quantization
+        if isinstance(vq, LookupFreeQuantizer):
+            return C_hip.decoder_forward(self.decoder, vq.decode(idx, B, H, W, rowmajor=True, validate=validate), rowmajor_in=True)
         z_q = F_hip.fsq_decode_indices(idx.contiguous().view(-1).to(torch.int64), vq.project_out.weight.detach(),
                                        vq.project_out.bias.detach(), vq.levels, B, H, W, rowmajor=True, validate=validate)
         return C_hip.decoder_forward(self.decoder, z_q, rowmajor_in=True)
@@ -1212,7 +1306,7 @@ class VQVAE(nn.Module):
             return self._decode_grouped(idx, B, H, W)
         if idx.numel() != B * H * W:
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
-        if isinstance(self.vector_quantization, FiniteScalarQuantizer):
+        if isinstance(self.vector_quantization, (FiniteScalarQuantizer, LookupFreeQuantizer)):
             return self._decode_fsq(idx, B, H, W, validate=validate)
         if self.vector_quantization.cosine_sim:
             return self._decode_codes(idx, B, H, W, validate=validate)

@@ -8,6 +8,9 @@
     `GroupedStraightThrough` grouped (product) quantization's gradients (vqvae_vq_grouped_backward_f32) and its autograd pairing
   * `fsq_backward`,
     `FSQStraightThrough`    finite scalar quantization's gradients (vqvae_fsq_backward_f32) and its autograd pairing
+  * `lfq_backward`,
+    `LFQStraightThrough`    lookup-free quantization's gradients, its entropy loss included (vqvae_lfq_backward_f32), and its
+                            autograd pairing
   * `step_losses`           `recon_loss`, `loss` and `perplexity` of main.py:75-76,81-83 in one fused
                             reduction, returned as ONE 3-element device tensor (one D2H copy per step)
 
@@ -429,3 +432,79 @@ class FSQStraightThrough(torch.autograd.Function):
         gz, gp = fsq_backward(z, g_zq, w_in, b_in, w_out, ctx.levels, rowmajor=ctx.rowmajor, need_z=need_z, need_params=need_p)
         gp = gp if gp is not None else (None,) * 4
         return (gz,) + tuple(g if n else None for g, n in zip(gp, ctx.needs_input_grad[1:5])) + (None, None)
+
+
+# ---- lookup-free quantization (csrc/vq_lfq.hip) ----------------------------------------------------------------------------------
+
+def lfq_backward(z_e, grad_zq, grad_loss, avg, w_in, b_in, w_out, n_e, *, beta=0.25, entropy_weight=0.1, diversity_gamma=1.0,
+                 inv_temperature=100.0, rowmajor=False, need_z=True, need_params=True, workspace=None):
+    """Gradients of functional.lfq_forward's z_q and loss (vqvae_lfq_backward_f32): rounding is straight-through, the commitment and
+    entropy terms are differentiated through the factorised softmax.  grad_zq (z_e's shape) may be None (zero); grad_loss is a device
+    scalar or None (one); avg is the forward's (K,) fp64, or None when the loss has no gradient.
+    -> (grad_z or None, (grad_w_in, grad_b_in, grad_w_out, grad_b_out) or None), in fixed-order fp64 sums."""
+    F_hip._check_dev("z_e", z_e)
+    if grad_zq is not None:
+        F_hip._check_dev("grad_zq", grad_zq)
+    if z_e.dim() != 4 or (grad_zq is not None and grad_zq.shape != z_e.shape):
+        raise ValueError("z_e must be 4-D and grad_zq must have its shape")
+    if not (need_z or need_params):
+        return None, None
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    d = F_hip._lfq_bits(n_e)
+    w_in, b_in, w_out = F_hip._fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out)
+    if avg is not None:
+        F_hip._check_dev("avg", avg, torch.float64)
+        if avg.numel() != n_e:
+            raise ValueError("avg must hold n_e values")
+        avg = avg.contiguous()
+    if grad_loss is not None:
+        F_hip._check_dev("grad_loss", grad_loss)
+        grad_loss = grad_loss.contiguous()
+    z_e = z_e.contiguous()
+    grad_zq = grad_zq.contiguous() if grad_zq is not None else None
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        gz = torch.empty_like(z_e) if need_z else None
+        gp = None
+        if need_params:
+            gp = (torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out), torch.empty((D,), dtype=torch.float32, device=dev))
+        ws = workspace if workspace is not None else F_hip.lfq_workspace(B * H * W, D, d, dev)
+        p = [t.data_ptr() for t in gp] if gp is not None else [None] * 4
+        _lib.check(_lib.load().vqvae_lfq_backward_f32(
+            z_e.data_ptr(), grad_zq.data_ptr() if grad_zq is not None else None, grad_loss.data_ptr() if grad_loss is not None else None,
+            avg.data_ptr() if avg is not None else None, w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), d, B, D, H, W,
+            F_hip.VQ_ROWMAJOR if rowmajor else 0, beta, entropy_weight, diversity_gamma, inv_temperature,
+            gz.data_ptr() if need_z else None, *p, ws.data_ptr(), ws.numel(), _sp(z_e)))
+    return gz, gp
+
+
+class LFQStraightThrough(torch.autograd.Function):
+    """(z_e, w_in, b_in, w_out, b_out) -> (z_q, loss, perplexity, idx, hist, losses, avg) of lookup-free quantization: z_q and loss
+    (0-dim) differentiable with respect to z_e and the four parameters, the rest not.
+    apply(z_e, w_in, b_in, w_out, b_out, n_e, (beta, entropy_weight, diversity_gamma, inv_temperature), rowmajor)."""
+
+    @staticmethod
+    def forward(ctx, z_e, w_in, b_in, w_out, b_out, n_e, weights, rowmajor):
+        z = z_e.detach().contiguous()
+        params = [t.detach().contiguous() for t in (w_in, b_in, w_out, b_out)]
+        beta, we, gamma, inv_t = (float(v) for v in weights)
+        z_q, perplexity, idx, hist, losses, avg = F_hip.lfq_forward(
+            z, *params, n_e, beta=beta, entropy_weight=we, diversity_gamma=gamma, inv_temperature=inv_t, rowmajor=rowmajor)
+        ctx.save_for_backward(z, *params[:3], avg)
+        ctx.n_e, ctx.weights, ctx.rowmajor = n_e, (beta, we, gamma, inv_t), rowmajor
+        loss = losses[0].clone()
+        ctx.mark_non_differentiable(perplexity, idx, hist, losses, avg)
+        return z_q, loss, perplexity, idx, hist, losses, avg
+
+    @staticmethod
+    def backward(ctx, g_zq, g_loss, *_unused):
+        z, w_in, b_in, w_out, avg = ctx.saved_tensors
+        need_z, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
+        beta, we, gamma, inv_t = ctx.weights
+        if g_zq is None and g_loss is None:
+            return (None,) * 8
+        gl = g_loss.to(torch.float32).reshape(()) if g_loss is not None else None
+        gz, gp = lfq_backward(z, g_zq, gl, avg if g_loss is not None else None, w_in, b_in, w_out, ctx.n_e, beta=beta, entropy_weight=we,
+                              diversity_gamma=gamma, inv_temperature=inv_t, rowmajor=ctx.rowmajor, need_z=need_z, need_params=need_p)
+        gp = gp if gp is not None else (None,) * 4
+        return (gz,) + tuple(g if n else None for g, n in zip(gp, ctx.needs_input_grad[1:5])) + (None, None, None)
