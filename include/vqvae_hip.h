@@ -408,6 +408,32 @@ VQVAE_API int vqvae_fsq_backward_f32(const float *z_e, const float *grad_zq, con
                                      float *grad_z, float *grad_w_in, float *grad_b_in, float *grad_w_out, float *grad_b_out,
                                      void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* The per-row linear map of latent rows, y = W x + b, forward and backward (csrc/vq_linear.hip; its header is the numeric
+ * contract): the projections of a factorized (low-dimensional) codebook (ViT-VQGAN, arXiv 2110.04627 section 3.2; `codebook_dim` in
+ * vector-quantize-pytorch).  x and grad_x have Cin channels, y and grad_y Cout channels, in the same layout; w is (Cout, Cin)
+ * row-major (nn.Linear.weight), b is (Cout).
+ *     y[n][j]      = float(double(b[j]) + sum_c double(w[j][c]) double(x[n][c]))    fp64 from b[j], c ascending, one rounding to fp32
+ *     grad_x[n][c] = float(sum_j double(w[j][c]) double(grad_y[n][j]))              fp64 from 0.0, j ascending, one rounding
+ *     grad_w[j][c] = float(sum_n double(grad_y[n][j]) double(x[n][c])),  grad_b[j] = float(sum_n double(grad_y[n][j])), in FSQ's
+ *                    order: blocks of 256 consecutive rows; inside a block one row after the other from 0.0; then the blocks in
+ *                    order from 0.0, by a second launch; one rounding
+ *   The order depends on N alone: every output has the same bits in both layouts, on the 16-byte and the element path, in every
+ *   run and in a graph replay; there is no floating-point atomic.  The product of two fp32 values is exact in fp64, so the kernels'
+ *   fused multiply-adds round as a multiplication and an addition do.  A non-finite x or grad_y stays in its own row of y / grad_x;
+ *   the parameter gradients follow IEEE through the stated order.
+ *   Rows and layouts are vqvae_vq_forward_f32's: N = B H W rows, (B,C,H,W) maps, or (N,C) rows with VQVAE_VQ_ROWMAJOR, the only flag.
+ *   backward: any of grad_x, grad_w, grad_b may be NULL (not all three); `workspace` (vqvae_linear_rows_backward_workspace_bytes; 0 =
+ *   outside the envelope) is needed for grad_w / grad_b only (VQVAE_ERR_WORKSPACE when it is missing or too small).
+ *   No host sync, no allocation, no memset, every launch on `stream` in one chain: capturable.
+ *   Envelope: 1 <= Cin, Cout <= 256, 1 <= N <= INT32_MAX.  VQVAE_ERR_UNSUPPORTED outside it, for a pointer that is not 4-byte aligned
+ *   (workspace: 8-byte) and for an output that overlaps an input or another output.                                              */
+VQVAE_API int vqvae_linear_rows_forward_f32(const float *x, const float *w, const float *b, int64_t B, int Cin, int H, int W,
+                                            int Cout, int flags, float *y, vqvae_stream_t stream);
+VQVAE_API size_t vqvae_linear_rows_backward_workspace_bytes(int64_t N, int Cin, int Cout);
+VQVAE_API int vqvae_linear_rows_backward_f32(const float *x, const float *grad_y, const float *w, int64_t B, int Cin, int H, int W,
+                                             int Cout, int flags, float *grad_x, float *grad_w, float *grad_b, void *workspace,
+                                             size_t workspace_bytes, vqvae_stream_t stream);
+
 /* Lookup-free quantization (csrc/vq_lfq.hip; its header is the numeric contract): the codebook is {-1, +1}^d, K = 2^d (MAGVIT-v2,
  * arXiv 2310.05737 section 3.1; vector-quantize-pytorch's LFQ).  A row is projected to d channels (w_in (d, D), b_in (d)), every
  * channel keeps its sign (c_j = +1 where y_j > 0, else -1), and the signs are projected back (w_out (D, d), b_out (D)); the

@@ -13,6 +13,7 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--rotation_trick]                             (off by default: the rotation-trick gradient)
                                      [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
                                      [--fsq_levels 8,5,5,5 --n_embeddings 1000]     (off by default: finite scalar quantization)
+                                     [--codebook_dim 8]                             (off by default: factorized codes)
                                      [--lookup_free --n_embeddings 1024 [--lfq_entropy_weight 0.1 --lfq_diversity_gamma 1 --lfq_inv_temperature 100]]
                                                                                     (off by default: lookup-free quantization)
                                      [--codebook_groups G]                          (off by default: grouped quantization, G codebooks)
@@ -80,6 +81,8 @@ def parse(argv=None):
     p.add_argument("--lfq_entropy_weight", type=float, default=argparse.SUPPRESS)
     p.add_argument("--lfq_diversity_gamma", type=float, default=argparse.SUPPRESS)
     p.add_argument("--lfq_inv_temperature", type=float, default=argparse.SUPPRESS)
+    # opt-in factorized codes (codebook_dim=d: the codebook is searched in d channels between two projections); absent unless given
+    p.add_argument("--codebook_dim", type=int, default=argparse.SUPPRESS, metavar="d")
     args = p.parse_args(argv)
     ema_kw = {}
     if hasattr(args, "lookup_free"):
@@ -87,6 +90,8 @@ def parse(argv=None):
     for name in ("lfq_entropy_weight", "lfq_diversity_gamma", "lfq_inv_temperature"):
         if hasattr(args, name):
             ema_kw[name] = getattr(args, name)
+    if hasattr(args, "codebook_dim"):
+        ema_kw["codebook_dim"] = args.codebook_dim
     if hasattr(args, "codebook_groups"):
         ema_kw["codebook_groups"] = args.codebook_groups
     if hasattr(args, "fsq_levels"):

@@ -684,3 +684,86 @@ def lfq_decode_indices(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tens
         _lib.check(_lib.load().vqvae_lfq_decode_indices_f32(idx.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), d, B, D, H, W,
                                                             VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), _stream_ptr(idx)))
     return out
+
+
+# ---- the per-row linear map: a factorized codebook's projections (csrc/vq_linear.hip) --------------------------------------------
+
+def _linear_dims(name, x, rowmajor):
+    """-> (B, C, H, W, rowmajor) of a 4-D map in the quantizer's layouts, or of a 2-D (K, C) tensor as K row-major rows"""
+    return _l2norm_dims(name, x, rowmajor)
+
+
+def _linear_weight(w, Cin=None):
+    _check_dev("w", w)
+    if w.dim() != 2 or (Cin is not None and w.shape[1] != Cin):
+        raise ValueError(f"w must be (Cout, Cin = {Cin}) as nn.Linear holds it, got {tuple(w.shape)}")
+    return w.contiguous()
+
+
+def _linear_like(x, C, rm):
+    """an empty tensor of x's rows and layout with C channels"""
+    if x.dim() == 2:
+        shape = (x.shape[0], C)
+    elif rm:
+        shape = (*x.shape[:3], C)
+    else:
+        shape = (x.shape[0], C, *x.shape[2:])
+    return torch.empty(shape, dtype=torch.float32, device=x.device)
+
+
+def linear_rows(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, rowmajor: bool = False) -> torch.Tensor:
+    """y = W x + b on every row (vqvae_linear_rows_forward_f32): an fp64 sum from b in ascending channel order, rounded once.
+    x: (B,Cin,H,W), (B,H,W,Cin) when rowmajor, or a 2-D (K, Cin) tensor -- rows as they stand; w (Cout, Cin), b (Cout) as nn.Linear
+    holds them.  -> y in x's layout with Cout channels.  The numeric contract is the header of csrc/vq_linear.hip."""
+    B, Cin, H, W, rm = _linear_dims("x", x, rowmajor)
+    w = _linear_weight(w, Cin)
+    _check_dev("b", b)
+    Cout = w.shape[0]
+    if tuple(b.shape) != (Cout,):
+        raise ValueError(f"b must be ({Cout},), got {tuple(b.shape)}")
+    x, b = x.contiguous(), b.contiguous()
+    with torch.cuda.device(x.device):
+        y = _linear_like(x, Cout, rm)
+        _lib.check(_lib.load().vqvae_linear_rows_forward_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), B, Cin, H, W, Cout,
+                                                             VQ_ROWMAJOR if rm else 0, y.data_ptr(), _stream_ptr(x)))
+    return y
+
+
+def linear_rows_backward_workspace(N: int, Cin: int, Cout: int, device) -> torch.Tensor:
+    """workspace of linear_rows_backward's parameter gradients: one fp64 record per block of 256 rows"""
+    n = _lib.load().vqvae_linear_rows_backward_workspace_bytes(N, Cin, Cout)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"linear_rows backward: N={N}, Cin={Cin}, Cout={Cout} not supported (1 <= Cin, Cout <= 256, "
+                                 "1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def linear_rows_backward(x: torch.Tensor, grad_y: torch.Tensor, w: torch.Tensor, *, rowmajor: bool = False,
+                         want=(True, True, True), workspace: torch.Tensor | None = None):
+    """Gradients of linear_rows (vqvae_linear_rows_backward_f32) from its input x and the upstream grad_y (y's shape):
+    -> (grad_x, grad_w, grad_b), None where `want` says so (not all three).  grad_w and grad_b are fp64 sums over the rows in an
+    order that depends on the number of rows alone: the same bits in both layouts and in every run."""
+    B, Cin, H, W, rm = _linear_dims("x", x, rowmajor)
+    w = _linear_weight(w, Cin)
+    Cout = w.shape[0]
+    _check_dev("grad_y", grad_y)
+    x, grad_y = x.contiguous(), grad_y.contiguous()
+    y_shape = (x.shape[0], Cout) if x.dim() == 2 else ((*x.shape[:3], Cout) if rm else (x.shape[0], Cout, *x.shape[2:]))
+    if tuple(grad_y.shape) != y_shape:
+        raise ValueError(f"grad_y must have y's shape {y_shape}, got {tuple(grad_y.shape)}")
+    want_x, want_w, want_b = (bool(v) for v in want)
+    if not (want_x or want_w or want_b):
+        raise ValueError("at least one gradient must be wanted")
+    dev = x.device
+    with torch.cuda.device(dev):
+        gx = torch.empty_like(x) if want_x else None
+        gw = torch.empty_like(w) if want_w else None
+        gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_b else None
+        ws = None
+        if want_w or want_b:
+            ws = workspace if workspace is not None else linear_rows_backward_workspace(B * H * W, Cin, Cout, dev)
+        _lib.check(_lib.load().vqvae_linear_rows_backward_f32(
+            x.data_ptr(), grad_y.data_ptr(), w.data_ptr(), B, Cin, H, W, Cout, VQ_ROWMAJOR if rm else 0,
+            gx.data_ptr() if want_x else None, gw.data_ptr() if want_w else None, gb.data_ptr() if want_b else None,
+            ws.data_ptr() if ws is not None else None, ws.numel() * ws.element_size() if ws is not None else 0, _stream_ptr(x)))
+    return gx, gw, gb

@@ -313,6 +313,105 @@ class VectorQuantizerEMA(VectorQuantizer):
         return out
 
 
+class FactorizedVectorQuantizer(VectorQuantizer):
+    """VectorQuantizer with factorized (low-dimensional) codes (ViT-VQGAN, arXiv 2110.04627 section 3.2; `codebook_dim` in
+    vector-quantize-pytorch): a latent row of `dim` channels is projected to `codebook_dim` channels (`project_in`), the codebook is
+    searched in that small space, and the chosen code is projected back to `dim` channels (`project_out`).  The quantizer in between
+    is VectorQuantizer as it stands, on narrower rows (e_dim = codebook_dim), with every option it has; the loss and the perplexity
+    are its own -- the loss is taken in the low-dimensional space.  Both projections run on the HIP kernels of csrc/vq_linear.hip.
+
+    State: `embedding.weight` (n_e, codebook_dim), `project_in` = nn.Linear(dim, codebook_dim), `project_out` =
+    nn.Linear(codebook_dim, dim), and nothing else.  Drawn in this order: the codebook, uniform(-1/K, 1/K) as VectorQuantizer draws
+    it; then project_in; then project_out (both as nn.Linear initialises itself)."""
+
+    _INNER = VectorQuantizer                  # the class whose quantize / init_codebook_ run on the projected rows
+
+    def __init__(self, n_e, dim, codebook_dim, beta, *, rotation_trick=False, cosine_sim=False):
+        dim, codebook_dim = self._check_dims(dim, codebook_dim)
+        super().__init__(n_e, codebook_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+        self._init_projections(dim, codebook_dim)
+
+    @staticmethod
+    def _check_dims(dim, codebook_dim):
+        for name, v in (("dim", dim), ("codebook_dim", codebook_dim)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 256:
+                raise ValueError(f"{name} must be an int in [1, 256], got {v!r}")
+        return dim, codebook_dim
+
+    def _init_projections(self, dim, codebook_dim):
+        self.dim, self.codebook_dim = dim, codebook_dim
+        self.project_in = nn.Linear(dim, codebook_dim)
+        self.project_out = nn.Linear(codebook_dim, dim)
+
+    def invalidate(self):
+        """VectorQuantizer.invalidate, and the decoded codebook of codebook() is forgotten too."""
+        super().invalidate()
+        _cache.drop(self, "factorized_codebook")
+
+    @staticmethod
+    def _project(x, lin, rowmajor):
+        """lin on every row of x: LinearRows while a graph is recorded (x, the weight and the bias get their gradients from the HIP
+        backward), functional.linear_rows otherwise"""
+        w, b = lin.weight, lin.bias
+        if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad):
+            from .training import LinearRows
+            return LinearRows.apply(x, w, b, rowmajor)
+        return F_hip.linear_rows(x, w.detach(), b.detach(), rowmajor=rowmajor)
+
+    def quantize(self, z, *, rowmajor=False, want_zq=True):
+        """-> (loss, z_q, perplexity, min_encoding_indices, hist): y = project_in(z); the inner quantizer's quantize of y, in the same
+        layout (with EMA: its update from y, or y^ with cosine_sim, in training mode); z_q = project_out of its z_q (None without
+        want_zq where no graph is recorded)."""
+        _need_hip_f32(z, type(self).__name__)
+        y = self._project(z, self.project_in, rowmajor)
+        loss, zq_low, perplexity, idx, hist = self._INNER.quantize(self, y, rowmajor=rowmajor, want_zq=want_zq)
+        z_q = self._project(zq_low, self.project_out, rowmajor) if zq_low is not None else None
+        return loss, z_q, perplexity, idx, hist
+
+    @torch.no_grad()
+    def codes(self):
+        """the (K, codebook_dim) table that is searched: `embedding.weight`, l2-normalised with cosine_sim"""
+        return self.normalized_codebook() if self.cosine_sim else self.embedding.weight.detach()
+
+    @torch.no_grad()
+    def codebook(self):
+        """the (K, dim) decoded rows project_out(codes()): what decode_indices gathers from.  Computed once per (data_ptr, _version)
+        of `embedding.weight`, `project_out.weight` and `project_out.bias`; invalidate() (after a write through `.data`) and
+        .to() / .cuda() drop it."""
+        ts = (self.embedding.weight, self.project_out.weight, self.project_out.bias)
+        _need_hip_f32(ts[0], type(self).__name__ + ".codebook")
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (ts[0].device, self.cosine_sim)
+        hit = _cache.side(self).get("factorized_codebook")
+        if hit is None or hit[0] != key:
+            hit = (key, F_hip.linear_rows(self.codes(), ts[1].detach(), ts[2].detach()))
+            _cache.side(self)["factorized_codebook"] = hit
+        return hit[1]
+
+    @torch.no_grad()
+    def init_codebook_(self, z, iters=10, generator=None, *, rowmajor=False):
+        """The inner quantizer's init_codebook_ on y = project_in(z): k-means of the projected rows (of y^ with cosine_sim)."""
+        _need_hip_f32(z, "init_codebook_")
+        y = F_hip.linear_rows(z.detach(), self.project_in.weight.detach(), self.project_in.bias.detach(), rowmajor=rowmajor)
+        return self._INNER.init_codebook_(self, y, iters, generator, rowmajor=rowmajor)
+
+
+class FactorizedVectorQuantizerEMA(FactorizedVectorQuantizer, VectorQuantizerEMA):
+    """FactorizedVectorQuantizer whose (n_e, codebook_dim) codebook follows exponential moving averages: VectorQuantizerEMA between
+    the two projections.  State: FactorizedVectorQuantizer's, and the buffers `ema_cluster_size` (K,) and `ema_w` (K, codebook_dim).
+    The update runs from y = project_in(z) (from y^ with cosine_sim) and that forward's indices, in training mode only, after the
+    inner quantizer's outputs are formed; the projections are trained by their gradients.  With init_codebook_ the EMA state
+    continues from the clusters, as VectorQuantizerEMA's does."""
+
+    _INNER = VectorQuantizerEMA
+
+    def __init__(self, n_e, dim, codebook_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *,
+                 rotation_trick=False, cosine_sim=False):
+        dim, codebook_dim = self._check_dims(dim, codebook_dim)
+        VectorQuantizerEMA.__init__(self, n_e, codebook_dim, beta, decay, eps, restart_threshold, generator,
+                                    rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+        self._init_projections(dim, codebook_dim)
+
+
 class ResidualVectorQuantizer(nn.Module):
     """Residual quantization (RQ-VAE, arXiv 2203.01941; SoundStream's RVQ): n_q codebooks quantize the same latent position, each
     stage -- the reference's quantizer as written -- what the stage before it left over; z_q is z + (sum of the stages' codes - z)
@@ -810,8 +909,16 @@ class VQVAE(nn.Module):
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
                  shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1,
-                 lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0):
+                 lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0, codebook_dim=None):
         super().__init__()
+        if codebook_dim is not None:
+            # factorized codes: the plain or the EMA quantizer between two projections, with the one-stage quantizers' options
+            FactorizedVectorQuantizer._check_dims(embedding_dim, codebook_dim)
+            for name, on in (("n_quantizers > 1", n_quantizers != 1), ("shared_codebook", shared_codebook),
+                             ("codebook_groups > 1", codebook_groups != 1), ("fsq_levels", fsq_levels is not None),
+                             ("lookup_free", lookup_free)):
+                if on:
+                    raise ValueError(f"codebook_dim (factorized codes) does not combine with {name}")
         if lookup_free:
             # lookup-free quantization: the codebook is {-1, +1}^d; beta weighs its commitment term
             for name, on in (("ema_decay", ema_decay is not None), ("restart_threshold", restart_threshold is not None),
@@ -873,6 +980,17 @@ class VQVAE(nn.Module):
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
             self.vector_quantization = ResidualVectorQuantizer(n_quantizers, n_embeddings, embedding_dim, beta,
                                                                shared_codebook=shared_codebook)
+        elif codebook_dim is not None:
+            if ema_decay is None:
+                if restart_threshold is not None:
+                    raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
+                self.vector_quantization = FactorizedVectorQuantizer(n_embeddings, embedding_dim, codebook_dim, beta,
+                                                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+            else:
+                self.vector_quantization = FactorizedVectorQuantizerEMA(n_embeddings, embedding_dim, codebook_dim, beta,
+                                                                        decay=ema_decay, eps=ema_eps,
+                                                                        restart_threshold=restart_threshold,
+                                                                        rotation_trick=rotation_trick, cosine_sim=cosine_sim)
         elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
@@ -929,6 +1047,9 @@ class VQVAE(nn.Module):
             raise VqvaeHipError("the fused whole-path entries have no lookup-free quantizer: LFQ models run layer by layer")
         if isinstance(self.vector_quantization, GroupedVectorQuantizer):
             raise VqvaeHipError("the fused whole-path entries quantize whole rows: grouped models run layer by layer")
+        if isinstance(self.vector_quantization, FactorizedVectorQuantizer):
+            raise VqvaeHipError("the fused whole-path entries search a codebook of embedding_dim channels: factorized models "
+                                "(codebook_dim) run layer by layer")
         params = dict(self.named_parameters(remove_duplicate=False))
         n_res = self.encoder.conv_stack[5].n_res_layers
         tensors = {}
@@ -1139,6 +1260,19 @@ class VQVAE(nn.Module):
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
             return embedding_loss, self._decode_fsq(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2], validate=False), perplexity
+        if isinstance(vq, FactorizedVectorQuantizer):
+            # factorized codes: the per-layer path too (the fused entries must never see a (K, codebook_dim) codebook).  The decoder
+            # takes rows of the decoded codebook through the helper decode_indices uses: decode_indices(encode(x)) is this x_hat
+            # bit for bit -- the map is per row, so project_out(E[idx]) and project_out(E)[idx] have the same bits.  (The training
+            # forward decodes project_out(y + (e - y)).)
+            _need_hip_f32(x, "VQVAE.forward")
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            # (an EMA quantizer in training mode moves the codebook inside quantize: every output is the codebook's BEFORE the
+            # update, so the decoded codebook is taken first)
+            before = vq.codebook() if isinstance(vq, VectorQuantizerEMA) and vq.training else None
+            embedding_loss, _, perplexity, idx, _ = vq.quantize(z_e, rowmajor=True, want_zq=False)
+            return embedding_loss, self._decode_factorized(idx, z_e.shape[0], z_e.shape[1], z_e.shape[2], validate=False,
+                                                           codebook=before), perplexity
         ema = isinstance(vq, VectorQuantizerEMA)
         # (an EMA quantizer in training mode updates its codebook from z_e: the per-layer path below materialises it; so does a
         # cosine_sim quantizer, whose rows are normalised between the encoder and the search -- the fused whole-path entries
@@ -1218,6 +1352,13 @@ class VQVAE(nn.Module):
             _need_hip_f32(x, "VQVAE.encode")
             z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
             return self.vector_quantization.quantize(z_e, rowmajor=True, want_zq=False, want_loss=False)[3]
+        if isinstance(self.vector_quantization, FactorizedVectorQuantizer):
+            # encoder -> linear_rows -> (l2norm_rows) -> index-only quantizer (VectorQuantizer's quantize: never an EMA update)
+            _need_hip_f32(x, "VQVAE.encode")
+            vq = self.vector_quantization
+            z_e = C_hip.encoder_forward(self.encoder, x, pre_quant=self.pre_quantization_conv)
+            y = F_hip.linear_rows(z_e, vq.project_in.weight.detach(), vq.project_in.bias.detach(), rowmajor=True)
+            return VectorQuantizer.quantize(vq, y, rowmajor=True, want_zq=False)[3]
         if (C_hip.get_conv_backend() != "hip" or not x.is_cuda or x.dtype != torch.float32
                 or self.vector_quantization.cosine_sim):
             # (cosine_sim: encoder -> l2norm_rows -> index-only quantizer, the training forward's indices bit for bit)
@@ -1254,6 +1395,16 @@ class VQVAE(nn.Module):
         from . import conv as C_hip
         z_q = F_hip.vq_decode_indices(idx.contiguous().view(-1).to(torch.int64), self.vector_quantization.normalized_codebook(),
                                       B, H, W, validate=validate)
+        return C_hip.decoder_forward(self.decoder, z_q.detach(), rowmajor_in=False)
+
+    def _decode_factorized(self, idx, B, H, W, validate, codebook=None):
+        """codebook_dim: rows of the decoded codebook project_out(codes()) (vq_decode_indices(idx, codebook())), then the decoder.
+        The no-grad forward and decode_indices both end here.  codebook: the decoded codebook the indices belong to, where it has
+        moved since (the training-mode EMA forward)."""
+        from . import conv as C_hip
+        z_q = F_hip.vq_decode_indices(idx.contiguous().view(-1).to(torch.int64),
+                                      codebook if codebook is not None else self.vector_quantization.codebook(), B, H, W,
+                                      validate=validate)
         return C_hip.decoder_forward(self.decoder, z_q.detach(), rowmajor_in=False)
 
     def _decode_grouped(self, idx, B, H, W):
@@ -1308,6 +1459,8 @@ class VQVAE(nn.Module):
             raise ValueError(f"expected {B * H * W} indices, got {idx.numel()}")
         if isinstance(self.vector_quantization, (FiniteScalarQuantizer, LookupFreeQuantizer)):
             return self._decode_fsq(idx, B, H, W, validate=validate)
+        if isinstance(self.vector_quantization, FactorizedVectorQuantizer):
+            return self._decode_factorized(idx, B, H, W, validate=validate)
         if self.vector_quantization.cosine_sim:
             return self._decode_codes(idx, B, H, W, validate=validate)
         if C_hip.get_conv_backend() != "hip" or not idx.is_cuda:

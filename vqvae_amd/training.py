@@ -11,6 +11,8 @@
   * `lfq_backward`,
     `LFQStraightThrough`    lookup-free quantization's gradients, its entropy loss included (vqvae_lfq_backward_f32), and its
                             autograd pairing
+  * `LinearRows`            the per-row linear map y = W x + b (vqvae_linear_rows_forward_f32 / _backward_f32) under autograd: the
+                            projections of the factorized quantizers
   * `step_losses`           `recon_loss`, `loss` and `perplexity` of main.py:75-76,81-83 in one fused
                             reduction, returned as ONE 3-element device tensor (one D2H copy per step)
 
@@ -508,3 +510,27 @@ class LFQStraightThrough(torch.autograd.Function):
                               diversity_gamma=gamma, inv_temperature=inv_t, rowmajor=ctx.rowmajor, need_z=need_z, need_params=need_p)
         gp = gp if gp is not None else (None,) * 4
         return (gz,) + tuple(g if n else None for g, n in zip(gp, ctx.needs_input_grad[1:5])) + (None, None, None)
+
+
+# ---- the per-row linear map: a factorized codebook's projections (csrc/vq_linear.hip) --------------------------------------------
+
+class LinearRows(torch.autograd.Function):
+    """x -> W x + b on every row, forward and backward on the HIP kernels (functional.linear_rows / linear_rows_backward): differentiable
+    with respect to x, w and b, and the backward asks only for the gradients that needs_input_grad names.
+    apply(x, w, b, rowmajor=False); x: a 4-D map in the quantizer's layouts or a 2-D (K, Cin) tensor."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, rowmajor=False):
+        x_, w_ = x.detach().contiguous(), w.detach().contiguous()
+        y = F_hip.linear_rows(x_, w_, b.detach(), rowmajor=rowmajor)
+        ctx.save_for_backward(x_, w_)
+        ctx.rowmajor = rowmajor
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[:3])
+        if not any(want):
+            return None, None, None, None
+        return F_hip.linear_rows_backward(x, g, w, rowmajor=ctx.rowmajor, want=want) + (None,)
