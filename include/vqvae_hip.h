@@ -434,6 +434,33 @@ VQVAE_API int vqvae_linear_rows_backward_f32(const float *x, const float *grad_y
                                              int Cout, int flags, float *grad_x, float *grad_w, float *grad_b, void *workspace,
                                              size_t workspace_bytes, vqvae_stream_t stream);
 
+/* The orthogonal regularization loss of a codebook and its gradient (csrc/vq_orthogonal.hip; its header is the numeric contract):
+ * L = |E^ E^T|_F^2 / M^2 - 1 / M over the M selected codes (arXiv 2112.00384 section 3.2; `orthogonal_reg_weight`,
+ * `orthogonal_reg_active_codes_only`, `orthogonal_reg_max_codes` in vector-quantize-pytorch).  `rows` (K, D) are taken as they stand:
+ * the caller normalises.  One K^2 D pass, no (K, K) array.  Every line is one IEEE operation in the stated precision:
+ *     candidate(k) = hist == NULL or hist[k] > 0;  under a cap (uniforms != NULL and max_codes > 0) the max_codes candidates that
+ *                    come first in the order (u_k ascending, then k ascending) are kept; selected[k] is 0 / 1, *count = M
+ *     G_ij = sum_c double(n_ic) double(n_jc)                 from 0.0, c ascending
+ *     R_i  = sum_{j selected} fl(G_ij G_ij),  V_ic = sum_{j selected} fl(G_ij double(n_jc))      from 0.0, j ascending, for selected
+ *            i; 0.0 for an unselected i
+ *     T    = the R_i of blocks of 256 consecutive codes added in ascending i from 0.0, then the blocks' sums in ascending order
+ *            from 0.0: an order that depends on K alone
+ *     loss = float(T / (double(M) double(M)) - 1.0 / double(M)),  0 where M = 0
+ *     grad_rows[i][c] = float((double(g) (4.0 / (double(M) double(M)))) V_ic) for selected i, +0.0 otherwise; g = *grad_loss, or 1
+ *   saved (K, D) fp64 receives V, or is NULL (the V sums are then not formed).  A non-finite value in a selected row makes the
+ *   loss and the selected rows' gradients non-finite (which NaN is unspecified) and never reaches an unselected row.
+ *   No host sync, no allocation, no memset, no atomic, one chain of launches on `stream`: capturable; the same bits in every run,
+ *   at every pointer alignment and in a graph replay.
+ *   Envelope: 1 <= K <= 16384, 1 <= D <= 256 (vqvae_vq_orthogonal_workspace_bytes: 0 outside it).  VQVAE_ERR_UNSUPPORTED outside
+ *   it, for flags != 0, for a pointer that is not 4-byte aligned (saved, workspace: 8-byte) and for an output that overlaps an input
+ *   or another output; VQVAE_ERR_WORKSPACE for a missing or short workspace.                                                     */
+VQVAE_API size_t vqvae_vq_orthogonal_workspace_bytes(int K, int D);
+VQVAE_API int vqvae_vq_orthogonal_forward_f32(const float *rows, const int32_t *hist, const float *uniforms, int max_codes, int K,
+                                              int D, int flags, float *loss, int32_t *count, int32_t *selected, double *saved,
+                                              void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_vq_orthogonal_backward_f32(const double *saved, const int32_t *selected, const int32_t *count,
+                                               const float *grad_loss, int K, int D, float *grad_rows, vqvae_stream_t stream);
+
 /* Lookup-free quantization (csrc/vq_lfq.hip; its header is the numeric contract): the codebook is {-1, +1}^d, K = 2^d (MAGVIT-v2,
  * arXiv 2310.05737 section 3.1; vector-quantize-pytorch's LFQ).  A row is projected to d channels (w_in (d, D), b_in (d)), every
  * channel keeps its sign (c_j = +1 where y_j > 0, else -1), and the signs are projected back (w_out (D, d), b_out (D)); the

@@ -14,6 +14,8 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--cosine_sim]                                 (off by default: the cosine-similarity codebook)
                                      [--fsq_levels 8,5,5,5 --n_embeddings 1000]     (off by default: finite scalar quantization)
                                      [--codebook_dim 8]                             (off by default: factorized codes)
+                                     [--orthogonal_reg_weight W [--orthogonal_reg_active_codes_only] [--orthogonal_reg_max_codes M]]
+                                                                                    (off by default: orthogonal regularization of the codebook)
                                      [--lookup_free --n_embeddings 1024 [--lfq_entropy_weight 0.1 --lfq_diversity_gamma 1 --lfq_inv_temperature 100]]
                                                                                     (off by default: lookup-free quantization)
                                      [--codebook_groups G]                          (off by default: grouped quantization, G codebooks)
@@ -83,8 +85,15 @@ def parse(argv=None):
     p.add_argument("--lfq_inv_temperature", type=float, default=argparse.SUPPRESS)
     # opt-in factorized codes (codebook_dim=d: the codebook is searched in d channels between two projections); absent unless given
     p.add_argument("--codebook_dim", type=int, default=argparse.SUPPRESS, metavar="d")
+    # opt-in orthogonal regularization loss of the codebook (orthogonal_reg_weight=W; csrc/vq_orthogonal.hip); absent unless given
+    p.add_argument("--orthogonal_reg_weight", type=float, default=argparse.SUPPRESS, metavar="W")
+    p.add_argument("--orthogonal_reg_active_codes_only", action="store_true", default=argparse.SUPPRESS)
+    p.add_argument("--orthogonal_reg_max_codes", type=int, default=argparse.SUPPRESS, metavar="M")
     args = p.parse_args(argv)
     ema_kw = {}
+    for name in ("orthogonal_reg_weight", "orthogonal_reg_active_codes_only", "orthogonal_reg_max_codes"):
+        if hasattr(args, name):
+            ema_kw[name] = getattr(args, name)
     if hasattr(args, "lookup_free"):
         ema_kw["lookup_free"] = True
     for name in ("lfq_entropy_weight", "lfq_diversity_gamma", "lfq_inv_temperature"):

@@ -767,3 +767,77 @@ def linear_rows_backward(x: torch.Tensor, grad_y: torch.Tensor, w: torch.Tensor,
             gx.data_ptr() if want_x else None, gw.data_ptr() if want_w else None, gb.data_ptr() if want_b else None,
             ws.data_ptr() if ws is not None else None, ws.numel() * ws.element_size() if ws is not None else 0, _stream_ptr(x)))
     return gx, gw, gb
+
+
+# ---- orthogonal regularization of a codebook (csrc/vq_orthogonal.hip) ------------------------------------------------------------
+
+def vq_orthogonal_workspace(K: int, D: int, device) -> torch.Tensor:
+    """workspace of vq_orthogonal_forward: the K fp64 row sums"""
+    n = _lib.load().vqvae_vq_orthogonal_workspace_bytes(K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"vq_orthogonal: K={K}, D={D} not supported (1 <= K <= 16384, 1 <= D <= 256)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_orthogonal_forward(rows: torch.Tensor, hist: torch.Tensor | None = None, *, max_codes: int | None = None,
+                          uniforms: torch.Tensor | None = None, want_saved: bool = False, workspace: torch.Tensor | None = None):
+    """The orthogonal regularization loss of the rows of a (K, D) table as they stand (vqvae_vq_orthogonal_forward_f32; the caller
+    normalises): |E E^T|_F^2 / M^2 - 1 / M over the M selected codes.  hist (K,) int32: only codes with hist > 0 are candidates
+    (None: every code).  max_codes with uniforms (K,) fp32 in [0, 1): of more candidates, the max_codes that come first by (u, k)
+    are kept.  -> (loss 0-dim, count 0-dim int32 = M, selected (K,) int32 0 / 1, saved (K, D) fp64 for vq_orthogonal_backward, or
+    None without want_saved).  No host sync.  The numeric contract is the header of csrc/vq_orthogonal.hip."""
+    _check_dev("rows", rows)
+    if rows.dim() != 2:
+        raise ValueError("rows must be a 2-D (K, D) tensor")
+    K, D = rows.shape
+    if hist is not None:
+        _check_dev("hist", hist, torch.int32)
+        if hist.shape != (K,):
+            raise ValueError("hist must be (K,)")
+        hist = hist.contiguous()
+    if max_codes is not None and uniforms is None:
+        raise ValueError("max_codes needs uniforms: one value in [0, 1) per code")
+    if uniforms is not None:
+        _check_dev("uniforms", uniforms)
+        if uniforms.shape != (K,):
+            raise ValueError("uniforms must be (K,)")
+        uniforms = uniforms.contiguous()
+    rows = rows.contiguous()
+    dev = rows.device
+    with torch.cuda.device(dev):
+        ws = workspace if workspace is not None else vq_orthogonal_workspace(K, D, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        count = torch.empty((), dtype=torch.int32, device=dev)
+        selected = torch.empty((K,), dtype=torch.int32, device=dev)
+        saved = torch.empty((K, D), dtype=torch.float64, device=dev) if want_saved else None
+        _lib.check(_lib.load().vqvae_vq_orthogonal_forward_f32(
+            rows.data_ptr(), hist.data_ptr() if hist is not None else None, uniforms.data_ptr() if uniforms is not None else None,
+            int(max_codes) if max_codes is not None else 0, K, D, 0, loss.data_ptr(), count.data_ptr(), selected.data_ptr(),
+            saved.data_ptr() if want_saved else None, ws.data_ptr(), ws.numel(), _stream_ptr(rows)))
+    return loss, count, selected, saved
+
+
+def vq_orthogonal_backward(saved: torch.Tensor, selected: torch.Tensor, count: torch.Tensor,
+                           grad_loss: torch.Tensor | None = None) -> torch.Tensor:
+    """grad_rows (K, D) fp32 of vq_orthogonal_forward's loss from its outputs (vqvae_vq_orthogonal_backward_f32): grad_loss (a device
+    scalar; None: 1) times 4 / M^2 times saved in the selected rows, +0.0 elsewhere."""
+    _check_dev("saved", saved, torch.float64)
+    _check_dev("selected", selected, torch.int32)
+    _check_dev("count", count, torch.int32)
+    if saved.dim() != 2:
+        raise ValueError("saved must be a 2-D (K, D) tensor")
+    K, D = saved.shape
+    if selected.shape != (K,) or count.numel() != 1:
+        raise ValueError("saved must be (K, D), selected (K,), count a scalar")
+    if grad_loss is not None:
+        _check_dev("grad_loss", grad_loss)
+        if grad_loss.numel() != 1:
+            raise ValueError("grad_loss must be a scalar")
+        grad_loss = grad_loss.contiguous()
+    saved, selected = saved.contiguous(), selected.contiguous()
+    with torch.cuda.device(saved.device):
+        grad_rows = torch.empty((K, D), dtype=torch.float32, device=saved.device)
+        _lib.check(_lib.load().vqvae_vq_orthogonal_backward_f32(
+            saved.data_ptr(), selected.data_ptr(), count.data_ptr(), grad_loss.data_ptr() if grad_loss is not None else None, K, D,
+            grad_rows.data_ptr(), _stream_ptr(saved)))
+    return grad_rows

@@ -131,11 +131,19 @@ class VectorQuantizer(nn.Module):
 
     LAZY_MIN_ENCODINGS = True          # forward()'s fourth output: LazyOneHot (the (N, K) one-hot on first use) or the tensor itself
 
-    def __init__(self, n_e, e_dim, beta, *, rotation_trick=False, cosine_sim=False):
+    def __init__(self, n_e, e_dim, beta, *, rotation_trick=False, cosine_sim=False, orthogonal_reg_weight=0.0,
+                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None):
         super().__init__()
         self.n_e = n_e
         self.e_dim = e_dim
         self.beta = beta
+        # opt-in: the orthogonal regularization loss of the codebook (arXiv 2112.00384 section 3.2; csrc/vq_orthogonal.hip) joins
+        # the training loss.  Plain attributes: no parameter, no buffer, no state_dict key; at weight 0 nothing is launched or drawn.
+        self.orthogonal_reg_weight, self.orthogonal_reg_max_codes = self._check_orthogonal(orthogonal_reg_weight,
+                                                                                           orthogonal_reg_max_codes)
+        self.orthogonal_reg_active_codes_only = bool(orthogonal_reg_active_codes_only)
+        self.generator = generator             # of the cap's draws (VectorQuantizerEMA: of its restart rows)
+        self.last_orthogonal_loss = None       # the latest term, a device scalar
         # opt-in: the decoder's gradient reaches the encoder through the rotation trick (arXiv 2410.06424; csrc/vq_rotation.hip)
         # instead of unchanged.  A plain attribute: no parameter, no buffer, no state_dict key; the forward is the same.
         self.rotation_trick = bool(rotation_trick)
@@ -145,6 +153,39 @@ class VectorQuantizer(nn.Module):
         self.cosine_sim = bool(cosine_sim)
         self.embedding = nn.Embedding(self.n_e, self.e_dim)
         self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)   # quantizer.py:27
+
+    @staticmethod
+    def _check_orthogonal(weight, max_codes):
+        weight = float(weight)
+        if not weight >= 0.0:
+            raise ValueError(f"orthogonal_reg_weight must be >= 0, got {weight!r}")
+        if max_codes is not None:
+            if isinstance(max_codes, bool) or not isinstance(max_codes, int) or max_codes < 1:
+                raise ValueError(f"orthogonal_reg_max_codes must be an int >= 1 or None, got {max_codes!r}")
+        return weight, max_codes
+
+    def _with_orthogonal(self, out, codes):
+        """quantize's outputs with weight * the orthogonal regularization loss of the l2-normalised codebook added to the loss:
+        only with a weight > 0, in training mode, while a graph is recorded, for a codebook that takes a gradient.  codes: the
+        rows the search ran on -- with cosine_sim the normalised codebook's node, which is used as it is (the codebook is
+        normalised once).  The term is kept in last_orthogonal_loss."""
+        w = self.embedding.weight
+        if not (self.orthogonal_reg_weight > 0.0 and self.training and torch.is_grad_enabled() and w.requires_grad):
+            return out
+        from .training import L2NormRows, OrthogonalLoss
+        unit = codes if self.cosine_sim else L2NormRows.apply(w)
+        table = _cache.side(self).setdefault("orth_ws", {})
+        skey = (str(w.device), torch.cuda.current_stream(w.device).cuda_stream)
+        ws = _cache.lru_get(table, skey)
+        if ws is None:
+            ws = F_hip.vq_orthogonal_workspace(self.n_e, self.e_dim, w.device)
+            _cache.lru_put(table, skey, ws, 8)
+        max_codes, uniforms = self.orthogonal_reg_max_codes, None
+        if max_codes is not None:
+            uniforms = torch.rand(self.n_e, device=w.device, generator=self.generator)
+        term = OrthogonalLoss.apply(unit, out[4] if self.orthogonal_reg_active_codes_only else None, max_codes, uniforms, ws)
+        self.last_orthogonal_loss = term.detach()
+        return (out[0] + self.orthogonal_reg_weight * term,) + tuple(out[1:])
 
     def invalidate(self):
         """Forget the prepared codebook image.  The cache is keyed on (data_ptr, _version, device), which in-place ops
@@ -209,7 +250,7 @@ class VectorQuantizer(nn.Module):
             out = F_hip.vq_forward(z, w.detach(), self.beta, rowmajor=rowmajor, workspace=ws,
                                    prepared=prepared, want_zq=want_zq)
         slot[1] = key
-        return out
+        return self._with_orthogonal(out, w)
 
     def _apply(self, fn, *args, **kwargs):
         self.invalidate()
@@ -326,9 +367,13 @@ class FactorizedVectorQuantizer(VectorQuantizer):
 
     _INNER = VectorQuantizer                  # the class whose quantize / init_codebook_ run on the projected rows
 
-    def __init__(self, n_e, dim, codebook_dim, beta, *, rotation_trick=False, cosine_sim=False):
+    def __init__(self, n_e, dim, codebook_dim, beta, *, rotation_trick=False, cosine_sim=False, orthogonal_reg_weight=0.0,
+                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None):
         dim, codebook_dim = self._check_dims(dim, codebook_dim)
-        super().__init__(n_e, codebook_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+        super().__init__(n_e, codebook_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim,
+                         orthogonal_reg_weight=orthogonal_reg_weight,
+                         orthogonal_reg_active_codes_only=orthogonal_reg_active_codes_only,
+                         orthogonal_reg_max_codes=orthogonal_reg_max_codes, generator=generator)
         self._init_projections(dim, codebook_dim)
 
     @staticmethod
@@ -909,8 +954,20 @@ class VQVAE(nn.Module):
     def __init__(self, h_dim, res_h_dim, n_res_layers, n_embeddings, embedding_dim, beta,
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
                  shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1,
-                 lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0, codebook_dim=None):
+                 lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0,
+                 orthogonal_reg_weight=0.0, orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, codebook_dim=None):
         super().__init__()
+        orthogonal_reg_weight, orthogonal_reg_max_codes = VectorQuantizer._check_orthogonal(orthogonal_reg_weight,
+                                                                                           orthogonal_reg_max_codes)
+        if orthogonal_reg_weight > 0.0:
+            # the orthogonal regularization loss trains the codebook by its gradient: the one-stage gradient-trained quantizers
+            for name, on in (("ema_decay (no gradient reaches an EMA codebook)", ema_decay is not None),
+                             ("n_quantizers > 1", n_quantizers != 1), ("codebook_groups > 1", codebook_groups != 1),
+                             ("fsq_levels", fsq_levels is not None), ("lookup_free", lookup_free)):
+                if on:
+                    raise ValueError(f"orthogonal_reg_weight > 0 does not combine with {name}")
+        orth = dict(orthogonal_reg_weight=orthogonal_reg_weight, orthogonal_reg_active_codes_only=orthogonal_reg_active_codes_only,
+                    orthogonal_reg_max_codes=orthogonal_reg_max_codes)
         if codebook_dim is not None:
             # factorized codes: the plain or the EMA quantizer between two projections, with the one-stage quantizers' options
             FactorizedVectorQuantizer._check_dims(embedding_dim, codebook_dim)
@@ -985,7 +1042,7 @@ class VQVAE(nn.Module):
                 if restart_threshold is not None:
                     raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
                 self.vector_quantization = FactorizedVectorQuantizer(n_embeddings, embedding_dim, codebook_dim, beta,
-                                                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+                                                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim, **orth)
             else:
                 self.vector_quantization = FactorizedVectorQuantizerEMA(n_embeddings, embedding_dim, codebook_dim, beta,
                                                                         decay=ema_decay, eps=ema_eps,
@@ -995,7 +1052,7 @@ class VQVAE(nn.Module):
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
             self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta, rotation_trick=rotation_trick,
-                                                       cosine_sim=cosine_sim)
+                                                       cosine_sim=cosine_sim, **orth)
         else:
             # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
             self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,

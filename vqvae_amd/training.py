@@ -534,3 +534,24 @@ class LinearRows(torch.autograd.Function):
         if not any(want):
             return None, None, None, None
         return F_hip.linear_rows_backward(x, g, w, rowmajor=ctx.rowmajor, want=want) + (None,)
+
+
+# ---- orthogonal regularization of a codebook (csrc/vq_orthogonal.hip) ------------------------------------------------------------
+
+class OrthogonalLoss(torch.autograd.Function):
+    """rows (K, D) -> the orthogonal regularization loss of the rows as they stand, forward and backward on the HIP kernels
+    (functional.vq_orthogonal_forward / vq_orthogonal_backward): differentiable with respect to rows only.  The forward saves V, the
+    fp64 sums its pass forms anyway; the backward is one elementwise kernel.
+    apply(rows, hist, max_codes, uniforms, workspace): hist (K,) int32 or None, max_codes with uniforms (K,) or None each."""
+
+    @staticmethod
+    def forward(ctx, rows, hist, max_codes, uniforms, workspace):
+        loss, count, selected, saved = F_hip.vq_orthogonal_forward(rows.detach(), hist, max_codes=max_codes, uniforms=uniforms,
+                                                                   want_saved=True, workspace=workspace)
+        ctx.save_for_backward(saved, selected, count)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        saved, selected, count = ctx.saved_tensors
+        return F_hip.vq_orthogonal_backward(saved, selected, count, g.contiguous()), None, None, None, None
