@@ -4,25 +4,7 @@
 // the row-major bodies runs as 256 host threads that meet at a barrier where the kernel has __syncthreads().  Every output is compared
 // bit for bit with a scalar loop in the order of vq_cosine.hip's header.  Zero rows, rows below eps, NaN and Inf rows are among the
 // rows.  tests/test_vq_cosine_cpu.py builds it with the sanitizers on (and -ffp-contract=off, as the library).
-#include <pthread.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define __device__
-#define __forceinline__ inline
-struct alignas(16) f32x4 { float x, y, z, w; };
-struct Dim3 { unsigned x; };
-static Dim3 blockIdx;
-static thread_local Dim3 threadIdx;
-static pthread_barrier_t g_barrier;
-static bool g_threads = false;
-static void __syncthreads() { if (g_threads) pthread_barrier_wait(&g_barrier); }
+#include "device_shim.h"
 #include "../../vqvae_amd/csrc/vq_cosine.h"
 using namespace vqvae;
 
@@ -37,18 +19,7 @@ template <typename Kfn> static void run_nchw(Kfn k, L2nArgs a, int V) {
 alignas(16) static float g_lds[kL2Waves * 2 * kL2TileFloats];
 
 template <bool BWD, int V> static void run_rows(L2nArgs a) {
-    const long long g = (a.N + 64 * kL2Waves - 1) / (64 * kL2Waves);
-    g_threads = true;
-    for (long long bx = 0; bx < g; ++bx) {
-        blockIdx.x = (unsigned)bx;
-        for (auto &v : g_lds) v = 0.f;
-        pthread_barrier_init(&g_barrier, nullptr, 256);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < 256; ++t) th.emplace_back([=] { threadIdx.x = t; l2n_rows_body<BWD, V>(a, g_lds); });
-        for (auto &t : th) t.join();
-        pthread_barrier_destroy(&g_barrier);
-    }
-    g_threads = false;
+    run_grid((a.N + 64 * kL2Waves - 1) / (64 * kL2Waves), 1, 256, [] { for (auto &v : g_lds) v = 0.f; }, [=] { l2n_rows_body<BWD, V>(a, g_lds); });
 }
 
 static size_t pos(long long row, int c, int D, int HW, int rm) {
@@ -56,8 +27,6 @@ static size_t pos(long long row, int c, int D, int HW, int rm) {
     const long long b = row / HW;
     return (size_t)((b * D + c) * HW + row % HW);
 }
-
-static bool same(float a, float b) { return (std::isnan(a) && std::isnan(b)) || !memcmp(&a, &b, 4); }
 
 int main() {
     int bad = 0;

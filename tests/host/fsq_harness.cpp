@@ -1,65 +1,24 @@
-// Host-side check of the finite-scalar-quantization kernels: compiles vqvae_amd/csrc/vq_fsq.h -- the text the HIP kernels compile --
-// for the host and runs the forward, the decode, the backward (with and without the parameter gradients) and the second launch of the
-// parameter gradients over small grids, in both layouts and on both access paths of the row-major kernels.  A workgroup runs as 256
+// Host-side check of the finite-scalar-quantization kernels: compiles vqvae_amd/csrc/vq_fsq.h and, through it, the skeleton it shares
+// with LFQ, vq_proj.h -- the text the HIP kernels compile -- for the host and runs the forward, the decode, the backward (with and
+// without the parameter gradients) and the second launch of the parameter gradients over small grids, in both layouts and on both access paths of the row-major kernels.  A workgroup runs as 256
 // host threads that meet at a barrier where the kernel has __syncthreads().  Every output is compared bit for bit with the values
 // tests/test_vq_fsq_cpu.py computed with tests/vq_fsq_ref.py and wrote into the file named on the command line (the same libm serves
 // both).  Built with the sanitizers on and -ffp-contract=off, as the library.
-#include <pthread.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define __device__
-#define __forceinline__ inline
-struct alignas(16) f32x4 { float x, y, z, w; };
-struct Dim3 { unsigned x; };
-static Dim3 blockIdx;
-static thread_local Dim3 threadIdx;
-static pthread_barrier_t g_barrier;
-static void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-static int atomicAdd(int *p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+#include "device_shim.h"
 #include "../../vqvae_amd/csrc/vq_fsq.h"
 using namespace vqvae;
 
 alignas(16) static float g_tiles[kL2Waves * kL2TileFloats];
-static float g_wl[kFsqWeightFloatsMax];
-static float g_chat[kFsqBlockRows * kFsqMaxLevels];
-static double g_gy[kFsqBlockRows * kFsqMaxLevels];
+static float g_wl[proj_weight_floats_max(kFsqMaxLevels)];
+static float g_chat[kProjBlockRows * kFsqMaxLevels];
+static double g_gy[kProjBlockRows * kFsqMaxLevels];
 
 // one grid of 256-thread workgroups, one after the other
 template <typename Body> static void run_grid(long long blocks, Body body) {
-    for (long long bx = 0; bx < blocks; ++bx) {
-        blockIdx.x = (unsigned)bx;
+    run_grid(blocks, 1, kProjBlockRows, [] {
         for (auto &v : g_tiles) v = -3.f;
         for (auto &v : g_wl) v = -3.f;
-        pthread_barrier_init(&g_barrier, nullptr, kFsqBlockRows);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < (unsigned)kFsqBlockRows; ++t) th.emplace_back([=] { threadIdx.x = t; body(); });
-        for (auto &t : th) t.join();
-        pthread_barrier_destroy(&g_barrier);
-    }
-}
-
-template <typename T> static std::vector<T> take(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { printf("short input file\n"); exit(2); }
-    return v;
-}
-
-static bool same(float a, float b) { return (std::isnan(a) && std::isnan(b)) || !memcmp(&a, &b, 4); }
-
-// (N, D) rows <-> the layout under test
-static std::vector<float> lay(const std::vector<float> &rows, long long N, int D, int HW, int rm) {
-    if (rm) return rows;
-    std::vector<float> m(rows.size());
-    for (long long r = 0; r < N; ++r)
-        for (int c = 0; c < D; ++c) m[(size_t)((r / HW * D + c) * HW + r % HW)] = rows[(size_t)(r * D + c)];
-    return m;
+    }, body);
 }
 
 static int g_bad = 0;
@@ -106,7 +65,7 @@ int main(int argc, char **argv) {
         const std::vector<long long> dec_idx = take<long long>(f, N);
         const std::vector<float> w_dec = take<float>(f, ND), w_gz = take<float>(f, ND), w_gwo = take<float>(f, (size_t)D * d),
                                  w_gbo = take<float>(f, D), w_gwi = take<float>(f, (size_t)d * D), w_gbi = take<float>(f, d);
-        const long long blocks = (N + kFsqBlockRows - 1) / kFsqBlockRows;
+        const long long blocks = (N + kProjBlockRows - 1) / kProjBlockRows;
         const int P = 2 * D * d + D + d;
         for (int rm = 0; rm < 2; ++rm) for (int V : {1, 4}) {
             if (V == 4 && (!rm || D % 4)) continue;
@@ -120,9 +79,9 @@ int main(int argc, char **argv) {
                 a.z = zl.data(); a.w_in = w_in.data(); a.b_in = b_in.data();
                 a.w_out = with_zq ? w_out.data() : nullptr; a.b_out = with_zq ? b_out.data() : nullptr;
                 a.out = with_zq ? zq.data() : nullptr; a.idx = idx.data(); a.hist = hist.data();
-                if (!rm) run_grid(blocks, [=] { fsq_fwd_nchw_body<false>(a, g_wl); });
-                else if (V == 4) run_grid(blocks, [=] { fsq_fwd_rows_body<false, 4>(a, g_tiles, g_wl); });
-                else run_grid(blocks, [=] { fsq_fwd_rows_body<false, 1>(a, g_tiles, g_wl); });
+                if (!rm) run_grid(blocks, [=] { proj_fwd_nchw_body<Fsq, false>(a, g_wl); });
+                else if (V == 4) run_grid(blocks, [=] { proj_fwd_rows_body<Fsq, false, 4>(a, g_tiles, g_wl); });
+                else run_grid(blocks, [=] { proj_fwd_rows_body<Fsq, false, 1>(a, g_tiles, g_wl); });
                 if (idx != w_idx) { printf("MISMATCH case %d idx rm=%d V=%d\n", cs, rm, V); ++g_bad; }
                 if (hist != w_hist) { printf("MISMATCH case %d hist rm=%d V=%d\n", cs, rm, V); ++g_bad; }
                 if (with_zq) cmp("z_q", zq, w_zq, N, D, HW, rm, V, cs);
@@ -133,9 +92,9 @@ int main(int argc, char **argv) {
                 std::vector<float> zq(ND, -7.f);
                 FsqArgs a = base;
                 a.idx_in = dec_idx.data(); a.w_out = w_out.data(); a.b_out = b_out.data(); a.out = zq.data();
-                if (!rm) run_grid(blocks, [=] { fsq_fwd_nchw_body<true>(a, g_wl); });
-                else if (V == 4) run_grid(blocks, [=] { fsq_fwd_rows_body<true, 4>(a, g_tiles, g_wl); });
-                else run_grid(blocks, [=] { fsq_fwd_rows_body<true, 1>(a, g_tiles, g_wl); });
+                if (!rm) run_grid(blocks, [=] { proj_fwd_nchw_body<Fsq, true>(a, g_wl); });
+                else if (V == 4) run_grid(blocks, [=] { proj_fwd_rows_body<Fsq, true, 4>(a, g_tiles, g_wl); });
+                else run_grid(blocks, [=] { proj_fwd_rows_body<Fsq, true, 1>(a, g_tiles, g_wl); });
                 cmp("decode", zq, w_dec, N, D, HW, rm, V, cs);
             }
             // backward: grad_z alone, then everything
@@ -146,21 +105,21 @@ int main(int argc, char **argv) {
                 a.z = zl.data(); a.g = gl.data(); a.w_in = w_in.data(); a.b_in = b_in.data(); a.w_out = w_out.data();
                 a.out = gz.data(); a.partials = params ? part.data() : nullptr;
                 if (!rm) {
-                    if (params) run_grid(blocks, [=] { fsq_bwd_nchw_body<true>(a, g_tiles, g_wl, g_chat, g_gy); });
-                    else run_grid(blocks, [=] { fsq_bwd_nchw_body<false>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    if (params) run_grid(blocks, [=] { Fsq::bwd_nchw_body<true>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    else run_grid(blocks, [=] { Fsq::bwd_nchw_body<false>(a, g_tiles, g_wl, g_chat, g_gy); });
                 } else if (V == 4) {
-                    if (params) run_grid(blocks, [=] { fsq_bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_chat, g_gy); });
-                    else run_grid(blocks, [=] { fsq_bwd_rows_body<false, 4>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    if (params) run_grid(blocks, [=] { Fsq::bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    else run_grid(blocks, [=] { Fsq::bwd_rows_body<false, 4>(a, g_tiles, g_wl, g_chat, g_gy); });
                 } else {
-                    if (params) run_grid(blocks, [=] { fsq_bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_chat, g_gy); });
-                    else run_grid(blocks, [=] { fsq_bwd_rows_body<false, 1>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    if (params) run_grid(blocks, [=] { Fsq::bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_chat, g_gy); });
+                    else run_grid(blocks, [=] { Fsq::bwd_rows_body<false, 1>(a, g_tiles, g_wl, g_chat, g_gy); });
                 }
                 cmp("grad_z", gz, w_gz, N, D, HW, rm, V, cs);
                 if (!params) continue;
                 std::vector<float> gwi((size_t)d * D, -7.f), gbi(d, -7.f), gwo((size_t)D * d, -7.f), gbo(D, -7.f);
                 const double *pp = part.data();
                 float *p_wi = gwi.data(), *p_bi = gbi.data(), *p_wo = gwo.data(), *p_bo = gbo.data();
-                run_grid((P + kFsqBlockRows - 1) / kFsqBlockRows, [=] { fsq_param_finalize_body(pp, blocks, D, d, p_wi, p_bi, p_wo, p_bo); });
+                run_grid((P + kProjBlockRows - 1) / kProjBlockRows, [=] { proj_param_finalize_body(pp, blocks, D, d, p_wi, p_bi, p_wo, p_bo); });
                 cmp_flat("grad_w_out", gwo.data(), w_gwo, rm, V, cs);
                 cmp_flat("grad_b_out", gbo.data(), w_gbo, rm, V, cs);
                 cmp_flat("grad_w_in", gwi.data(), w_gwi, rm, V, cs);
@@ -168,7 +127,7 @@ int main(int argc, char **argv) {
                 // a NULL gradient is skipped: nothing is written through the others' slots either
                 std::vector<float> only(D, -7.f);
                 float *p_only = only.data();
-                run_grid((P + kFsqBlockRows - 1) / kFsqBlockRows, [=] { fsq_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, nullptr, p_only); });
+                run_grid((P + kProjBlockRows - 1) / kProjBlockRows, [=] { proj_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, nullptr, p_only); });
                 cmp_flat("grad_b_out alone", only.data(), w_gbo, rm, V, cs);
             }
         }

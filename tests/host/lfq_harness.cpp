@@ -1,57 +1,31 @@
-// Host-side check of the lookup-free-quantization kernels: compiles vqvae_amd/csrc/vq_lfq.h -- the text the HIP kernels compile -- for
-// the host and runs both launch chains of vq_lfq.hip over small grids, in both layouts and on both access paths of the row-major
-// kernels: forward (row kernel, avg partials, avg, loss finalize), decode, backward (y pass, log avg, entropy gradient, row kernel with
+// Host-side check of the lookup-free-quantization kernels: compiles vqvae_amd/csrc/vq_lfq.h and, through it, the skeleton it shares
+// with FSQ, vq_proj.h -- the text the HIP kernels compile -- for the host and runs both launch chains of vq_lfq.hip over small
+// grids, in both layouts and on both access paths of the row-major kernels: forward (row kernel, avg partials, avg, loss finalize), decode, backward (y pass, log avg, entropy gradient, row kernel with
 // and without the parameter gradients, parameter finalize), with and without a loss gradient.  A workgroup runs as host threads that
 // meet at a barrier where the kernel has __syncthreads().  z_q, idx, hist, y, decode and the straight-through gradients are compared
 // bit for bit with the values tests/test_vq_lfq_cpu.py computed with tests/vq_lfq_ref.py and wrote into the file named on the
 // command line; the losses, avg and the loss's gradients within the bounds written there (their sums run in another order than
 // numpy's).  Built with the sanitizers on and -ffp-contract=off, as the library.
-#include <pthread.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define __device__
-#define __forceinline__ inline
-struct alignas(16) f32x4 { float x, y, z, w; };
-struct Dim3 { unsigned x, y; };
-static Dim3 blockIdx;
-static thread_local Dim3 threadIdx;
-static pthread_barrier_t g_barrier;
-static void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-static int atomicAdd(int *p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+#include "device_shim.h"
 #include "../../vqvae_amd/csrc/vq_lfq.h"
 using namespace vqvae;
 
 alignas(16) static float g_tiles[kL2Waves * kL2TileFloats];
-static float g_nchw[kL2Chunk * kLfqNchwStride];
-static float g_wl[kLfqWeightFloatsMax];
-static float g_code[kLfqBlockRows * kLfqMaxBits];
-static double g_gy[kLfqBlockRows * kLfqMaxBits];
+static float g_nchw[kL2Chunk * kProjNchwStride];
+static float g_wl[proj_weight_floats_max(kLfqMaxBits)];
+static float g_code[kProjBlockRows * kLfqMaxBits];
+static double g_gy[kProjBlockRows * kLfqMaxBits];
 static double g_pp[2 * kLfqChunkRows * kLfqMaxBits], g_hh[kLfqChunkRows * kLfqMaxBits], g_cc[kLfqChunkRows * kLfqMaxBits];
 static double g_red[256], g_ch[kLfqScalarSlots];
 static double g_llds[kLfqLogLdsDoubles], g_pb[2 * kLfqMaxBits], g_A[256], g_B[256], g_u[256], g_v[256], g_T[2 * kLfqMaxBits];
 
 // one grid of workgroups of `nthreads` threads, one after the other
 template <typename Body> static void run_grid(long long bx_n, int by_n, int nthreads, Body body) {
-    for (int by = 0; by < by_n; ++by)
-        for (long long bx = 0; bx < bx_n; ++bx) {
-            blockIdx.x = (unsigned)bx;
-            blockIdx.y = (unsigned)by;
-            for (auto &v : g_tiles) v = -3.f;
-            for (auto &v : g_wl) v = -3.f;
-            for (auto &v : g_llds) v = -3.0;
-            pthread_barrier_init(&g_barrier, nullptr, nthreads);
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < (unsigned)nthreads; ++t) th.emplace_back([=] { threadIdx.x = t; threadIdx.y = 0; body(); });
-            for (auto &t : th) t.join();
-            pthread_barrier_destroy(&g_barrier);
-        }
+    run_grid(bx_n, by_n, (unsigned)nthreads, [] {
+        for (auto &v : g_tiles) v = -3.f;
+        for (auto &v : g_wl) v = -3.f;
+        for (auto &v : g_llds) v = -3.0;
+    }, body);
 }
 
 // a grid whose kernel has no barrier: the threads of a workgroup one after the other on this thread
@@ -64,23 +38,6 @@ template <typename Body> static void run_grid_serial(long long bx_n, int nthread
             body();
         }
     }
-}
-
-template <typename T> static std::vector<T> take(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { printf("short input file\n"); exit(2); }
-    return v;
-}
-
-static bool same(float a, float b) { return (std::isnan(a) && std::isnan(b)) || !memcmp(&a, &b, 4); }
-
-// (N, D) rows <-> the layout under test
-template <typename T> static std::vector<T> lay(const std::vector<T> &rows, long long N, int D, int HW, int rm) {
-    if (rm) return rows;
-    std::vector<T> m(rows.size());
-    for (long long r = 0; r < N; ++r)
-        for (int c = 0; c < D; ++c) m[(size_t)((r / HW * D + c) * HW + r % HW)] = rows[(size_t)(r * D + c)];
-    return m;
 }
 
 static int g_bad = 0;
@@ -141,7 +98,7 @@ int main(int argc, char **argv) {
         const std::vector<double> w_e = take<double>(f, Nd), b_e = take<double>(f, Nd), w_gz = take<double>(f, ND), b_gz = take<double>(f, ND),
                                   w_gwi = take<double>(f, (size_t)d * D), b_gwi = take<double>(f, (size_t)d * D), w_gbi = take<double>(f, d),
                                   b_gbi = take<double>(f, d);
-        const long long blocks = (N + kLfqBlockRows - 1) / kLfqBlockRows;
+        const long long blocks = (N + kProjBlockRows - 1) / kProjBlockRows;
         const int PC = 2 * D * d + D + d;
         LfqArgs base = {};
         base.N = N; base.D = D; base.HW = HW; base.d = d; base.K = K;
@@ -153,9 +110,9 @@ int main(int argc, char **argv) {
             if (V == 4 && (!rm || D % 4)) continue;
             const std::vector<float> zl = lay(z, N, D, HW, rm), gl = lay(g, N, D, HW, rm);
             auto fwd = [&](const LfqArgs &a) {
-                if (!rm) run_grid(blocks, 1, 256, [=] { lfq_fwd_nchw_body<false>(a, g_wl); });
-                else if (V == 4) run_grid(blocks, 1, 256, [=] { lfq_fwd_rows_body<false, 4>(a, g_tiles, g_wl); });
-                else run_grid(blocks, 1, 256, [=] { lfq_fwd_rows_body<false, 1>(a, g_tiles, g_wl); });
+                if (!rm) run_grid(blocks, 1, 256, [=] { proj_fwd_nchw_body<Lfq, false>(a, g_wl); });
+                else if (V == 4) run_grid(blocks, 1, 256, [=] { proj_fwd_rows_body<Lfq, false, 4>(a, g_tiles, g_wl); });
+                else run_grid(blocks, 1, 256, [=] { proj_fwd_rows_body<Lfq, false, 1>(a, g_tiles, g_wl); });
             };
             std::vector<double> avg(K, -7.0);
             // forward, with z_q and the losses, then without either
@@ -188,9 +145,9 @@ int main(int argc, char **argv) {
                 std::vector<float> zq(ND, -7.f);
                 LfqArgs a = base;
                 a.idx_in = dec_idx.data(); a.w_out = w_out.data(); a.b_out = b_out.data(); a.out = zq.data();
-                if (!rm) run_grid(blocks, 1, 256, [=] { lfq_fwd_nchw_body<true>(a, g_wl); });
-                else if (V == 4) run_grid(blocks, 1, 256, [=] { lfq_fwd_rows_body<true, 4>(a, g_tiles, g_wl); });
-                else run_grid(blocks, 1, 256, [=] { lfq_fwd_rows_body<true, 1>(a, g_tiles, g_wl); });
+                if (!rm) run_grid(blocks, 1, 256, [=] { proj_fwd_nchw_body<Lfq, true>(a, g_wl); });
+                else if (V == 4) run_grid(blocks, 1, 256, [=] { proj_fwd_rows_body<Lfq, true, 4>(a, g_tiles, g_wl); });
+                else run_grid(blocks, 1, 256, [=] { proj_fwd_rows_body<Lfq, true, 1>(a, g_tiles, g_wl); });
                 cmp("decode", zq, w_dec, N, D, HW, rm, V, cs);
             }
             // backward: without the loss gradient (exact), then with it; grad_z alone, then everything
@@ -216,14 +173,14 @@ int main(int argc, char **argv) {
                     a.e = with_loss ? e.data() : nullptr; a.gl = &gl_f;
                     a.out = gz.data(); a.partials = params ? part.data() : nullptr;
                     if (!rm) {
-                        if (params) run_grid(blocks, 1, 256, [=] { lfq_bwd_nchw_body<true>(a, g_nchw, g_wl, g_code, g_gy); });
-                        else run_grid(blocks, 1, 256, [=] { lfq_bwd_nchw_body<false>(a, g_nchw, g_wl, g_code, g_gy); });
+                        if (params) run_grid(blocks, 1, 256, [=] { Lfq::bwd_nchw_body<true>(a, g_nchw, g_wl, g_code, g_gy); });
+                        else run_grid(blocks, 1, 256, [=] { Lfq::bwd_nchw_body<false>(a, g_nchw, g_wl, g_code, g_gy); });
                     } else if (V == 4) {
-                        if (params) run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_code, g_gy); });
-                        else run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<false, 4>(a, g_tiles, g_wl, g_code, g_gy); });
+                        if (params) run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_code, g_gy); });
+                        else run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<false, 4>(a, g_tiles, g_wl, g_code, g_gy); });
                     } else {
-                        if (params) run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_code, g_gy); });
-                        else run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<false, 1>(a, g_tiles, g_wl, g_code, g_gy); });
+                        if (params) run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_code, g_gy); });
+                        else run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<false, 1>(a, g_tiles, g_wl, g_code, g_gy); });
                     }
                     if (!with_loss) cmp("grad_z (straight-through)", gz, st_gz, N, D, HW, rm, V, cs);
                     else if (clean) {
@@ -234,7 +191,7 @@ int main(int argc, char **argv) {
                     std::vector<float> gwi((size_t)d * D, -7.f), gbi(d, -7.f), gwo((size_t)D * d, -7.f), gbo(D, -7.f);
                     const double *pp = part.data();
                     float *p_wi = gwi.data(), *p_bi = gbi.data(), *p_wo = gwo.data(), *p_bo = gbo.data();
-                    run_grid((PC + kLfqBlockRows - 1) / kLfqBlockRows, 1, 256, [=] { lfq_param_finalize_body(pp, blocks, D, d, p_wi, p_bi, p_wo, p_bo); });
+                    run_grid((PC + kProjBlockRows - 1) / kProjBlockRows, 1, 256, [=] { proj_param_finalize_body(pp, blocks, D, d, p_wi, p_bi, p_wo, p_bo); });
                     cmp_flat("grad_w_out", gwo.data(), st_gwo, rm, V, cs);
                     cmp_flat("grad_b_out", gbo.data(), st_gbo, rm, V, cs);
                     if (!with_loss) {
@@ -247,7 +204,7 @@ int main(int argc, char **argv) {
                     // a NULL gradient is skipped: nothing is written through the others' slots either
                     std::vector<float> only(D, -7.f);
                     float *p_only = only.data();
-                    run_grid((PC + kLfqBlockRows - 1) / kLfqBlockRows, 1, 256, [=] { lfq_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, nullptr, p_only); });
+                    run_grid((PC + kProjBlockRows - 1) / kProjBlockRows, 1, 256, [=] { proj_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, nullptr, p_only); });
                     cmp_flat("grad_b_out alone", only.data(), st_gbo, rm, V, cs);
                 }
             }
@@ -256,12 +213,12 @@ int main(int argc, char **argv) {
                 std::vector<double> part((size_t)blocks * PC, -7.0);
                 LfqArgs a = base;
                 a.z = zl.data(); a.w_in = w_in.data(); a.w_out = w_out.data(); a.y = y.data(); a.out = gz.data(); a.partials = part.data();
-                if (!rm) run_grid(blocks, 1, 256, [=] { lfq_bwd_nchw_body<true>(a, g_nchw, g_wl, g_code, g_gy); });
-                else if (V == 4) run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_code, g_gy); });
-                else run_grid(blocks, 1, 256, [=] { lfq_bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_code, g_gy); });
+                if (!rm) run_grid(blocks, 1, 256, [=] { Lfq::bwd_nchw_body<true>(a, g_nchw, g_wl, g_code, g_gy); });
+                else if (V == 4) run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<true, 4>(a, g_tiles, g_wl, g_code, g_gy); });
+                else run_grid(blocks, 1, 256, [=] { Lfq::bwd_rows_body<true, 1>(a, g_tiles, g_wl, g_code, g_gy); });
                 const double *pp = part.data();
                 float *p_wo = gwo.data(), *p_bo = gbo.data();
-                run_grid((PC + kLfqBlockRows - 1) / kLfqBlockRows, 1, 256, [=] { lfq_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, p_wo, p_bo); });
+                run_grid((PC + kProjBlockRows - 1) / kProjBlockRows, 1, 256, [=] { proj_param_finalize_body(pp, blocks, D, d, nullptr, nullptr, p_wo, p_bo); });
                 for (float v : gz) if (v != 0.0f) { printf("case %d: grad_z without any upstream gradient is not zero\n", cs); ++g_bad; break; }
                 for (float v : gwo) if (v != 0.0f) { printf("case %d: grad_w_out without grad_zq is not zero\n", cs); ++g_bad; break; }
                 for (float v : gbo) if (v != 0.0f) { printf("case %d: grad_b_out without grad_zq is not zero\n", cs); ++g_bad; break; }

@@ -4,24 +4,7 @@
 // threads that meet at a barrier where the kernel has __syncthreads().  Every output is compared bit for bit with the values
 // tests/test_vq_linear_cpu.py computed with tests/vq_linear_ref.py and wrote into the file named on the command line.  Built with
 // the sanitizers on and -ffp-contract=off, as the library.
-#include <pthread.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define __device__
-#define __forceinline__ inline
-struct alignas(16) f32x4 { float x, y, z, w; };
-struct Dim3 { unsigned x; };
-static Dim3 blockIdx;
-static thread_local Dim3 threadIdx;
-static pthread_barrier_t g_barrier;
-static void __syncthreads() { pthread_barrier_wait(&g_barrier); }
+#include "device_shim.h"
 #include "../../vqvae_amd/csrc/vq_linear.h"
 using namespace vqvae;
 
@@ -31,34 +14,11 @@ static double g_wl[kLinWeightsMax];
 
 // one grid of workgroups of `threads` threads, one after the other
 template <typename Body> static void run_grid(long long blocks, Body body, unsigned threads = kLinBlockRows) {
-    for (long long bx = 0; bx < blocks; ++bx) {
-        blockIdx.x = (unsigned)bx;
+    run_grid(blocks, 1, threads, [] {
         for (auto &v : g_tiles) v = -3.f;
         for (auto &v : g_bt) v = -3.f;
         for (auto &v : g_wl) v = -3.0;
-        pthread_barrier_init(&g_barrier, nullptr, threads);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < threads; ++t) th.emplace_back([=] { threadIdx.x = t; body(); });
-        for (auto &t : th) t.join();
-        pthread_barrier_destroy(&g_barrier);
-    }
-}
-
-template <typename T> static std::vector<T> take(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { printf("short input file\n"); exit(2); }
-    return v;
-}
-
-static bool same(float a, float b) { return (std::isnan(a) && std::isnan(b)) || !memcmp(&a, &b, 4); }
-
-// (N, C) rows -> the layout under test
-static std::vector<float> lay(const std::vector<float> &rows, long long N, int C, int HW, int rm) {
-    if (rm) return rows;
-    std::vector<float> m(rows.size());
-    for (long long r = 0; r < N; ++r)
-        for (int c = 0; c < C; ++c) m[(size_t)((r / HW * C + c) * HW + r % HW)] = rows[(size_t)(r * C + c)];
-    return m;
+    }, body);
 }
 
 static int g_bad = 0;

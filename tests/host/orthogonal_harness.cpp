@@ -4,24 +4,7 @@
 // V.  A workgroup runs as host threads that meet at a barrier where the kernel has __syncthreads().  Every output is compared bit for bit with the values
 // tests/test_vq_orthogonal_cpu.py computed with tests/vq_orthogonal_ref.py and wrote into the file named on the command line.  Built
 // with the sanitizers on and -ffp-contract=off, as the library.
-#include <pthread.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define __device__
-#define __forceinline__ inline
-struct alignas(16) f32x4 { float x, y, z, w; };
-struct Dim3 { unsigned x; };
-static Dim3 blockIdx;
-static thread_local Dim3 threadIdx;
-static pthread_barrier_t g_barrier;
-static void __syncthreads() { pthread_barrier_wait(&g_barrier); }
+#include "device_shim.h"
 #include "../../vqvae_amd/csrc/vq_orthogonal.h"
 using namespace vqvae;
 
@@ -32,26 +15,14 @@ static int g_selj[kOrthTile], g_cnt[kOrthThreads];
 
 // one grid of workgroups of 256 threads, one after the other; the "LDS" holds other values at every start
 template <typename Body> static void run_grid(long long blocks, Body body) {
-    for (long long bx = 0; bx < blocks; ++bx) {
-        blockIdx.x = (unsigned)bx;
+    run_grid(blocks, 1, kOrthThreads, [] {
         for (auto &v : g_ni) v = -3.f;
         for (auto &v : g_nj) v = -3.f;
         for (auto &v : g_g) v = -3.0;
         for (auto &v : g_part) v = -3.0;
         for (auto &v : g_selj) v = 1;
         for (auto &v : g_cnt) v = 9;
-        pthread_barrier_init(&g_barrier, nullptr, kOrthThreads);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < (unsigned)kOrthThreads; ++t) th.emplace_back([=] { threadIdx.x = t; body(); });
-        for (auto &t : th) t.join();
-        pthread_barrier_destroy(&g_barrier);
-    }
-}
-
-template <typename T> static std::vector<T> take(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { printf("short input file\n"); exit(2); }
-    return v;
+    }, body);
 }
 
 static int g_bad = 0;

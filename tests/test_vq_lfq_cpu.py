@@ -301,10 +301,11 @@ def test_train_tool_options_are_absent_unless_given():
 
 # (B, HW, D, d, clean, nwg, inv_t, scale): one row; odd D on the element path, d = 1; the flagship split (5 + 5 bits) over two blocks;
 # an odd split (5 + 4) with rows wider than one chunk; special rows (losses unspecified, nothing faults); d = 16: 64 code tiles, log avg
-# read from memory; the LDS table's largest form (K = 4096)
+# read from memory; the LDS table's largest form (K = 4096); d = 16 with the large weight capacity (D = 68 > 64: a full chunk and a
+# ragged one, the 16-byte path) at the GPU test's 300 rows
 HOST_CASES = [(1, 1, 16, 4, 1, 1, 100.0, 1.0), (3, 35, 7, 1, 1, 7, 100.0, 0.01), (5, 64, 64, 10, 1, 13, 100.0, 0.02),
               (2, 150, 68, 9, 1, 64, 1.0, 1.0), (9, 36, 12, 3, 0, 5, 100.0, 1.0), (1, 6, 12, 16, 1, 3, 100.0, 0.01),
-              (1, 70, 8, 12, 1, 9, 100.0, 0.02)]
+              (1, 70, 8, 12, 1, 9, 100.0, 0.02), (3, 100, 68, 16, 1, 16, 100.0, 0.01)]
 
 
 def host_case_bytes(B, HW, D, d, clean, nwg, inv_t, scale, seed):

@@ -48,9 +48,10 @@ KW = dict(beta=BETA, entropy_weight=WE, diversity_gamma=GAMMA, inv_temperature=I
 
 # (B, H, W, D, d, scale of y): 1, 63, 65, 257 and 1025 rows (the wave, the 256-row block and the partition edges); D = 1, 7 (the element
 # path), 64, 256 (four chunks); d = 1, 2, 9 (an odd split), 10; saturated rows (|s y| near 400: the library's temperature on y of unit
-# scale) and rows on the soft part of the sigmoid; d = 16 once, at 300 rows
+# scale) and rows on the soft part of the sigmoid; d = 16 at 300 rows, once at D = 64 and once at D = 68: the 16-wide code path with the
+# large weight capacity (D > 64), a full chunk plus a ragged one of 4 channels, on the 16-byte path (68 % 4 == 0)
 CASES = [(1, 1, 1, 64, 10, 0.02), (3, 3, 7, 7, 2, 0.02), (5, 13, 1, 1, 1, 0.02), (1, 257, 1, 256, 9, 0.02), (5, 5, 41, 64, 10, 1.0),
-         (5, 5, 41, 7, 9, 0.02), (1, 257, 1, 64, 2, 0.005), (3, 10, 10, 64, 16, 0.01)]
+         (5, 5, 41, 7, 9, 0.02), (1, 257, 1, 64, 2, 0.005), (3, 10, 10, 64, 16, 0.01), (3, 10, 10, 68, 16, 0.01)]
 FLAG = (5, 5, 41, 64, 10, 0.02)                                 # the other tests' case: 1025 rows, D = 64, K = 1024
 
 

@@ -103,21 +103,21 @@ def resource_report(say):
     src = os.path.join(build.CSRC, "vq_fsq.hip")
     r = subprocess.run([build.hipcc(), *build.flags_for(src), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
                        capture_output=True, text=True)
-    say("compiler report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): fsq_fwd_nchw_kernel<decode, weight floats>, "
-        "fsq_fwd_rows_kernel<decode, floats per global access, weight floats>, fsq_bwd_nchw_kernel<parameter gradients, weight floats>, "
-        "fsq_bwd_rows_kernel<parameter gradients, floats per global access, weight floats>")
+    say("compiler report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): proj_fwd_nchw_kernel<Fsq, decode, weight floats>, "
+        "proj_fwd_rows_kernel<Fsq, decode, floats per global access, weight floats>, proj_bwd_nchw_kernel<Fsq, parameter gradients, "
+        "weight floats>, proj_bwd_rows_kernel<Fsq, parameter gradients, floats per global access, weight floats> (vq_proj_kernels.h)")
     name, row = None, {}
     for line in r.stderr.splitlines():
         m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         if m.group(1) == "Function Name":
-            t = re.search(r"(fsq_\w+?_kernel)(?:ILb([01])E((?:Li\d+E)*))?", m.group(2))
+            t = re.search(r"(proj_\w+?_kernel)INS_\d(Fsq)E(?:Lb([01])E((?:Li\d+E)*))?", m.group(2))
             name = m.group(2)
-            if t and t.group(2) is not None:
-                name = f"{t.group(1)}<{'true' if t.group(2) == '1' else 'false'}" + "".join(f", {v}" for v in re.findall(r"Li(\d+)E", t.group(3))) + ">"
+            if t and t.group(3) is not None:
+                name = f"{t.group(1)}<{t.group(2)}, {'true' if t.group(3) == '1' else 'false'}" + "".join(f", {v}" for v in re.findall(r"Li(\d+)E", t.group(4))) + ">"
             elif t:
-                name = t.group(1)
+                name = f"{t.group(1)}<{t.group(2)}>"
             row = {}
         else:
             row[m.group(1)] = m.group(2)

@@ -114,19 +114,21 @@ def resource_report(say):
     src = os.path.join(build.CSRC, "vq_lfq.hip")
     r = subprocess.run([build.hipcc(), *build.flags_for(src), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
                        capture_output=True, text=True)
-    say("compiler report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): lfq_fwd_nchw_kernel<decode, weight floats>, "
-        "lfq_fwd_rows_kernel<decode, floats per global access, weight floats>, lfq_bwd_nchw_kernel<parameter gradients, weight floats>, "
-        "lfq_bwd_rows_kernel<parameter gradients, floats per global access, weight floats>, lfq_entgrad_kernel<doubles of log avg in LDS>")
+    say("compiler report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): proj_fwd_nchw_kernel<Lfq, decode, weight floats>, "
+        "proj_fwd_rows_kernel<Lfq, decode, floats per global access, weight floats>, proj_bwd_nchw_kernel<Lfq, parameter gradients, "
+        "weight floats>, proj_bwd_rows_kernel<Lfq, parameter gradients, floats per global access, weight floats> (vq_proj_kernels.h), "
+        "lfq_entgrad_kernel<doubles of log avg in LDS>")
     name, row = None, {}
     for line in r.stderr.splitlines():
         m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         if m.group(1) == "Function Name":
-            t = re.search(r"(lfq_\w+?_kernel)(?:I(?:Lb([01])E)?((?:Li\d+E)*))?", m.group(2))
+            t = re.search(r"((?:lfq|proj)_\w+?_kernel)(?:I(?:NS_\d(Lfq)E)?(?:Lb([01])E)?((?:Li\d+E)*))?", m.group(2))
             name = m.group(2)
             if t:
-                args = ([("true" if t.group(2) == "1" else "false")] if t.group(2) is not None else []) + re.findall(r"Li(\d+)E", t.group(3) or "")
+                args = ([t.group(2)] if t.group(2) else []) + ([("true" if t.group(3) == "1" else "false")] if t.group(3) is not None else []) + \
+                    re.findall(r"Li(\d+)E", t.group(4) or "")
                 name = t.group(1) + (f"<{', '.join(args)}>" if args else "")
             row = {}
         else:

@@ -58,6 +58,45 @@ inline unsigned grid_of(long long total, long long cap = 65536) {
     return (unsigned)g;
 }
 
+// ---- the entries' checks: the header's codes, before any launch (vq_fsq.hip, vq_lfq.hip, vq_linear.hip, vq_orthogonal.hip) ----------
+struct Span { const void *p; size_t bytes; int align; };
+
+inline bool spans_overlap(const Span &x, const Span &y) {
+    if (!x.p || !y.p) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
+    return a < b + y.bytes && b < a + x.bytes;
+}
+
+// every pointer aligned to its span's `align` (NULL passes), and no output on an input
+inline int check_pointers(const Span *in, int n_in, const Span *out, int n_out) {
+    for (int i = 0; i < n_in; ++i)
+        if (reinterpret_cast<uintptr_t>(in[i].p) & (uintptr_t)(in[i].align - 1)) return VQVAE_ERR_UNSUPPORTED;
+    for (int o = 0; o < n_out; ++o) {
+        if (reinterpret_cast<uintptr_t>(out[o].p) & (uintptr_t)(out[o].align - 1)) return VQVAE_ERR_UNSUPPORTED;
+        for (int i = 0; i < n_in; ++i)
+            if (spans_overlap(out[o], in[i])) return VQVAE_ERR_UNSUPPORTED;
+    }
+    return VQVAE_OK;
+}
+
+// nor one output on another
+inline int check_outputs_apart(const Span *out, int n_out) {
+    for (int o = 0; o < n_out; ++o)
+        for (int k = o + 1; k < n_out; ++k)
+            if (spans_overlap(out[o], out[k])) return VQVAE_ERR_UNSUPPORTED;
+    return VQVAE_OK;
+}
+
+// (B, H, W) -> N = B H W rows and HW, both within int32
+inline int check_rows_shape(int64_t B, int H, int W, long long &N, int &HW) {
+    if (B < 1 || H < 1 || W < 1) return VQVAE_ERR_SHAPE;
+    const long long hw = (long long)H * W;
+    if (hw > INT32_MAX || B > INT32_MAX / hw) return VQVAE_ERR_UNSUPPORTED;
+    HW = (int)hw;
+    N = B * hw;
+    return VQVAE_OK;
+}
+
 // Every clear in a chain that may be captured is this kernel launch, not hipMemsetAsync.  Captured memsets of 400 and of 4000 bytes
 // (the histogram at K = 100 and at K = 1000) came back from a graph replay with other bytes than the fill value in them, while every
 // kernel of those chains replayed as captured.  p: 4-byte aligned; bytes: a multiple of 4; every byte becomes

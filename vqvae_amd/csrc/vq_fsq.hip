@@ -49,7 +49,8 @@
 // indices agree; the device's fp64 tanh is not guaranteed correctly rounded, so idx can differ on rows within an ulp of a rounding
 // boundary, and grad_z carries tanh's error through 1 - t^2.
 //
-// Mappings (bodies in vq_fsq.h): NCHW maps one pixel per lane, every channel one coalesced access of the wave; row-major rows are
+// Mappings (bodies in vq_proj.h, which LFQ's row kernels share; the bound, the rounding and the backward bodies in vq_fsq.h; kernels
+// and launches in vq_proj_kernels.h): NCHW maps one pixel per lane, every channel one coalesced access of the wave; row-major rows are
 // staged through vq_cosine.h's LDS tile, 64 rows per wave, in 16-byte accesses (D % 4 == 0 and 16-byte aligned pointers) or element
 // by element, and each lane walks its own row of the tile.  The projection weights lie in LDS and are read as broadcasts.  No
 // scratch.  Every launch is on the caller's stream in one chain; no host sync, no allocation: capturable.
@@ -57,110 +58,9 @@
 
 #include "common.h"
 #include "vq_fsq.h"
+#include "vq_proj_kernels.h"
 
 namespace vqvae {
-
-template <bool DECODE, int WF>
-__global__ __launch_bounds__(kFsqBlockRows) void fsq_fwd_nchw_kernel(FsqArgs a) {
-    __shared__ float wl[WF];
-    fsq_fwd_nchw_body<DECODE>(a, wl);
-}
-
-template <bool DECODE, int V, int WF>
-__global__ __launch_bounds__(kFsqBlockRows) void fsq_fwd_rows_kernel(FsqArgs a) {
-    __shared__ __attribute__((aligned(16))) float tiles[kL2Waves * kL2TileFloats];
-    __shared__ float wl[WF];
-    fsq_fwd_rows_body<DECODE, V>(a, tiles, wl);
-}
-
-template <bool PARAMS, int WF>
-__global__ __launch_bounds__(kFsqBlockRows) void fsq_bwd_nchw_kernel(FsqArgs a) {
-    __shared__ float tile[PARAMS ? kL2Chunk * kFsqNchwStride : 1];
-    __shared__ float wl[WF];
-    __shared__ float chat_l[PARAMS ? kFsqBlockRows * kFsqMaxLevels : 1];
-    __shared__ double gy_l[PARAMS ? kFsqBlockRows * kFsqMaxLevels : 1];
-    fsq_bwd_nchw_body<PARAMS>(a, tile, wl, chat_l, gy_l);
-}
-
-template <bool PARAMS, int V, int WF>
-__global__ __launch_bounds__(kFsqBlockRows) void fsq_bwd_rows_kernel(FsqArgs a) {
-    __shared__ __attribute__((aligned(16))) float tiles[kL2Waves * kL2TileFloats];
-    __shared__ float wl[WF];
-    __shared__ float chat_l[PARAMS ? kFsqBlockRows * kFsqMaxLevels : 1];
-    __shared__ double gy_l[PARAMS ? kFsqBlockRows * kFsqMaxLevels : 1];
-    fsq_bwd_rows_body<PARAMS, V>(a, tiles, wl, chat_l, gy_l);
-}
-
-__global__ __launch_bounds__(kFsqBlockRows) void fsq_param_finalize_kernel(const double *partials, long long nblocks, int D, int d,
-                                                                           float *g_w_in, float *g_b_in, float *g_w_out, float *g_b_out) {
-    fsq_param_finalize_body(partials, nblocks, D, d, g_w_in, g_b_in, g_w_out, g_b_out);
-}
-
-__global__ __launch_bounds__(256) void fsq_perplexity_kernel(const int *hist, int K, long long N, float *perplexity) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int k = tid; k < K; k += 256) {
-        const double p = (double)hist[k] / (double)N;
-        s = s + p * log(p + 1e-10);
-    }
-    block_sum_f64(red, tid, s);
-    if (tid == 0) *perplexity = (float)exp(-red[0]);
-}
-
-static bool fsq_small(const FsqArgs &a) { return a.D <= 64; }
-static unsigned fsq_grid(const FsqArgs &a) { return (unsigned)((a.N + kFsqBlockRows - 1) / kFsqBlockRows); }
-static bool fsq_wide(const FsqArgs &a, uintptr_t bits) { return (a.D & 3) == 0 && !(bits & 15); }
-
-template <bool DECODE>
-static void fsq_launch_fwd(const FsqArgs &a, bool rowmajor, hipStream_t st) {
-    const dim3 grid(fsq_grid(a)), block(kFsqBlockRows);
-    constexpr int S = kFsqWeightFloatsSmall, M = kFsqWeightFloatsMax;
-    if (!rowmajor) {
-        if (fsq_small(a)) hipLaunchKernelGGL((fsq_fwd_nchw_kernel<DECODE, S>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((fsq_fwd_nchw_kernel<DECODE, M>), grid, block, 0, st, a);
-        return;
-    }
-    const bool wide = fsq_wide(a, reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.out));
-    if (wide && fsq_small(a)) hipLaunchKernelGGL((fsq_fwd_rows_kernel<DECODE, 4, S>), grid, block, 0, st, a);
-    else if (wide) hipLaunchKernelGGL((fsq_fwd_rows_kernel<DECODE, 4, M>), grid, block, 0, st, a);
-    else if (fsq_small(a)) hipLaunchKernelGGL((fsq_fwd_rows_kernel<DECODE, 1, S>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((fsq_fwd_rows_kernel<DECODE, 1, M>), grid, block, 0, st, a);
-}
-
-void launch_fsq_forward(const FsqArgs &a, bool rowmajor, hipStream_t st) { fsq_launch_fwd<false>(a, rowmajor, st); }
-void launch_fsq_decode(const FsqArgs &a, bool rowmajor, hipStream_t st) { fsq_launch_fwd<true>(a, rowmajor, st); }
-
-template <bool PARAMS>
-static void fsq_launch_bwd(const FsqArgs &a, bool rowmajor, hipStream_t st) {
-    const dim3 grid(fsq_grid(a)), block(kFsqBlockRows);
-    constexpr int S = kFsqWeightFloatsSmall, M = kFsqWeightFloatsMax;
-    if (!rowmajor) {
-        if (fsq_small(a)) hipLaunchKernelGGL((fsq_bwd_nchw_kernel<PARAMS, S>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((fsq_bwd_nchw_kernel<PARAMS, M>), grid, block, 0, st, a);
-        return;
-    }
-    const bool wide = fsq_wide(a, reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.out));
-    if (wide && fsq_small(a)) hipLaunchKernelGGL((fsq_bwd_rows_kernel<PARAMS, 4, S>), grid, block, 0, st, a);
-    else if (wide) hipLaunchKernelGGL((fsq_bwd_rows_kernel<PARAMS, 4, M>), grid, block, 0, st, a);
-    else if (fsq_small(a)) hipLaunchKernelGGL((fsq_bwd_rows_kernel<PARAMS, 1, S>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((fsq_bwd_rows_kernel<PARAMS, 1, M>), grid, block, 0, st, a);
-}
-
-void launch_fsq_backward(const FsqArgs &a, bool rowmajor, hipStream_t st) {
-    if (a.partials) fsq_launch_bwd<true>(a, rowmajor, st);
-    else fsq_launch_bwd<false>(a, rowmajor, st);
-}
-
-// ---- the entries' checks: the header's codes, before any launch ---------------------------------------------------------------------
-
-struct FsqSpan { const void *p; size_t bytes; };
-
-static bool fsq_overlap(const FsqSpan &x, const FsqSpan &y) {
-    if (!x.p || !y.p) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-    return a < b + y.bytes && b < a + x.bytes;
-}
 
 // levels and the constants that follow from them -> a; VQVAE_ERR_UNSUPPORTED outside the envelope
 static int fsq_levels(const int *levels, int n_levels, int D, FsqArgs &a) {
@@ -185,31 +85,10 @@ static int fsq_levels(const int *levels, int n_levels, int D, FsqArgs &a) {
     return VQVAE_OK;
 }
 
-static int fsq_shape(int64_t B, int H, int W, FsqArgs &a) {
-    if (B < 1 || H < 1 || W < 1) return VQVAE_ERR_SHAPE;
-    if ((long long)H * W > INT32_MAX) return VQVAE_ERR_UNSUPPORTED;
-    const long long HW = (long long)H * W;
-    if (B > INT32_MAX / HW) return VQVAE_ERR_UNSUPPORTED;
-    a.HW = (int)HW;
-    a.N = B * HW;
-    return VQVAE_OK;
-}
-
-// every pointer aligned to `align` of its span (NULL passes), and no output on an input
-static int fsq_pointers(const FsqSpan *in, const int *in_align, int n_in, const FsqSpan *out, const int *out_align, int n_out) {
-    for (int i = 0; i < n_in; ++i)
-        if (reinterpret_cast<uintptr_t>(in[i].p) & (uintptr_t)(in_align[i] - 1)) return VQVAE_ERR_UNSUPPORTED;
-    for (int o = 0; o < n_out; ++o) {
-        if (reinterpret_cast<uintptr_t>(out[o].p) & (uintptr_t)(out_align[o] - 1)) return VQVAE_ERR_UNSUPPORTED;
-        for (int i = 0; i < n_in; ++i)
-            if (fsq_overlap(out[o], in[i])) return VQVAE_ERR_UNSUPPORTED;
-    }
-    return VQVAE_OK;
-}
-
-static size_t fsq_backward_ws(long long N, int D, int d) {
-    const size_t nblocks = (size_t)((N + kFsqBlockRows - 1) / kFsqBlockRows);
-    return nblocks * (size_t)(2 * D * d + D + d) * sizeof(double);
+// the entries' first checks, in the header's order: the shape, then the levels
+static int fsq_shape(int64_t B, int H, int W, const int *levels, int n_levels, int D, FsqArgs &a) {
+    const int rc = check_rows_shape(B, H, W, a.N, a.HW);
+    return rc != VQVAE_OK ? rc : fsq_levels(levels, n_levels, D, a);
 }
 
 }  // namespace vqvae
@@ -224,23 +103,20 @@ int vqvae_fsq_forward_f32(const float *z_e, const float *w_in, const float *b_in
     if (!z_e || !w_in || !b_in || !levels || !idx || (z_q && (!w_out || !b_out)) || (perplexity && !hist)) return VQVAE_ERR_NULL;
     if (flags & ~VQVAE_VQ_ROWMAJOR) return VQVAE_ERR_UNSUPPORTED;
     FsqArgs a = {};
-    int rc = fsq_shape(B, H, W, a);
-    if (rc == VQVAE_OK) rc = fsq_levels(levels, n_levels, D, a);
+    int rc = fsq_shape(B, H, W, levels, n_levels, D, a);
     if (rc != VQVAE_OK) return rc;
     const size_t nd = (size_t)a.N * D * 4, wd = (size_t)a.d * D * 4;
-    const FsqSpan in[] = {{z_e, nd}, {w_in, wd}, {b_in, (size_t)a.d * 4}, {w_out, wd}, {b_out, (size_t)D * 4}};
-    const int in_al[] = {4, 4, 4, 4, 4};
-    const FsqSpan out[] = {{z_q, nd}, {idx, (size_t)a.N * 8}, {hist, (size_t)a.K * 4}, {perplexity, 4}};
-    const int out_al[] = {4, 8, 4, 4};
-    if ((rc = fsq_pointers(in, in_al, 5, out, out_al, 4)) != VQVAE_OK) return rc;
+    const Span in[] = {{z_e, nd, 4}, {w_in, wd, 4}, {b_in, (size_t)a.d * 4, 4}, {w_out, wd, 4}, {b_out, (size_t)D * 4, 4}};
+    const Span out[] = {{z_q, nd, 4}, {idx, (size_t)a.N * 8, 8}, {hist, (size_t)a.K * 4, 4}, {perplexity, 4, 4}};
+    if ((rc = check_pointers(in, 5, out, 4)) != VQVAE_OK) return rc;
     a.z = z_e; a.w_in = w_in; a.b_in = b_in; a.w_out = z_q ? w_out : nullptr; a.b_out = z_q ? b_out : nullptr;
     a.out = z_q; a.idx = reinterpret_cast<long long *>(idx); a.hist = hist;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // hist = 0 in front of the forward, by a kernel (common.h: fill_bytes_async): a captured hipMemsetAsync of its K * 4 bytes (4000 for
     // levels (8, 5, 5, 5)) came back from a graph replay with other values than zero in it
     if (hist && (rc = fill_bytes_async(hist, 0, (size_t)a.K * 4, st)) != 0) return rc;
-    launch_fsq_forward(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
-    if (perplexity) hipLaunchKernelGGL(fsq_perplexity_kernel, dim3(1), dim3(256), 0, st, hist, a.K, a.N, perplexity);
+    proj_launch_fwd<Fsq, false>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
+    if (perplexity) hipLaunchKernelGGL(proj_perplexity_kernel<Fsq>, dim3(1), dim3(256), 0, st, hist, a.K, a.N, perplexity);
     return (int)hipGetLastError();
 }
 
@@ -249,22 +125,19 @@ int vqvae_fsq_decode_indices_f32(const int64_t *idx, const float *w_out, const f
     if (!idx || !w_out || !b_out || !levels || !z_q) return VQVAE_ERR_NULL;
     if (flags & ~VQVAE_VQ_ROWMAJOR) return VQVAE_ERR_UNSUPPORTED;
     FsqArgs a = {};
-    int rc = fsq_shape(B, H, W, a);
-    if (rc == VQVAE_OK) rc = fsq_levels(levels, n_levels, D, a);
+    int rc = fsq_shape(B, H, W, levels, n_levels, D, a);
     if (rc != VQVAE_OK) return rc;
-    const FsqSpan in[] = {{idx, (size_t)a.N * 8}, {w_out, (size_t)a.d * D * 4}, {b_out, (size_t)D * 4}};
-    const int in_al[] = {8, 4, 4};
-    const FsqSpan out[] = {{z_q, (size_t)a.N * D * 4}};
-    const int out_al[] = {4};
-    if ((rc = fsq_pointers(in, in_al, 3, out, out_al, 1)) != VQVAE_OK) return rc;
+    const Span in[] = {{idx, (size_t)a.N * 8, 8}, {w_out, (size_t)a.d * D * 4, 4}, {b_out, (size_t)D * 4, 4}};
+    const Span out[] = {{z_q, (size_t)a.N * D * 4, 4}};
+    if ((rc = check_pointers(in, 3, out, 1)) != VQVAE_OK) return rc;
     a.idx_in = reinterpret_cast<const long long *>(idx); a.w_out = w_out; a.b_out = b_out; a.out = z_q;
-    launch_fsq_decode(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, static_cast<hipStream_t>(stream));
+    proj_launch_fwd<Fsq, true>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, static_cast<hipStream_t>(stream));
     return (int)hipGetLastError();
 }
 
 size_t vqvae_fsq_backward_workspace_bytes(int64_t N, int D, int n_levels) {
     if (N < 1 || N > INT32_MAX || D < 1 || D > 256 || n_levels < 1 || n_levels > kFsqMaxLevels) return 0;
-    return fsq_backward_ws(N, D, n_levels);
+    return proj_partial_bytes(N, D, n_levels);
 }
 
 int vqvae_fsq_backward_f32(const float *z_e, const float *grad_zq, const float *w_in, const float *b_in, const float *w_out,
@@ -275,27 +148,17 @@ int vqvae_fsq_backward_f32(const float *z_e, const float *grad_zq, const float *
     if (!z_e || !grad_zq || !w_in || !b_in || !w_out || !levels || (!grad_z && !params)) return VQVAE_ERR_NULL;
     if (flags & ~VQVAE_VQ_ROWMAJOR) return VQVAE_ERR_UNSUPPORTED;
     FsqArgs a = {};
-    int rc = fsq_shape(B, H, W, a);
-    if (rc == VQVAE_OK) rc = fsq_levels(levels, n_levels, D, a);
+    int rc = fsq_shape(B, H, W, levels, n_levels, D, a);
     if (rc != VQVAE_OK) return rc;
-    const size_t nd = (size_t)a.N * D * 4, wd = (size_t)a.d * D * 4, need = params ? fsq_backward_ws(a.N, D, a.d) : 0;
-    const FsqSpan in[] = {{z_e, nd}, {grad_zq, nd}, {w_in, wd}, {b_in, (size_t)a.d * 4}, {w_out, wd}};
-    const int in_al[] = {4, 4, 4, 4, 4};
-    const FsqSpan out[] = {{grad_z, nd}, {grad_w_in, wd}, {grad_b_in, (size_t)a.d * 4}, {grad_w_out, wd}, {grad_b_out, (size_t)D * 4},
-                           {params ? workspace : nullptr, need}};
-    const int out_al[] = {4, 4, 4, 4, 4, 8};
-    if ((rc = fsq_pointers(in, in_al, 5, out, out_al, 6)) != VQVAE_OK) return rc;
+    const size_t nd = (size_t)a.N * D * 4, wd = (size_t)a.d * D * 4, need = params ? proj_partial_bytes(a.N, D, a.d) : 0;
+    const Span in[] = {{z_e, nd, 4}, {grad_zq, nd, 4}, {w_in, wd, 4}, {b_in, (size_t)a.d * 4, 4}, {w_out, wd, 4}};
+    const Span out[] = {{grad_z, nd, 4}, {grad_w_in, wd, 4}, {grad_b_in, (size_t)a.d * 4, 4}, {grad_w_out, wd, 4},
+                        {grad_b_out, (size_t)D * 4, 4}, {params ? workspace : nullptr, need, 8}};
+    if ((rc = check_pointers(in, 5, out, 6)) != VQVAE_OK) return rc;
     if (params && (!workspace || workspace_bytes < need)) return VQVAE_ERR_WORKSPACE;
     a.z = z_e; a.g = grad_zq; a.w_in = w_in; a.b_in = b_in; a.w_out = w_out; a.out = grad_z;
     a.partials = params ? static_cast<double *>(workspace) : nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    launch_fsq_backward(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
-    if (params) {
-        const int P = 2 * D * a.d + D + a.d;
-        hipLaunchKernelGGL(fsq_param_finalize_kernel, dim3((unsigned)((P + kFsqBlockRows - 1) / kFsqBlockRows)), dim3(kFsqBlockRows), 0,
-                           st, a.partials, (long long)((a.N + kFsqBlockRows - 1) / kFsqBlockRows), D, a.d, grad_w_in, grad_b_in,
-                           grad_w_out, grad_b_out);
-    }
+    proj_launch_bwd<Fsq>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, grad_w_in, grad_b_in, grad_w_out, grad_b_out, static_cast<hipStream_t>(stream));
     return (int)hipGetLastError();
 }
 

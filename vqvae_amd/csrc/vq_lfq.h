@@ -1,18 +1,15 @@
-// Lookup-free quantization (vq_lfq.hip, whose header states the arithmetic): the per-row operations and the whole bodies of the
-// kernels.  Plain C++ over `__device__ __forceinline__`, so that tests/host/lfq_harness.cpp compiles THIS text for the host (blockIdx /
-// threadIdx, f32x4, __syncthreads, atomicAdd and <cmath> supplied by the harness) and runs it under the sanitizers.  The LDS tile, its
-// 16-byte / element copies and the lane-walks-its-own-row scheme are vq_cosine.h's; the row kernels follow vq_fsq.h's.
+// Lookup-free quantization (vq_lfq.hip, whose header states the arithmetic): what LFQ does with the finished sums of a row -- the sign
+// code -- every loss kernel, and its backward bodies, which read the y and e the earlier launches left.  The kernel skeleton around
+// them (the weights in LDS, the projections, the forward / decode bodies, the parameter-gradient reductions and their second launch)
+// is vq_proj.h's, the same text FSQ's row kernels compile; it takes `Lfq` below as its policy.  Plain C++ over
+// `__device__ __forceinline__`, so that tests/host/lfq_harness.cpp compiles THIS text for the host and runs it under the sanitizers.
 #pragma once
 
-#include "vq_cosine.h"
+#include "vq_proj.h"
 
 namespace vqvae {
 
 constexpr int kLfqMaxBits = 16;
-constexpr int kLfqBlockRows = 64 * kL2Waves;                          // rows of one workgroup of the row kernels, in either layout: 256
-constexpr int kLfqWeightFloatsMax = 2 * kLfqMaxBits * 256 + kLfqMaxBits + 256;   // W_in, b_in (16 slots), W_out, b_out at D = 256
-constexpr int kLfqWeightFloatsSmall = 2 * kLfqMaxBits * 64 + kLfqMaxBits + 64;   // ... at D <= 64
-constexpr int kLfqNchwStride = kLfqBlockRows + 1;                     // dwords between two channels of the backward's NCHW tile
 constexpr int kLfqChunkRows = 64;                                     // rows whose probabilities the avg kernel stages at a time
 constexpr int kLfqTileCodes = 4 * 256;                                // codes of one workgroup of the avg kernel: 4 per thread
 constexpr int kLfqLdsLogK = 4096;                                     // log avg lies in LDS up to this K (padded: kLfqLogLdsDoubles)
@@ -21,20 +18,10 @@ constexpr int kLfqLogLdsDoublesSmall = 32 * 33;                       // K <= 10
 constexpr int kLfqGradThreads = 64;                                  // one wave per row in the entropy-gradient kernel
 constexpr int kLfqScalarSlots = 2 * kLfqMaxBits;                      // per partition: [P sums of the d channels] [C sums]
 
-struct LfqArgs {
-    const float *z;                                  // forward: z_e.  backward: z_e.  (N, D) rows or (B, D, HW) maps
-    const float *g;                                  // backward: grad_zq, z's layout, or NULL (zero)
-    const float *w_in, *b_in, *w_out, *b_out;        // (d, D), (d), (D, d), (D); NULL where the kernel does not read them
-    const long long *idx_in;                         // decode
-    float *out;                                      // forward / decode: z_q; backward: grad_z.  May be NULL (forward, backward)
-    long long *idx;                                  // forward, may be NULL (the backward's y pass)
-    int *hist;                                       // forward, may be NULL; zero on entry
+struct LfqArgs : ProjArgs {
     float *y;                                        // forward: (N, d) out, may be NULL.  backward: (N, d) in
     const double *e;                                 // backward: (N, d) d loss / d y without grad_loss, or NULL (no loss gradient)
     const float *gl;                                 // backward: grad_loss (device scalar), NULL = 1
-    double *partials;                                // backward: one record of lfq_partial_count() doubles per workgroup, or NULL
-    long long N;
-    int D, HW, d, K;
 };
 
 // what the loss kernels share
@@ -51,35 +38,7 @@ struct LfqLossArgs {
     double *e;                                       // backward: (N, d)
 };
 
-// one workgroup's record of parameter-gradient partials: [W_out (D, d)] [b_out (D)] [W_in (d, D)] [b_in (d)]
-__device__ __forceinline__ int lfq_partial_count(int D, int d) { return 2 * D * d + D + d; }
-
-// ---- the weights in LDS: [W_in d D] [b_in 16] [W_out D d] [b_out D]; uniform reads are broadcasts --------------------------------
-struct LfqLdsW { const float *w_in, *b_in, *w_out, *b_out; };
-
-__device__ __forceinline__ LfqLdsW lfq_stage_weights(const LfqArgs &a, float *w) {
-    const int dD = a.d * a.D;
-    float *wi = w, *bi = w + dD, *wo = bi + kLfqMaxBits, *bo = wo + dD;
-    for (int i = threadIdx.x; i < dD; i += kLfqBlockRows) {
-        if (a.w_in) wi[i] = a.w_in[i];
-        if (a.w_out) wo[i] = a.w_out[i];
-    }
-    if (a.b_in)
-        for (int i = threadIdx.x; i < a.d; i += kLfqBlockRows) bi[i] = a.b_in[i];
-    if (a.b_out)
-        for (int i = threadIdx.x; i < a.D; i += kLfqBlockRows) bo[i] = a.b_out[i];
-    __syncthreads();
-    return {wi, bi, wo, bo};
-}
-
 // ---- the per-row operations, one IEEE operation each -----------------------------------------------------------------------------
-
-// channel c of a row joins the d sums `acc` through row c of a (D, d)-shaped view: w[j * sj + c * sc]
-__device__ __forceinline__ void lfq_project(double *acc, const float *w, int sj, int sc, int c, int d, float x) {
-#pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j)
-        if (j < d) acc[j] = acc[j] + (double)w[j * sj + c * sc] * (double)x;
-}
 
 // the code of one y: +1 above zero, -1 at and below it, NaN for a NaN
 __device__ __forceinline__ float lfq_code(float y) { return y != y ? __builtin_nanf("") : (y > 0.0f ? 1.0f : -1.0f); }
@@ -95,33 +54,6 @@ __device__ __forceinline__ long long lfq_quantize(int d, const double *acc, floa
             idx += y[j] > 0.0f ? (1LL << j) : 0LL;
         }
     return idx;
-}
-
-// an index -> codes; outside [0, K): NaN codes
-__device__ __forceinline__ void lfq_codes_of_index(int d, int K, long long idx, float *code) {
-    const bool ok = idx >= 0 && idx < (long long)K;
-    const unsigned u = ok ? (unsigned)idx : 0u;
-#pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j)
-        if (j < d) code[j] = ok ? (((u >> j) & 1u) ? 1.0f : -1.0f) : __builtin_nanf("");
-}
-
-// z_q of channel c from the codes
-__device__ __forceinline__ float lfq_zq(const LfqLdsW &w, int c, int d, const float *code) {
-    double s = (double)w.b_out[c];
-#pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j)
-        if (j < d) s = s + (double)w.w_out[c * d + j] * (double)code[j];
-    return (float)s;
-}
-
-// grad_z of channel c from gy (fp64, unrounded)
-__device__ __forceinline__ float lfq_gz(const LfqLdsW &w, int c, int D, int d, const double *gy) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j)
-        if (j < d) s = s + (double)w.w_in[j * D + c] * gy[j];
-    return (float)s;
 }
 
 // p+ = sigma(a), p- = sigma(-a), each computed directly from e = exp(-|a|); small = sigma(-|a|)
@@ -145,8 +77,7 @@ __device__ __forceinline__ void lfq_block_sum(double *red, int tid, double v) {
     }
 }
 
-// ---- forward and decode ----------------------------------------------------------------------------------------------------------
-
+// what the forward keeps of a row
 __device__ __forceinline__ void lfq_row_out(const LfqArgs &a, long long row, long long idx, const float *y) {
     if (a.idx) a.idx[row] = idx;
     if (a.hist) atomicAdd(a.hist + idx, 1);
@@ -154,84 +85,6 @@ __device__ __forceinline__ void lfq_row_out(const LfqArgs &a, long long row, lon
 #pragma unroll
         for (int j = 0; j < kLfqMaxBits; ++j)
             if (j < a.d) a.y[(size_t)row * a.d + j] = y[j];
-    }
-}
-
-// NCHW maps: a lane owns one pixel; every channel is one coalesced access of the wave
-template <bool DECODE>
-__device__ __forceinline__ void lfq_fwd_nchw_body(const LfqArgs &a, float *wl) {
-    const LfqLdsW w = lfq_stage_weights(a, wl);
-    const long long row = (long long)blockIdx.x * kLfqBlockRows + threadIdx.x;
-    if (row >= a.N) return;                                                   // (no barrier below)
-    const int D = a.D, d = a.d;
-    const long long b = row / a.HW;
-    const size_t base = (size_t)b * D * a.HW + (size_t)(row - b * a.HW), stride = (size_t)a.HW;
-    float code[kLfqMaxBits];
-    if constexpr (DECODE) {
-        lfq_codes_of_index(d, a.K, a.idx_in[row], code);
-    } else {
-        double acc[kLfqMaxBits];
-        float y[kLfqMaxBits];
-#pragma unroll
-        for (int j = 0; j < kLfqMaxBits; ++j) acc[j] = j < d ? (double)w.b_in[j] : 0.0;
-#pragma unroll 4
-        for (int c = 0; c < D; ++c) lfq_project(acc, w.w_in, D, 1, c, d, a.z[base + c * stride]);
-        const long long idx = lfq_quantize(d, acc, y, code);
-        lfq_row_out(a, row, idx, y);
-        if (!a.out) return;
-    }
-#pragma unroll 4
-    for (int c = 0; c < D; ++c) a.out[base + c * stride] = lfq_zq(w, c, d, code);
-}
-
-// row-major rows: a wave owns 64 consecutive rows and stages 64 channels of them at a time through its LDS tile (vq_cosine.h)
-template <bool DECODE, int V>
-__device__ __forceinline__ void lfq_fwd_rows_body(const LfqArgs &a, float *tiles, float *wl) {
-    const LfqLdsW w = lfq_stage_weights(a, wl);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float *tx = tiles + wave * kL2TileFloats, *mx = tx + lane * kL2Stride;
-    const long long r0 = ((long long)blockIdx.x * kL2Waves + wave) * 64, left = a.N - r0;
-    const int nr = left <= 0 ? 0 : (left < 64 ? (int)left : 64);              // a wave without rows still meets every barrier
-    const int D = a.D, d = a.d, nch = (D + kL2Chunk - 1) / kL2Chunk;
-    const bool mine = lane < nr;
-    float code[kLfqMaxBits];
-    if constexpr (DECODE) {
-        lfq_codes_of_index(d, a.K, mine ? a.idx_in[r0 + lane] : 0, code);
-    } else {
-        double acc[kLfqMaxBits];
-        float y[kLfqMaxBits];
-#pragma unroll
-        for (int j = 0; j < kLfqMaxBits; ++j) acc[j] = j < d ? (double)w.b_in[j] : 0.0;
-        for (int ch = 0; ch < nch; ++ch) {
-            const int c0 = ch * kL2Chunk, cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
-            l2n_copy<V, true>(const_cast<float *>(a.z), tx, r0, nr, D, c0, cw, lane);
-            __syncthreads();
-            if (mine)
-                for (int c = 0; c < cw; c += 4) {
-                    float xv[4];
-                    l2n_load<4>(mx, (size_t)c, xv);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (c + k < cw) lfq_project(acc, w.w_in, D, 1, c0 + c + k, d, xv[k]);
-                }
-            __syncthreads();
-        }
-        const long long idx = lfq_quantize(d, acc, y, code);
-        if (mine) lfq_row_out(a, r0 + lane, idx, y);
-        if (!a.out) return;                                                   // (uniform: every thread leaves)
-    }
-    for (int ch = 0; ch < nch; ++ch) {
-        const int c0 = ch * kL2Chunk, cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
-        if (mine)
-            for (int c = 0; c < cw; c += 4) {
-                float o[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = c + k < cw ? lfq_zq(w, c0 + c + k, d, code) : 0.0f;
-                l2n_store<4>(mx, (size_t)c, o);                               // (slots past cw belong to the row's padding)
-            }
-        __syncthreads();
-        l2n_copy<V, false>(a.out, tx, r0, nr, D, c0, cw, lane);
-        __syncthreads();
     }
 }
 
@@ -426,57 +279,6 @@ __device__ __forceinline__ void lfq_entgrad_body(const LfqLossArgs &a, double *l
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------
-// The row-local part runs as the forward does, from the y the first launch left.  The parameter gradients are sums over rows: every
-// workgroup owns the SAME 256 consecutive rows in either layout, leaves their codes c (fp32) and gy (fp64) in LDS, brings 64 channels
-// of g, then of z, into a tile, and thread o of the workgroup adds the 256 terms of output o one row after the other, in ascending
-// row order, into an fp64 partial of the workgroup's record.  lfq_param_finalize_body adds the records in ascending workgroup order.
-// `tile` is addressed as tile[row * RS + channel * CS] (vq_fsq.h).
-
-template <int RS, int CS>
-__device__ __forceinline__ void lfq_reduce_w_out(const LfqArgs &a, const float *tile, const float *code_l, int c0, int cw, int nrb,
-                                                 double *part) {
-    const int d = a.d;
-    const bool have = a.g != nullptr;                                         // no upstream gradient: the sums are 0.0
-    for (int o = threadIdx.x; o < cw * d + cw; o += kLfqBlockRows) {
-        double s = 0.0;
-        if (o < cw * d) {
-            const int j = o / cw, c = o - j * cw;
-            if (have) {
-#pragma unroll 8
-                for (int r = 0; r < nrb; ++r) s = s + (double)tile[r * RS + c * CS] * (double)code_l[r * kLfqMaxBits + j];
-            }
-            part[(c0 + c) * d + j] = s;
-        } else {
-            const int c = o - cw * d;
-            if (have) {
-#pragma unroll 8
-                for (int r = 0; r < nrb; ++r) s = s + (double)tile[r * RS + c * CS];
-            }
-            part[a.D * d + c0 + c] = s;
-        }
-    }
-}
-
-template <int RS, int CS>
-__device__ __forceinline__ void lfq_reduce_w_in(const LfqArgs &a, const float *tile, const double *gy_l, int c0, int cw, int nrb,
-                                                double *part) {
-    const int d = a.d, D = a.D;
-    double *p_w = part + D * d + D, *p_b = p_w + d * D;
-    for (int o = threadIdx.x; o < cw * d + (c0 == 0 ? d : 0); o += kLfqBlockRows) {
-        double s = 0.0;
-        if (o < cw * d) {
-            const int j = o / cw, c = o - j * cw;
-#pragma unroll 8
-            for (int r = 0; r < nrb; ++r) s = s + gy_l[r * kLfqMaxBits + j] * (double)tile[r * RS + c * CS];
-            p_w[j * D + c0 + c] = s;
-        } else {
-            const int j = o - cw * d;
-#pragma unroll 8
-            for (int r = 0; r < nrb; ++r) s = s + gy_l[r * kLfqMaxBits + j];
-            p_b[j] = s;
-        }
-    }
-}
 
 // gy of a row from its gc sums: gy_j = gc_j + g * e_j (two operations; without e: gc_j); codes and gy to LDS for the reductions
 __device__ __forceinline__ void lfq_bwd_row(const LfqArgs &a, long long row, const double *acc_g, bool params, bool mine, float *code_l,
@@ -496,127 +298,123 @@ __device__ __forceinline__ void lfq_bwd_row(const LfqArgs &a, long long row, con
         }
 }
 
-template <bool PARAMS>
-__device__ __forceinline__ void lfq_bwd_nchw_body(const LfqArgs &a, float *tile, float *wl, float *code_l, double *gy_l) {
-    const LfqLdsW w = lfq_stage_weights(a, wl);
-    const long long row0 = (long long)blockIdx.x * kLfqBlockRows, row = row0 + threadIdx.x, left = a.N - row0;
-    const int nrb = left < kLfqBlockRows ? (int)left : kLfqBlockRows;
-    const bool mine = row < a.N;
-    const int D = a.D, d = a.d;
-    const long long b = mine ? row / a.HW : 0;
-    const size_t base = (size_t)b * D * a.HW + (size_t)(mine ? row - b * a.HW : 0), stride = (size_t)a.HW;
-    double acc_g[kLfqMaxBits], gy[kLfqMaxBits];
+// ---- vq_proj.h's policy ------------------------------------------------------------------------------------------------------------
+struct Lfq {
+    using Args = LfqArgs;
+    static constexpr int kMaxD = kLfqMaxBits, kNchwUnroll = 4;
+    using Side = float[kLfqMaxBits];                 // y
+
+    // an index -> codes; outside [0, K): NaN codes
+    static __device__ __forceinline__ void codes_of_index(const LfqArgs &a, long long idx, float *code) {
+        const bool ok = idx >= 0 && idx < (long long)a.K;
+        const unsigned u = ok ? (unsigned)idx : 0u;
 #pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j) acc_g[j] = 0.0;
-    if (mine && a.g) {
-#pragma unroll 4
-        for (int c = 0; c < D; ++c) lfq_project(acc_g, w.w_out, 1, d, c, d, a.g[base + c * stride]);
+        for (int j = 0; j < kLfqMaxBits; ++j)
+            if (j < a.d) code[j] = ok ? (((u >> j) & 1u) ? 1.0f : -1.0f) : __builtin_nanf("");
     }
-    lfq_bwd_row(a, row, acc_g, PARAMS, mine, code_l, gy_l, gy);
-    if (a.out && mine) {
-#pragma unroll 4
-        for (int c = 0; c < D; ++c) a.out[base + c * stride] = lfq_gz(w, c, D, d, gy);
+
+    static __device__ __forceinline__ void quantize_row(const LfqArgs &a, const double *acc, long long row, bool mine, float *code,
+                                                        float *y) {
+        const long long idx = lfq_quantize(a.d, acc, y, code);
+        if (mine) lfq_row_out(a, row, idx, y);
     }
-    if constexpr (PARAMS) {
-        double *part = a.partials + (size_t)blockIdx.x * lfq_partial_count(D, d);
-        for (int c0 = 0; c0 < D; c0 += kL2Chunk) {
-            const int cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
-            __syncthreads();                                                  // code_l / gy_l written; the tile's last readers are done
-            if (mine && a.g)
-                for (int c = 0; c < cw; ++c) tile[c * kLfqNchwStride + threadIdx.x] = a.g[base + (c0 + c) * stride];
-            __syncthreads();
-            lfq_reduce_w_out<1, kLfqNchwStride>(a, tile, code_l, c0, cw, nrb, part);
-            __syncthreads();
-            if (mine)
-                for (int c = 0; c < cw; ++c) tile[c * kLfqNchwStride + threadIdx.x] = a.z[base + (c0 + c) * stride];
-            __syncthreads();
-            lfq_reduce_w_in<1, kLfqNchwStride>(a, tile, gy_l, c0, cw, nrb, part);
+
+    // the backward: the row-local part runs from the y the first launch left; only gc is projected, and only where g is given
+    template <bool PARAMS>
+    static __device__ __forceinline__ void bwd_nchw_body(const LfqArgs &a, float *tile, float *wl, float *code_l, double *gy_l) {
+        const ProjLdsW w = proj_stage_weights<kMaxD>(a, wl);
+        const ProjNchwPos p = proj_nchw_pos(a);
+        const int D = a.D, d = a.d;
+        double acc_g[kMaxD], gy[kMaxD];
+#pragma unroll
+        for (int j = 0; j < kMaxD; ++j) acc_g[j] = 0.0;
+        if (p.mine && a.g) {
+#pragma unroll 4
+            for (int c = 0; c < D; ++c) proj_project<kMaxD>(acc_g, w.w_out, 1, d, c, d, a.g[p.base + c * p.stride]);
+        }
+        lfq_bwd_row(a, p.row, acc_g, PARAMS, p.mine, code_l, gy_l, gy);
+        if (a.out && p.mine) {
+#pragma unroll 4
+            for (int c = 0; c < D; ++c) a.out[p.base + c * p.stride] = proj_gz<kMaxD>(w, c, D, d, gy);
+        }
+        if constexpr (PARAMS) {
+            double *part = a.partials + (size_t)blockIdx.x * proj_partial_count(D, d);
+            for (int c0 = 0; c0 < D; c0 += kL2Chunk) {
+                const int cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
+                __syncthreads();                                              // code_l / gy_l written; the tile's last readers are done
+                if (p.mine && a.g)
+                    for (int c = 0; c < cw; ++c) tile[c * kProjNchwStride + threadIdx.x] = a.g[p.base + (c0 + c) * p.stride];
+                __syncthreads();
+                proj_reduce_w_out<kMaxD, 1, kProjNchwStride, true>(a, tile, code_l, c0, cw, p.nrb, part);
+                __syncthreads();
+                if (p.mine)
+                    for (int c = 0; c < cw; ++c) tile[c * kProjNchwStride + threadIdx.x] = a.z[p.base + (c0 + c) * p.stride];
+                __syncthreads();
+                proj_reduce_w_in<kMaxD, 1, kProjNchwStride>(a, tile, gy_l, c0, cw, p.nrb, part);
+            }
         }
     }
-}
 
-template <bool PARAMS, int V>
-__device__ __forceinline__ void lfq_bwd_rows_body(const LfqArgs &a, float *tiles, float *wl, float *code_l, double *gy_l) {
-    const LfqLdsW w = lfq_stage_weights(a, wl);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float *tx = tiles + wave * kL2TileFloats, *mx = tx + lane * kL2Stride;
-    const long long row0 = (long long)blockIdx.x * kLfqBlockRows, r0 = row0 + wave * 64, left = a.N - r0, leftb = a.N - row0;
-    const int nr = left <= 0 ? 0 : (left < 64 ? (int)left : 64);
-    const int nrb = leftb < kLfqBlockRows ? (int)leftb : kLfqBlockRows;
-    const int D = a.D, d = a.d, nch = (D + kL2Chunk - 1) / kL2Chunk;
-    const bool mine = lane < nr;
-    double acc_g[kLfqMaxBits], gy[kLfqMaxBits];
+    template <bool PARAMS, int V>
+    static __device__ __forceinline__ void bwd_rows_body(const LfqArgs &a, float *tiles, float *wl, float *code_l, double *gy_l) {
+        const ProjLdsW w = proj_stage_weights<kMaxD>(a, wl);
+        const ProjRowsPos p = proj_rows_pos(a, tiles);
+        const int D = a.D, d = a.d, nch = (D + kL2Chunk - 1) / kL2Chunk;
+        double acc_g[kMaxD], gy[kMaxD];
 #pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j) acc_g[j] = 0.0;
-    if (a.g)                                                                  // (uniform)
+        for (int j = 0; j < kMaxD; ++j) acc_g[j] = 0.0;
+        if (a.g)                                                                  // (uniform)
+            for (int ch = 0; ch < nch; ++ch) {
+                const int c0 = ch * kL2Chunk, cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
+                l2n_copy<V, true>(const_cast<float *>(a.g), p.tx, p.r0, p.nr, D, c0, cw, p.lane);
+                __syncthreads();
+                if (p.mine)
+                    for (int c = 0; c < cw; c += 4) {
+                        float xv[4];
+                        l2n_load<4>(p.mx, (size_t)c, xv);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (c + k < cw) proj_project<kMaxD>(acc_g, w.w_out, 1, d, c0 + c + k, d, xv[k]);
+                    }
+                __syncthreads();
+            }
+        lfq_bwd_row(a, p.r0 + p.lane, acc_g, PARAMS, p.mine, code_l, gy_l, gy);
+        double *part = PARAMS ? a.partials + (size_t)blockIdx.x * proj_partial_count(D, d) : nullptr;
         for (int ch = 0; ch < nch; ++ch) {
             const int c0 = ch * kL2Chunk, cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
-            l2n_copy<V, true>(const_cast<float *>(a.g), tx, r0, nr, D, c0, cw, lane);
-            __syncthreads();
-            if (mine)
-                for (int c = 0; c < cw; c += 4) {
-                    float xv[4];
-                    l2n_load<4>(mx, (size_t)c, xv);
+            if constexpr (PARAMS) {
+                if (a.g) l2n_copy<V, true>(const_cast<float *>(a.g), p.tx, p.r0, p.nr, D, c0, cw, p.lane);
+                __syncthreads();                                              // (and code_l / gy_l are written)
+                proj_reduce_w_out<kMaxD, kL2Stride, 1, true>(a, tiles, code_l, c0, cw, p.nrb, part);
+                __syncthreads();
+                l2n_copy<V, true>(const_cast<float *>(a.z), p.tx, p.r0, p.nr, D, c0, cw, p.lane);
+                __syncthreads();
+                proj_reduce_w_in<kMaxD, kL2Stride, 1>(a, tiles, gy_l, c0, cw, p.nrb, part);
+                __syncthreads();
+            }
+            if (a.out) {
+                if (p.mine)
+                    for (int c = 0; c < cw; c += 4) {
+                        float o[4];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (c + k < cw) lfq_project(acc_g, w.w_out, 1, d, c0 + c + k, d, xv[k]);
-                }
-            __syncthreads();
-        }
-    lfq_bwd_row(a, r0 + lane, acc_g, PARAMS, mine, code_l, gy_l, gy);
-    double *part = PARAMS ? a.partials + (size_t)blockIdx.x * lfq_partial_count(D, d) : nullptr;
-    for (int ch = 0; ch < nch; ++ch) {
-        const int c0 = ch * kL2Chunk, cw = D - c0 < kL2Chunk ? D - c0 : kL2Chunk;
-        if constexpr (PARAMS) {
-            if (a.g) l2n_copy<V, true>(const_cast<float *>(a.g), tx, r0, nr, D, c0, cw, lane);
-            __syncthreads();                                                  // (and code_l / gy_l are written)
-            lfq_reduce_w_out<kL2Stride, 1>(a, tiles, code_l, c0, cw, nrb, part);
-            __syncthreads();
-            l2n_copy<V, true>(const_cast<float *>(a.z), tx, r0, nr, D, c0, cw, lane);
-            __syncthreads();
-            lfq_reduce_w_in<kL2Stride, 1>(a, tiles, gy_l, c0, cw, nrb, part);
-            __syncthreads();
-        }
-        if (a.out) {
-            if (mine)
-                for (int c = 0; c < cw; c += 4) {
-                    float o[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = c + k < cw ? lfq_gz(w, c0 + c + k, D, d, gy) : 0.0f;
-                    l2n_store<4>(mx, (size_t)c, o);
-                }
-            __syncthreads();
-            l2n_copy<V, false>(a.out, tx, r0, nr, D, c0, cw, lane);
-            __syncthreads();
+                        for (int k = 0; k < 4; ++k) o[k] = c + k < cw ? proj_gz<kMaxD>(w, c0 + c + k, D, d, gy) : 0.0f;
+                        l2n_store<4>(p.mx, (size_t)c, o);
+                    }
+                __syncthreads();
+                l2n_copy<V, false>(a.out, p.tx, p.r0, p.nr, D, c0, cw, p.lane);
+                __syncthreads();
+            }
         }
     }
-}
-
-// the last launch: output o = the workgroups' partials of o in ascending workgroup order, rounded once.  A NULL gradient is skipped.
-__device__ __forceinline__ void lfq_param_finalize_body(const double *partials, long long nblocks, int D, int d, float *g_w_in,
-                                                        float *g_b_in, float *g_w_out, float *g_b_out) {
-    const int P = lfq_partial_count(D, d), o = blockIdx.x * kLfqBlockRows + threadIdx.x;
-    if (o >= P) return;
-    float *dst;
-    int at;
-    if (o < D * d) { dst = g_w_out; at = o; }
-    else if (o < D * d + D) { dst = g_b_out; at = o - D * d; }
-    else if (o < 2 * D * d + D) { dst = g_w_in; at = o - D * d - D; }
-    else { dst = g_b_in; at = o - 2 * D * d - D; }
-    if (!dst) return;
-    double s = 0.0;
-#pragma unroll 8
-    for (long long b = 0; b < nblocks; ++b) s = s + partials[(size_t)b * P + o];
-    dst[at] = (float)s;
-}
+};
 
 // the partition of the rows for the sums of the losses: whole blocks of 256 rows, at most max(16, min(1024, 2^20 / K)) partitions,
 // so that the (P, K) partials take at most 8 MiB.  A function of (N, K) alone.
 inline void lfq_partition(long long N, int K, long long &rows_per_part, int &P) {
     long long pmax = (1LL << 20) / K;
     pmax = pmax < 16 ? 16 : (pmax > 1024 ? 1024 : pmax);
-    const long long blocks = (N + kLfqBlockRows - 1) / kLfqBlockRows, bpp = (blocks + pmax - 1) / pmax;
-    rows_per_part = bpp * kLfqBlockRows;
+    const long long blocks = (N + kProjBlockRows - 1) / kProjBlockRows, bpp = (blocks + pmax - 1) / pmax;
+    rows_per_part = bpp * kProjBlockRows;
     P = (int)((blocks + bpp - 1) / bpp);
 }
 

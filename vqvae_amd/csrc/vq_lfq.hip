@@ -71,7 +71,8 @@
 // Workspace (vqvae_lfq_workspace_bytes(N, D, d), one size for both chains): y (N, d) fp32, then the larger of
 // {avg partials (P, K), scalar partials (P, 32)} and {L (K), e (N, d), parameter partials (ceil(N / 256), 2 D d + D + d)}, all fp64.
 //
-// Mappings (bodies in vq_lfq.h): the row kernels are vq_fsq.hip's -- NCHW maps one pixel per lane, row-major rows staged through
+// Mappings (the row kernels' bodies in vq_proj.h, their kernels and launches in vq_proj_kernels.h; the sign code, the loss kernels
+// and the backward bodies in vq_lfq.h): the row kernels are vq_fsq.hip's -- NCHW maps one pixel per lane, row-major rows staged through
 // vq_cosine.h's LDS tile, 64 rows per wave, 16-byte or element accesses.  avg partials: workgroup (partition, 1024 codes), 4 codes per
 // thread, rows staged 64 at a time as fp64 probabilities.  Entropy gradient: one wave per row, L in LDS up to K = 4096 (rows padded by
 // one double), read from memory above.  No scratch.
@@ -79,56 +80,9 @@
 
 #include "common.h"
 #include "vq_lfq.h"
+#include "vq_proj_kernels.h"
 
 namespace vqvae {
-
-template <bool DECODE, int WF>
-__global__ __launch_bounds__(kLfqBlockRows) void lfq_fwd_nchw_kernel(LfqArgs a) {
-    __shared__ float wl[WF];
-    lfq_fwd_nchw_body<DECODE>(a, wl);
-}
-
-template <bool DECODE, int V, int WF>
-__global__ __launch_bounds__(kLfqBlockRows) void lfq_fwd_rows_kernel(LfqArgs a) {
-    __shared__ __attribute__((aligned(16))) float tiles[kL2Waves * kL2TileFloats];
-    __shared__ float wl[WF];
-    lfq_fwd_rows_body<DECODE, V>(a, tiles, wl);
-}
-
-template <bool PARAMS, int WF>
-__global__ __launch_bounds__(kLfqBlockRows) void lfq_bwd_nchw_kernel(LfqArgs a) {
-    __shared__ float tile[PARAMS ? kL2Chunk * kLfqNchwStride : 1];
-    __shared__ float wl[WF];
-    __shared__ float code_l[PARAMS ? kLfqBlockRows * kLfqMaxBits : 1];
-    __shared__ double gy_l[PARAMS ? kLfqBlockRows * kLfqMaxBits : 1];
-    lfq_bwd_nchw_body<PARAMS>(a, tile, wl, code_l, gy_l);
-}
-
-template <bool PARAMS, int V, int WF>
-__global__ __launch_bounds__(kLfqBlockRows) void lfq_bwd_rows_kernel(LfqArgs a) {
-    __shared__ __attribute__((aligned(16))) float tiles[kL2Waves * kL2TileFloats];
-    __shared__ float wl[WF];
-    __shared__ float code_l[PARAMS ? kLfqBlockRows * kLfqMaxBits : 1];
-    __shared__ double gy_l[PARAMS ? kLfqBlockRows * kLfqMaxBits : 1];
-    lfq_bwd_rows_body<PARAMS, V>(a, tiles, wl, code_l, gy_l);
-}
-
-__global__ __launch_bounds__(kLfqBlockRows) void lfq_param_finalize_kernel(const double *partials, long long nblocks, int D, int d,
-                                                                           float *g_w_in, float *g_b_in, float *g_w_out, float *g_b_out) {
-    lfq_param_finalize_body(partials, nblocks, D, d, g_w_in, g_b_in, g_w_out, g_b_out);
-}
-
-__global__ __launch_bounds__(256) void lfq_perplexity_kernel(const int *hist, int K, long long N, float *perplexity) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int k = tid; k < K; k += 256) {
-        const double p = (double)hist[k] / (double)N;
-        s = s + p * log(p + 1e-10);
-    }
-    block_sum_f64(red, tid, s);
-    if (tid == 0) *perplexity = (float)exp(-red[0]);
-}
 
 __global__ __launch_bounds__(256) void lfq_avg_kernel(LfqLossArgs a) {
     __shared__ double pp[2 * kLfqChunkRows * kLfqMaxBits], hh[kLfqChunkRows * kLfqMaxBits], cc[kLfqChunkRows * kLfqMaxBits];
@@ -150,75 +104,14 @@ __global__ __launch_bounds__(kLfqGradThreads) void lfq_entgrad_kernel(LfqLossArg
     lfq_entgrad_body(a, l_lds, pb, A, B, u, v, T);
 }
 
-static bool lfq_small(const LfqArgs &a) { return a.D <= 64; }
-static unsigned lfq_grid(const LfqArgs &a) { return (unsigned)((a.N + kLfqBlockRows - 1) / kLfqBlockRows); }
-static bool lfq_wide(const LfqArgs &a, uintptr_t bits) { return (a.D & 3) == 0 && !(bits & 15); }
-
-template <bool DECODE>
-static void lfq_launch_fwd(const LfqArgs &a, bool rowmajor, hipStream_t st) {
-    const dim3 grid(lfq_grid(a)), block(kLfqBlockRows);
-    constexpr int S = kLfqWeightFloatsSmall, M = kLfqWeightFloatsMax;
-    if (!rowmajor) {
-        if (lfq_small(a)) hipLaunchKernelGGL((lfq_fwd_nchw_kernel<DECODE, S>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((lfq_fwd_nchw_kernel<DECODE, M>), grid, block, 0, st, a);
-        return;
-    }
-    const bool wide = lfq_wide(a, reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.out));
-    if (wide && lfq_small(a)) hipLaunchKernelGGL((lfq_fwd_rows_kernel<DECODE, 4, S>), grid, block, 0, st, a);
-    else if (wide) hipLaunchKernelGGL((lfq_fwd_rows_kernel<DECODE, 4, M>), grid, block, 0, st, a);
-    else if (lfq_small(a)) hipLaunchKernelGGL((lfq_fwd_rows_kernel<DECODE, 1, S>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((lfq_fwd_rows_kernel<DECODE, 1, M>), grid, block, 0, st, a);
-}
-
-template <bool PARAMS>
-static void lfq_launch_bwd(const LfqArgs &a, bool rowmajor, hipStream_t st) {
-    const dim3 grid(lfq_grid(a)), block(kLfqBlockRows);
-    constexpr int S = kLfqWeightFloatsSmall, M = kLfqWeightFloatsMax;
-    if (!rowmajor) {
-        if (lfq_small(a)) hipLaunchKernelGGL((lfq_bwd_nchw_kernel<PARAMS, S>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((lfq_bwd_nchw_kernel<PARAMS, M>), grid, block, 0, st, a);
-        return;
-    }
-    const bool wide = lfq_wide(a, reinterpret_cast<uintptr_t>(a.z) | reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.out));
-    if (wide && lfq_small(a)) hipLaunchKernelGGL((lfq_bwd_rows_kernel<PARAMS, 4, S>), grid, block, 0, st, a);
-    else if (wide) hipLaunchKernelGGL((lfq_bwd_rows_kernel<PARAMS, 4, M>), grid, block, 0, st, a);
-    else if (lfq_small(a)) hipLaunchKernelGGL((lfq_bwd_rows_kernel<PARAMS, 1, S>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((lfq_bwd_rows_kernel<PARAMS, 1, M>), grid, block, 0, st, a);
-}
-
-// ---- the entries' checks: the header's codes, before any launch ---------------------------------------------------------------------
-
-struct LfqSpan { const void *p; size_t bytes; };
-
-static bool lfq_overlap(const LfqSpan &x, const LfqSpan &y) {
-    if (!x.p || !y.p) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-    return a < b + y.bytes && b < a + x.bytes;
-}
-
+// the entries' first checks, in the header's order
 static int lfq_shape(int64_t B, int D, int H, int W, int d, LfqArgs &a) {
-    if (B < 1 || H < 1 || W < 1) return VQVAE_ERR_SHAPE;
+    const int rc = check_rows_shape(B, H, W, a.N, a.HW);
+    if (rc != VQVAE_OK) return rc;
     if (d < 1 || d > kLfqMaxBits || D < 1 || D > 256) return VQVAE_ERR_UNSUPPORTED;
-    if ((long long)H * W > INT32_MAX) return VQVAE_ERR_UNSUPPORTED;
-    const long long HW = (long long)H * W;
-    if (B > INT32_MAX / HW) return VQVAE_ERR_UNSUPPORTED;
-    a.HW = (int)HW;
-    a.N = B * HW;
     a.D = D;
     a.d = d;
     a.K = 1 << d;
-    return VQVAE_OK;
-}
-
-// every pointer aligned to `align` of its span (NULL passes), and no output on an input
-static int lfq_pointers(const LfqSpan *in, const int *in_align, int n_in, const LfqSpan *out, const int *out_align, int n_out) {
-    for (int i = 0; i < n_in; ++i)
-        if (reinterpret_cast<uintptr_t>(in[i].p) & (uintptr_t)(in_align[i] - 1)) return VQVAE_ERR_UNSUPPORTED;
-    for (int o = 0; o < n_out; ++o) {
-        if (reinterpret_cast<uintptr_t>(out[o].p) & (uintptr_t)(out_align[o] - 1)) return VQVAE_ERR_UNSUPPORTED;
-        for (int i = 0; i < n_in; ++i)
-            if (lfq_overlap(out[o], in[i])) return VQVAE_ERR_UNSUPPORTED;
-    }
     return VQVAE_OK;
 }
 
@@ -240,8 +133,7 @@ static LfqPlan lfq_plan(long long N, int D, int d) {
     p.logavg = p.off_a;
     p.e = p.logavg + (size_t)K * 8;
     p.partials = p.e + (size_t)N * d * 8;
-    const size_t nblocks = (size_t)((N + kLfqBlockRows - 1) / kLfqBlockRows);
-    const size_t bwd_end = p.partials + nblocks * (size_t)(2 * D * d + D + d) * 8;
+    const size_t bwd_end = p.partials + proj_partial_bytes(N, D, d);
     p.total = fwd_end > bwd_end ? fwd_end : bwd_end;
     return p;
 }
@@ -269,12 +161,10 @@ int vqvae_lfq_forward_f32(const float *z_e, const float *w_in, const float *b_in
     if (rc != VQVAE_OK) return rc;
     const LfqPlan plan = lfq_plan(a.N, D, d);
     const size_t nd = (size_t)a.N * D * 4, wd = (size_t)d * D * 4;
-    const LfqSpan in[] = {{z_e, nd}, {w_in, wd}, {b_in, (size_t)d * 4}, {w_out, wd}, {b_out, (size_t)D * 4}};
-    const int in_al[] = {4, 4, 4, 4, 4};
-    const LfqSpan out[] = {{z_q, nd}, {idx, (size_t)a.N * 8}, {hist, (size_t)a.K * 4}, {perplexity, 4}, {losses, 16},
-                           {avg, (size_t)a.K * 8}, {losses ? workspace : nullptr, plan.total}};
-    const int out_al[] = {4, 8, 4, 4, 4, 8, 8};
-    if ((rc = lfq_pointers(in, in_al, 5, out, out_al, 7)) != VQVAE_OK) return rc;
+    const Span in[] = {{z_e, nd, 4}, {w_in, wd, 4}, {b_in, (size_t)d * 4, 4}, {w_out, wd, 4}, {b_out, (size_t)D * 4, 4}};
+    const Span out[] = {{z_q, nd, 4}, {idx, (size_t)a.N * 8, 8}, {hist, (size_t)a.K * 4, 4}, {perplexity, 4, 4}, {losses, 16, 4},
+                        {avg, (size_t)a.K * 8, 8}, {losses ? workspace : nullptr, plan.total, 8}};
+    if ((rc = check_pointers(in, 5, out, 7)) != VQVAE_OK) return rc;
     if (losses && (!workspace || workspace_bytes < plan.total)) return VQVAE_ERR_WORKSPACE;
     char *ws = static_cast<char *>(workspace);
     a.z = z_e; a.w_in = w_in; a.b_in = b_in; a.w_out = z_q ? w_out : nullptr; a.b_out = z_q ? b_out : nullptr;
@@ -283,8 +173,8 @@ int vqvae_lfq_forward_f32(const float *z_e, const float *w_in, const float *b_in
     hipStream_t st = static_cast<hipStream_t>(stream);
     // hist = 0 by a kernel, not hipMemsetAsync: the chain is captured and replayed
     if (hist && (rc = fill_bytes_async(hist, 0, (size_t)a.K * 4, st)) != 0) return rc;
-    lfq_launch_fwd<false>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
-    if (perplexity) hipLaunchKernelGGL(lfq_perplexity_kernel, dim3(1), dim3(256), 0, st, hist, a.K, a.N, perplexity);
+    proj_launch_fwd<Lfq, false>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, st);
+    if (perplexity) hipLaunchKernelGGL(proj_perplexity_kernel<Lfq>, dim3(1), dim3(256), 0, st, hist, a.K, a.N, perplexity);
     if (losses) {
         LfqLossArgs l = {};
         l.y = a.y; l.N = a.N; l.rows_per_part = plan.rows_per_part; l.d = d; l.K = a.K; l.P = plan.P;
@@ -306,13 +196,11 @@ int vqvae_lfq_decode_indices_f32(const int64_t *idx, const float *w_out, const f
     LfqArgs a = {};
     int rc = lfq_shape(B, D, H, W, d, a);
     if (rc != VQVAE_OK) return rc;
-    const LfqSpan in[] = {{idx, (size_t)a.N * 8}, {w_out, (size_t)d * D * 4}, {b_out, (size_t)D * 4}};
-    const int in_al[] = {8, 4, 4};
-    const LfqSpan out[] = {{z_q, (size_t)a.N * D * 4}};
-    const int out_al[] = {4};
-    if ((rc = lfq_pointers(in, in_al, 3, out, out_al, 1)) != VQVAE_OK) return rc;
+    const Span in[] = {{idx, (size_t)a.N * 8, 8}, {w_out, (size_t)d * D * 4, 4}, {b_out, (size_t)D * 4, 4}};
+    const Span out[] = {{z_q, (size_t)a.N * D * 4, 4}};
+    if ((rc = check_pointers(in, 3, out, 1)) != VQVAE_OK) return rc;
     a.idx_in = reinterpret_cast<const long long *>(idx); a.w_out = w_out; a.b_out = b_out; a.out = z_q;
-    lfq_launch_fwd<true>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, static_cast<hipStream_t>(stream));
+    proj_launch_fwd<Lfq, true>(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, static_cast<hipStream_t>(stream));
     return (int)hipGetLastError();
 }
 
@@ -329,12 +217,11 @@ int vqvae_lfq_backward_f32(const float *z_e, const float *grad_zq, const float *
     if (rc != VQVAE_OK) return rc;
     const LfqPlan plan = lfq_plan(a.N, D, d);
     const size_t nd = (size_t)a.N * D * 4, wd = (size_t)d * D * 4;
-    const LfqSpan in[] = {{z_e, nd}, {grad_zq, nd}, {grad_loss, 4}, {avg, (size_t)a.K * 8}, {w_in, wd}, {b_in, (size_t)d * 4}, {w_out, wd}};
-    const int in_al[] = {4, 4, 4, 8, 4, 4, 4};
-    const LfqSpan out[] = {{grad_z, nd}, {grad_w_in, wd}, {grad_b_in, (size_t)d * 4}, {grad_w_out, wd}, {grad_b_out, (size_t)D * 4},
-                           {workspace, plan.total}};
-    const int out_al[] = {4, 4, 4, 4, 4, 8};
-    if ((rc = lfq_pointers(in, in_al, 7, out, out_al, 6)) != VQVAE_OK) return rc;
+    const Span in[] = {{z_e, nd, 4}, {grad_zq, nd, 4}, {grad_loss, 4, 4}, {avg, (size_t)a.K * 8, 8}, {w_in, wd, 4}, {b_in, (size_t)d * 4, 4},
+                       {w_out, wd, 4}};
+    const Span out[] = {{grad_z, nd, 4}, {grad_w_in, wd, 4}, {grad_b_in, (size_t)d * 4, 4}, {grad_w_out, wd, 4},
+                        {grad_b_out, (size_t)D * 4, 4}, {workspace, plan.total, 8}};
+    if ((rc = check_pointers(in, 7, out, 6)) != VQVAE_OK) return rc;
     if (!workspace || workspace_bytes < plan.total) return VQVAE_ERR_WORKSPACE;
     char *ws = static_cast<char *>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -342,7 +229,7 @@ int vqvae_lfq_backward_f32(const float *z_e, const float *grad_zq, const float *
     // 1: y of every row, as the forward computes it
     LfqArgs f = a;
     f.z = z_e; f.w_in = w_in; f.b_in = b_in; f.y = reinterpret_cast<float *>(ws);
-    lfq_launch_fwd<false>(f, rowmajor, st);
+    proj_launch_fwd<Lfq, false>(f, rowmajor, st);
     // 2: the loss's gradient with respect to y
     double *e = nullptr;
     if (avg) {
@@ -356,17 +243,10 @@ int vqvae_lfq_backward_f32(const float *z_e, const float *grad_zq, const float *
         else if (a.K <= kLfqLdsLogK) hipLaunchKernelGGL((lfq_entgrad_kernel<kLfqLogLdsDoubles>), dim3((unsigned)l.nwg), dim3(kLfqGradThreads), 0, st, l);
         else hipLaunchKernelGGL((lfq_entgrad_kernel<1>), dim3((unsigned)l.nwg), dim3(kLfqGradThreads), 0, st, l);
     }
-    // 3: the rows' gradients and the parameter gradients' partials
+    // 3: the rows' gradients, the parameter gradients' partials and their sums
     a.z = z_e; a.g = grad_zq; a.w_in = w_in; a.w_out = w_out; a.out = grad_z; a.y = f.y; a.e = e; a.gl = grad_loss;
     a.partials = params ? reinterpret_cast<double *>(ws + plan.partials) : nullptr;
-    if (params) lfq_launch_bwd<true>(a, rowmajor, st);
-    else lfq_launch_bwd<false>(a, rowmajor, st);
-    if (params) {
-        const int P = 2 * D * d + D + d;
-        hipLaunchKernelGGL(lfq_param_finalize_kernel, dim3((unsigned)((P + kLfqBlockRows - 1) / kLfqBlockRows)), dim3(kLfqBlockRows), 0,
-                           st, a.partials, (long long)((a.N + kLfqBlockRows - 1) / kLfqBlockRows), D, d, grad_w_in, grad_b_in,
-                           grad_w_out, grad_b_out);
-    }
+    proj_launch_bwd<Lfq>(a, rowmajor, grad_w_in, grad_b_in, grad_w_out, grad_b_out, st);
     return (int)hipGetLastError();
 }
 

@@ -119,36 +119,12 @@ void launch_linear_params(const LinParamArgs &a, bool rowmajor, float *grad_w, f
 
 // ---- the entries' checks: the header's codes, before any launch ---------------------------------------------------------------------
 
-struct LinSpan { const void *p; size_t bytes; int align; };
-
-static bool lin_overlap(const LinSpan &x, const LinSpan &y) {
-    if (!x.p || !y.p) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-    return a < b + y.bytes && b < a + x.bytes;
-}
-
-// every pointer aligned (NULL passes), and no output on an input
-static int lin_pointers(const LinSpan *in, int n_in, const LinSpan *out, int n_out) {
-    for (int i = 0; i < n_in; ++i)
-        if (reinterpret_cast<uintptr_t>(in[i].p) & (uintptr_t)(in[i].align - 1)) return VQVAE_ERR_UNSUPPORTED;
-    for (int o = 0; o < n_out; ++o) {
-        if (reinterpret_cast<uintptr_t>(out[o].p) & (uintptr_t)(out[o].align - 1)) return VQVAE_ERR_UNSUPPORTED;
-        for (int i = 0; i < n_in; ++i)
-            if (lin_overlap(out[o], in[i])) return VQVAE_ERR_UNSUPPORTED;
-    }
-    return VQVAE_OK;
-}
-
 // -> N and HW, or the header's code
 static int lin_shape(int64_t B, int Cin, int H, int W, int Cout, int flags, long long &N, int &HW) {
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return VQVAE_ERR_SHAPE;
     if (flags & ~VQVAE_VQ_ROWMAJOR) return VQVAE_ERR_UNSUPPORTED;
-    if (Cin > 256 || Cout > 256 || (long long)H * W > INT32_MAX) return VQVAE_ERR_UNSUPPORTED;
-    const long long hw = (long long)H * W;
-    if (B > INT32_MAX / hw) return VQVAE_ERR_UNSUPPORTED;
-    HW = (int)hw;
-    N = B * hw;
-    return VQVAE_OK;
+    if (Cin > 256 || Cout > 256) return VQVAE_ERR_UNSUPPORTED;
+    return check_rows_shape(B, H, W, N, HW);
 }
 
 static size_t lin_backward_ws(long long N, int Cin, int Cout) {
@@ -167,9 +143,9 @@ int vqvae_linear_rows_forward_f32(const float *x, const float *w, const float *b
     LinArgs a = {};
     int rc = lin_shape(B, Cin, H, W, Cout, flags, a.N, a.HW);
     if (rc != VQVAE_OK) return rc;
-    const LinSpan in[] = {{x, (size_t)a.N * Cin * 4, 4}, {w, (size_t)Cout * Cin * 4, 4}, {b, (size_t)Cout * 4, 4}};
-    const LinSpan out[] = {{y, (size_t)a.N * Cout * 4, 4}};
-    if ((rc = lin_pointers(in, 3, out, 1)) != VQVAE_OK) return rc;
+    const Span in[] = {{x, (size_t)a.N * Cin * 4, 4}, {w, (size_t)Cout * Cin * 4, 4}, {b, (size_t)Cout * 4, 4}};
+    const Span out[] = {{y, (size_t)a.N * Cout * 4, 4}};
+    if ((rc = check_pointers(in, 3, out, 1)) != VQVAE_OK) return rc;
     a.x = x; a.w = w; a.b = b; a.out = y;
     a.NI = Cin; a.NO = Cout; a.ws_o = Cin; a.ws_i = 1;
     launch_linear_rows(a, (flags & VQVAE_VQ_ROWMAJOR) != 0, static_cast<hipStream_t>(stream));
@@ -191,13 +167,11 @@ int vqvae_linear_rows_backward_f32(const float *x, const float *grad_y, const fl
     int rc = lin_shape(B, Cin, H, W, Cout, flags, N, HW);
     if (rc != VQVAE_OK) return rc;
     const size_t need = params ? lin_backward_ws(N, Cin, Cout) : 0;
-    const LinSpan in[] = {{x, (size_t)N * Cin * 4, 4}, {grad_y, (size_t)N * Cout * 4, 4}, {w, (size_t)Cout * Cin * 4, 4}};
-    const LinSpan out[] = {{grad_x, (size_t)N * Cin * 4, 4}, {grad_w, (size_t)Cout * Cin * 4, 4}, {grad_b, (size_t)Cout * 4, 4},
+    const Span in[] = {{x, (size_t)N * Cin * 4, 4}, {grad_y, (size_t)N * Cout * 4, 4}, {w, (size_t)Cout * Cin * 4, 4}};
+    const Span out[] = {{grad_x, (size_t)N * Cin * 4, 4}, {grad_w, (size_t)Cout * Cin * 4, 4}, {grad_b, (size_t)Cout * 4, 4},
                            {params ? workspace : nullptr, need, 8}};
-    if ((rc = lin_pointers(in, 3, out, 4)) != VQVAE_OK) return rc;
-    for (int i = 0; i < 4; ++i)                                               // nor one output on another
-        for (int k = i + 1; k < 4; ++k)
-            if (lin_overlap(out[i], out[k])) return VQVAE_ERR_UNSUPPORTED;
+    if ((rc = check_pointers(in, 3, out, 4)) != VQVAE_OK) return rc;
+    if ((rc = check_outputs_apart(out, 4)) != VQVAE_OK) return rc;
     if (params && (!workspace || workspace_bytes < need)) return VQVAE_ERR_WORKSPACE;
     const bool rowmajor = (flags & VQVAE_VQ_ROWMAJOR) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);

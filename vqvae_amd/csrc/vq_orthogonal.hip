@@ -75,26 +75,10 @@ static void orth_launch_main(const OrthArgs &a, hipStream_t st) {
     else hipLaunchKernelGGL((orth_main_kernel<DT, false>), grid, block, 0, st, a);
 }
 
-struct OrthSpan { const void *p; size_t bytes; int align; };
-
-static bool orth_overlap(const OrthSpan &x, const OrthSpan &y) {
-    if (!x.p || !y.p) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-    return a < b + y.bytes && b < a + x.bytes;
-}
-
 // every pointer aligned (NULL passes), no output on an input, nor on another output
-static int orth_pointers(const OrthSpan *in, int n_in, const OrthSpan *out, int n_out) {
-    for (int i = 0; i < n_in; ++i)
-        if (reinterpret_cast<uintptr_t>(in[i].p) & (uintptr_t)(in[i].align - 1)) return VQVAE_ERR_UNSUPPORTED;
-    for (int o = 0; o < n_out; ++o) {
-        if (reinterpret_cast<uintptr_t>(out[o].p) & (uintptr_t)(out[o].align - 1)) return VQVAE_ERR_UNSUPPORTED;
-        for (int i = 0; i < n_in; ++i)
-            if (orth_overlap(out[o], in[i])) return VQVAE_ERR_UNSUPPORTED;
-        for (int k = o + 1; k < n_out; ++k)
-            if (orth_overlap(out[o], out[k])) return VQVAE_ERR_UNSUPPORTED;
-    }
-    return VQVAE_OK;
+static int orth_pointers(const Span *in, int n_in, const Span *out, int n_out) {
+    const int rc = check_pointers(in, n_in, out, n_out);
+    return rc != VQVAE_OK ? rc : check_outputs_apart(out, n_out);
 }
 
 static int orth_shape(int K, int D) {
@@ -122,8 +106,8 @@ int vqvae_vq_orthogonal_forward_f32(const float *rows, const int32_t *hist, cons
     if (rc != VQVAE_OK) return rc;
     if (flags) return VQVAE_ERR_UNSUPPORTED;
     const size_t need = (size_t)K * sizeof(double);
-    const OrthSpan in[] = {{rows, (size_t)K * D * 4, 4}, {hist, (size_t)K * 4, 4}, {uniforms, (size_t)K * 4, 4}};
-    const OrthSpan out[] = {{loss, 4, 4}, {count, 4, 4}, {selected, (size_t)K * 4, 4}, {saved, (size_t)K * D * 8, 8},
+    const Span in[] = {{rows, (size_t)K * D * 4, 4}, {hist, (size_t)K * 4, 4}, {uniforms, (size_t)K * 4, 4}};
+    const Span out[] = {{loss, 4, 4}, {count, 4, 4}, {selected, (size_t)K * 4, 4}, {saved, (size_t)K * D * 8, 8},
                             {workspace, need, 8}};
     if ((rc = orth_pointers(in, 3, out, 5)) != VQVAE_OK) return rc;
     if (!workspace || workspace_bytes < need) return VQVAE_ERR_WORKSPACE;
@@ -144,8 +128,8 @@ int vqvae_vq_orthogonal_backward_f32(const double *saved, const int32_t *selecte
     if (!saved || !selected || !count || !grad_rows) return VQVAE_ERR_NULL;
     int rc = orth_shape(K, D);
     if (rc != VQVAE_OK) return rc;
-    const OrthSpan in[] = {{saved, (size_t)K * D * 8, 8}, {selected, (size_t)K * 4, 4}, {count, 4, 4}, {grad_loss, 4, 4}};
-    const OrthSpan out[] = {{grad_rows, (size_t)K * D * 4, 4}};
+    const Span in[] = {{saved, (size_t)K * D * 8, 8}, {selected, (size_t)K * 4, 4}, {count, 4, 4}, {grad_loss, 4, 4}};
+    const Span out[] = {{grad_rows, (size_t)K * D * 4, 4}};
     if ((rc = orth_pointers(in, 4, out, 1)) != VQVAE_OK) return rc;
     hipLaunchKernelGGL(orth_backward_kernel, dim3(grid_of((long long)K * D, 2048)), dim3(kOrthThreads), 0, static_cast<hipStream_t>(stream),
                        saved, selected, count, grad_loss, K, D, grad_rows);
