@@ -461,6 +461,34 @@ VQVAE_API int vqvae_vq_orthogonal_forward_f32(const float *rows, const int32_t *
 VQVAE_API int vqvae_vq_orthogonal_backward_f32(const double *saved, const int32_t *selected, const int32_t *count,
                                                const float *grad_loss, int K, int D, float *grad_rows, vqvae_stream_t stream);
 
+/* The code-entropy loss of a learned codebook and its gradients (csrc/vq_entropy.hip; its header is the numeric contract): the
+ * entropy penalty of MaskGIT's VQGAN tokenizer, MAGVIT and LlamaGen (`entropy_loss_ratio`; `codebook_diversity_loss_weight` in
+ * vector-quantize-pytorch), streamed: no (N, K) array, O(N + K D) memory.  Rows and layouts are vqvae_vq_forward_f32's (N = B H W
+ * rows z_n; (B, D, H, W) maps, or (N, D) rows with VQVAE_VQ_ROWMAJOR, the only flag); codebook e_k (K, D).  s = inv_temperature.
+ * Everything in fp64 from the fp32 inputs:
+ *     l_nk = -s ((zz_n + ee_k) - 2 dot_nk);  p_nk = softmax_k(l_nk), shifted by the row maximum
+ *     H_n = -sum_k p_nk log p_nk;  P = (1 / N) sum_n H_n;  avg_k = (1 / N) sum_n p_nk;  H = -sum_k avg_k log avg_k  (0 log 0 = 0)
+ *     losses = float(P - gamma H, P, H);  avg (K) fp64;  rowstat (N, 2) fp64: the row's log-sum-exp and H_n, or NULL
+ *   backward, g = *grad_loss (NULL = 1), L_k = log avg_k (0 where avg_k = 0), M_n = sum_j p_nj L_j; avg and rowstat are the forward's:
+ *     a_nk = (g / N) p_nk [-(log p_nk + H_n) + gamma (L_k - M_n)]
+ *     grad_z_n = float(-2 s sum_k a_nk (z_n - e_k));  grad_codebook_k = float(2 s sum_n a_nk (z_n - e_k));  either may be NULL, not both
+ *   exp and log on the device are not correctly rounded: the results agree with a restatement within a derived bound, not by bits.
+ *   The order of every sum is a function of (N, K, D) alone; no floating-point atomics, no host sync, no allocation, no memset, one
+ *   chain of launches on `stream`: capturable; the same bits in both layouts, at every pointer alignment, in every run and in a graph
+ *   replay.  The losses and gradients of a batch that holds a non-finite value are unspecified (nothing is read out of bounds).
+ *   Envelope: 1 <= K <= 16384, 1 <= D <= 256, N < 2^31, s > 0 and finite, gamma finite (vqvae_vq_entropy_workspace_bytes: 0 outside
+ *   it; one size for both calls).  VQVAE_ERR_UNSUPPORTED outside it, for another flag, for a pointer that is not 4-byte aligned
+ *   (avg, rowstat, workspace: 8-byte) and for an output that overlaps an input or another output; VQVAE_ERR_WORKSPACE for a missing
+ *   or short workspace.                                                                                                          */
+VQVAE_API size_t vqvae_vq_entropy_workspace_bytes(int64_t N, int K, int D);
+VQVAE_API int vqvae_vq_entropy_forward_f32(const float *z_e, const float *codebook, int64_t B, int D, int H, int W, int K,
+                                           double inv_temperature, double gamma, int flags, float *losses, double *avg,
+                                           double *rowstat, void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API int vqvae_vq_entropy_backward_f32(const float *z_e, const float *codebook, const double *avg, const double *rowstat,
+                                            const float *grad_loss, int64_t B, int D, int H, int W, int K, double inv_temperature,
+                                            double gamma, int flags, float *grad_z, float *grad_codebook, void *workspace,
+                                            size_t workspace_bytes, vqvae_stream_t stream);
+
 /* Lookup-free quantization (csrc/vq_lfq.hip; its header is the numeric contract): the codebook is {-1, +1}^d, K = 2^d (MAGVIT-v2,
  * arXiv 2310.05737 section 3.1; vector-quantize-pytorch's LFQ).  A row is projected to d channels (w_in (d, D), b_in (d)), every
  * channel keeps its sign (c_j = +1 where y_j > 0, else -1), and the signs are projected back (w_out (D, d), b_out (D)); the

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Training-step time (forward + loss + backward, no optimizer) of main.py:74-78: convs on the HIP kernels vs
 torch's conv autograd (MIOpen), the quantizer on the HIP forward/backward either way.
-    train_bench.py [B] [backends] [steps] [adam|hipadam|-] [rotation] [cosine] [fsq] [groups] [lfq] [factorized] [orth]
+    train_bench.py [B] [backends] [steps] [adam|hipadam|-] [rotation] [cosine] [fsq] [groups] [lfq] [factorized] [orth] [entropy]
+                                                     entropy: VQVAE(..., entropy_weight=0.1), the code-entropy loss of the codebook joins the training
+                                                     loss (csrc/vq_entropy.hip); absent: the model as it always was
                                                      orth: VQVAE(..., orthogonal_reg_weight=10.0), the orthogonal regularization loss of
                                                      the codebook joins the training loss (csrc/vq_orthogonal.hip); absent: the model as it always was
                                                      factorized: VQVAE(..., codebook_dim=8), the codebook searched in 8 channels between
@@ -35,10 +37,11 @@ groups = "groups" in sys.argv[4:]
 lfq = "lfq" in sys.argv[4:]
 factorized = "factorized" in sys.argv[4:]
 orth = "orth" in sys.argv[4:]
+entropy = "entropy" in sys.argv[4:]
 opts = {**({"rotation_trick": True} if rotation else {}), **({"cosine_sim": True} if cosine else {}),
         **({"fsq_levels": (8, 5, 5, 5)} if fsq else {}), **({"codebook_groups": 4} if groups else {}),
         **({"lookup_free": True} if lfq else {}), **({"codebook_dim": 8} if factorized else {}),
-        **({"orthogonal_reg_weight": 10.0} if orth else {})}
+        **({"orthogonal_reg_weight": 10.0} if orth else {}), **({"entropy_weight": 0.1} if entropy else {})}
 model = VQVAE(128, 32, 2, 1000 if fsq else (1024 if lfq else 512), 64, 0.25, **opts).to(dev).train()
 x = torch.randn(B, 3, 32, 32, device=dev)
 backends = sys.argv[2].split(",") if len(sys.argv) > 2 else ["hip", "torch"]
@@ -69,5 +72,5 @@ for backend in backends:
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / n
-    print(f"backend={backend:5s} B={B}{' +' + which_adam if with_adam else ''}{' rotation_trick' if rotation else ''}{' cosine_sim' if cosine else ''}{' fsq_levels=(8,5,5,5)' if fsq else ''}{' codebook_groups=4' if groups else ''}{' lookup_free' if lfq else ''}{' codebook_dim=8' if factorized else ''}{' orthogonal_reg_weight=10' if orth else ''}: {dt * 1e3:8.2f} ms per forward+backward   {B / dt / 1e3:8.1f} k img/s", flush=True)
+    print(f"backend={backend:5s} B={B}{' +' + which_adam if with_adam else ''}{' rotation_trick' if rotation else ''}{' cosine_sim' if cosine else ''}{' fsq_levels=(8,5,5,5)' if fsq else ''}{' codebook_groups=4' if groups else ''}{' lookup_free' if lfq else ''}{' codebook_dim=8' if factorized else ''}{' orthogonal_reg_weight=10' if orth else ''}{' entropy_weight=0.1' if entropy else ''}: {dt * 1e3:8.2f} ms per forward+backward   {B / dt / 1e3:8.1f} k img/s", flush=True)
 conv.set_conv_backend("hip")

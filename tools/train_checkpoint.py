@@ -16,6 +16,8 @@ vqvae_amd.optim.Adam (csrc/optim.hip: a written-down operation order, so the run
                                      [--codebook_dim 8]                             (off by default: factorized codes)
                                      [--orthogonal_reg_weight W [--orthogonal_reg_active_codes_only] [--orthogonal_reg_max_codes M]]
                                                                                     (off by default: orthogonal regularization of the codebook)
+                                     [--entropy_weight W [--entropy_diversity_gamma G --entropy_inv_temperature S]]
+                                                                                    (off by default: the code-entropy loss of the codebook)
                                      [--lookup_free --n_embeddings 1024 [--lfq_entropy_weight 0.1 --lfq_diversity_gamma 1 --lfq_inv_temperature 100]]
                                                                                     (off by default: lookup-free quantization)
                                      [--codebook_groups G]                          (off by default: grouped quantization, G codebooks)
@@ -89,8 +91,15 @@ def parse(argv=None):
     p.add_argument("--orthogonal_reg_weight", type=float, default=argparse.SUPPRESS, metavar="W")
     p.add_argument("--orthogonal_reg_active_codes_only", action="store_true", default=argparse.SUPPRESS)
     p.add_argument("--orthogonal_reg_max_codes", type=int, default=argparse.SUPPRESS, metavar="M")
+    # opt-in code-entropy loss of the learned codebook (entropy_weight=W; csrc/vq_entropy.hip); absent unless given
+    p.add_argument("--entropy_weight", type=float, default=argparse.SUPPRESS, metavar="W")
+    p.add_argument("--entropy_diversity_gamma", type=float, default=argparse.SUPPRESS, metavar="G")
+    p.add_argument("--entropy_inv_temperature", type=float, default=argparse.SUPPRESS, metavar="S")
     args = p.parse_args(argv)
     ema_kw = {}
+    for name in ("entropy_weight", "entropy_diversity_gamma", "entropy_inv_temperature"):
+        if hasattr(args, name):
+            ema_kw[name] = getattr(args, name)
     for name in ("orthogonal_reg_weight", "orthogonal_reg_active_codes_only", "orthogonal_reg_max_codes"):
         if hasattr(args, name):
             ema_kw[name] = getattr(args, name)

@@ -104,6 +104,11 @@ SIGNATURES = {
     "vqvae_vq_orthogonal_workspace_bytes": (_sz, [_i32, _i32]),
     "vqvae_vq_orthogonal_forward_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vqvae_vq_orthogonal_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "vqvae_vq_entropy_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vqvae_vq_entropy_forward_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp,
+                                            _sz, _vp]),
+    "vqvae_vq_entropy_backward_f32": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp,
+                                             _sz, _vp]),
     "vqvae_lfq_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vqvae_lfq_forward_f32": (_i32, [_vp] * 5 + [_i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32] + [_vp] * 7 + [_sz, _vp]),
     "vqvae_lfq_decode_indices_f32": (_i32, [_vp] * 3 + [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -841,3 +841,78 @@ def vq_orthogonal_backward(saved: torch.Tensor, selected: torch.Tensor, count: t
             saved.data_ptr(), selected.data_ptr(), count.data_ptr(), grad_loss.data_ptr() if grad_loss is not None else None, K, D,
             grad_rows.data_ptr(), _stream_ptr(saved)))
     return grad_rows
+
+
+# ---- the code-entropy loss of a learned codebook (csrc/vq_entropy.hip) --------------------------------------------------------------
+
+def _vq_entropy_dims(z, codebook, rowmajor):
+    _check_dev("z", z)
+    _check_dev("codebook", codebook)
+    if z.dim() != 4:
+        raise ValueError("z must be 4-D: (B, D, H, W), or (B, H, W, D) when rowmajor")
+    B, H, W, D = z.shape if rowmajor else (z.shape[0], z.shape[2], z.shape[3], z.shape[1])
+    if codebook.dim() != 2 or codebook.shape[1] != D:
+        raise ValueError(f"codebook must be (K, D = {D}), got {tuple(codebook.shape)}")
+    return B, H, W, D, codebook.shape[0]
+
+
+def vq_entropy_workspace(N: int, K: int, D: int, device) -> torch.Tensor:
+    """workspace of vq_entropy_forward and vq_entropy_backward (vqvae_vq_entropy_workspace_bytes: one size for both)"""
+    n = _lib.load().vqvae_vq_entropy_workspace_bytes(N, K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"vq_entropy: N={N}, K={K}, D={D} not supported (1 <= K <= 16384, 1 <= D <= 256, 1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_entropy_forward(z: torch.Tensor, codebook: torch.Tensor, *, inv_temperature: float, gamma: float, rowmajor: bool = False,
+                       want_saved: bool = True, workspace: torch.Tensor | None = None):
+    """The code-entropy loss of the rows of z against a (K, D) codebook (vqvae_vq_entropy_forward_f32): with p = softmax_k of
+    -inv_temperature * |z_n - e_k|^2, P the mean row entropy and H the entropy of the batch's mean p, term = P - gamma * H.  z:
+    (B, D, H, W), or (B, H, W, D) when rowmajor.  -> (losses (3,) fp32 = (term, P, H), avg (K,) fp64, rowstat (N, 2) fp64 = the rows'
+    log-sum-exp and entropy for vq_entropy_backward, or None without want_saved).  No (N, K) array, no host sync.  The numeric
+    contract is the header of csrc/vq_entropy.hip."""
+    B, H, W, D, K = _vq_entropy_dims(z, codebook, rowmajor)
+    z, codebook = z.contiguous(), codebook.contiguous()
+    dev, N = z.device, B * H * W
+    with torch.cuda.device(dev):
+        ws = workspace if workspace is not None else vq_entropy_workspace(N, K, D, dev)
+        losses = torch.empty((3,), dtype=torch.float32, device=dev)
+        avg = torch.empty((K,), dtype=torch.float64, device=dev)
+        rowstat = torch.empty((N, 2), dtype=torch.float64, device=dev) if want_saved else None
+        _lib.check(_lib.load().vqvae_vq_entropy_forward_f32(
+            z.data_ptr(), codebook.data_ptr(), B, D, H, W, K, float(inv_temperature), float(gamma), VQ_ROWMAJOR if rowmajor else 0,
+            losses.data_ptr(), avg.data_ptr(), rowstat.data_ptr() if want_saved else None, ws.data_ptr(), ws.numel(), _stream_ptr(z)))
+    return losses, avg, rowstat
+
+
+def vq_entropy_backward(z: torch.Tensor, codebook: torch.Tensor, avg: torch.Tensor, rowstat: torch.Tensor,
+                        grad_loss: torch.Tensor | None = None, *, inv_temperature: float, gamma: float, rowmajor: bool = False,
+                        want=(True, True), workspace: torch.Tensor | None = None):
+    """The gradients of vq_entropy_forward's term (vqvae_vq_entropy_backward_f32) from its avg and rowstat: grad_loss (a device
+    scalar; None: 1) times d term / d z (like z) and d term / d codebook (K, D).  want = (grad_z, grad_codebook): at least one;
+    -> (grad_z or None, grad_codebook or None)."""
+    B, H, W, D, K = _vq_entropy_dims(z, codebook, rowmajor)
+    _check_dev("avg", avg, torch.float64)
+    _check_dev("rowstat", rowstat, torch.float64)
+    N = B * H * W
+    if avg.shape != (K,) or rowstat.shape != (N, 2):
+        raise ValueError("avg must be (K,) and rowstat (N, 2): vq_entropy_forward's outputs")
+    want_z, want_e = bool(want[0]), bool(want[1])
+    if not (want_z or want_e):
+        raise ValueError("want: at least one of (grad_z, grad_codebook)")
+    if grad_loss is not None:
+        _check_dev("grad_loss", grad_loss)
+        if grad_loss.numel() != 1:
+            raise ValueError("grad_loss must be a scalar")
+        grad_loss = grad_loss.contiguous()
+    z, codebook, avg, rowstat = z.contiguous(), codebook.contiguous(), avg.contiguous(), rowstat.contiguous()
+    dev = z.device
+    with torch.cuda.device(dev):
+        ws = workspace if workspace is not None else vq_entropy_workspace(N, K, D, dev)
+        gz = torch.empty_like(z) if want_z else None
+        ge = torch.empty_like(codebook) if want_e else None
+        _lib.check(_lib.load().vqvae_vq_entropy_backward_f32(
+            z.data_ptr(), codebook.data_ptr(), avg.data_ptr(), rowstat.data_ptr(), grad_loss.data_ptr() if grad_loss is not None else None,
+            B, D, H, W, K, float(inv_temperature), float(gamma), VQ_ROWMAJOR if rowmajor else 0, gz.data_ptr() if want_z else None,
+            ge.data_ptr() if want_e else None, ws.data_ptr(), ws.numel(), _stream_ptr(z)))
+    return gz, ge

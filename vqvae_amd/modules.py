@@ -132,11 +132,19 @@ class VectorQuantizer(nn.Module):
     LAZY_MIN_ENCODINGS = True          # forward()'s fourth output: LazyOneHot (the (N, K) one-hot on first use) or the tensor itself
 
     def __init__(self, n_e, e_dim, beta, *, rotation_trick=False, cosine_sim=False, orthogonal_reg_weight=0.0,
-                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None):
+                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None, entropy_weight=0.0,
+                 entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0):
         super().__init__()
         self.n_e = n_e
         self.e_dim = e_dim
         self.beta = beta
+        # opt-in: the code-entropy loss (MaskGIT's VQGAN tokenizer, MAGVIT, LlamaGen's `entropy_loss_ratio`; csrc/vq_entropy.hip) joins
+        # the training loss: weight * (P - gamma * H) of the rows' softmax over the codes at -inv_temperature * squared distance.  On
+        # unit rows d = 2 - 2 cos, so inv_temperature = 50 with cosine_sim is MaskGIT's temperature of 0.01.  Plain attributes: no
+        # parameter, no buffer, no state_dict key; at weight 0 nothing is launched.
+        self.entropy_weight, self.entropy_diversity_gamma, self.entropy_inv_temperature = self._check_entropy(
+            entropy_weight, entropy_diversity_gamma, entropy_inv_temperature)
+        self.last_entropy_losses = None        # the latest (term, P, H), a device 3-vector
         # opt-in: the orthogonal regularization loss of the codebook (arXiv 2112.00384 section 3.2; csrc/vq_orthogonal.hip) joins
         # the training loss.  Plain attributes: no parameter, no buffer, no state_dict key; at weight 0 nothing is launched or drawn.
         self.orthogonal_reg_weight, self.orthogonal_reg_max_codes = self._check_orthogonal(orthogonal_reg_weight,
@@ -163,6 +171,38 @@ class VectorQuantizer(nn.Module):
             if isinstance(max_codes, bool) or not isinstance(max_codes, int) or max_codes < 1:
                 raise ValueError(f"orthogonal_reg_max_codes must be an int >= 1 or None, got {max_codes!r}")
         return weight, max_codes
+
+    @staticmethod
+    def _check_entropy(weight, gamma, inv_temperature):
+        weight, gamma, inv_temperature = float(weight), float(gamma), float(inv_temperature)
+        if not weight >= 0.0 or weight == float("inf"):
+            raise ValueError(f"entropy_weight must be >= 0 and finite, got {weight!r}")
+        if not (inv_temperature > 0.0 and inv_temperature < float("inf")):
+            raise ValueError(f"entropy_inv_temperature must be > 0 and finite, got {inv_temperature!r}")
+        if gamma != gamma or abs(gamma) == float("inf"):
+            raise ValueError(f"entropy_diversity_gamma must be finite, got {gamma!r}")
+        return weight, gamma, inv_temperature
+
+    def _with_entropy(self, out, z, codes, rowmajor):
+        """quantize's outputs with entropy_weight * the code-entropy term added to the loss: only with a weight > 0, in training
+        mode, while a graph is recorded.  z, codes: the very operands the search ran on -- the unit rows and unit codes with
+        cosine_sim, the projected rows and the low-dimensional codebook with codebook_dim.  A codebook that takes no gradient (EMA)
+        is passed without one: only z gets a gradient.  (term, P, H) is kept in last_entropy_losses."""
+        if not (self.entropy_weight > 0.0 and self.training and torch.is_grad_enabled() and (z.requires_grad or codes.requires_grad)):
+            return out
+        from .training import CodeEntropyLoss
+        if not codes.requires_grad and codes.data_ptr() == self.embedding.weight.data_ptr():
+            codes = codes.detach().clone()     # an EMA update writes embedding.weight in place before the backward reads the codes
+        N = out[3].numel()
+        table = _cache.side(self).setdefault("entropy_ws", {})
+        skey = (str(z.device), torch.cuda.current_stream(z.device).cuda_stream, N)
+        ws = _cache.lru_get(table, skey)
+        if ws is None:
+            ws = F_hip.vq_entropy_workspace(N, self.n_e, self.e_dim, z.device)
+            _cache.lru_put(table, skey, ws, 4)
+        term = CodeEntropyLoss.apply(z, codes, self.entropy_inv_temperature, self.entropy_diversity_gamma, rowmajor, ws)
+        self.last_entropy_losses = CodeEntropyLoss.last_losses
+        return (out[0] + self.entropy_weight * term,) + tuple(out[1:])
 
     def _with_orthogonal(self, out, codes):
         """quantize's outputs with weight * the orthogonal regularization loss of the l2-normalised codebook added to the loss:
@@ -250,7 +290,7 @@ class VectorQuantizer(nn.Module):
             out = F_hip.vq_forward(z, w.detach(), self.beta, rowmajor=rowmajor, workspace=ws,
                                    prepared=prepared, want_zq=want_zq)
         slot[1] = key
-        return self._with_orthogonal(out, w)
+        return self._with_entropy(self._with_orthogonal(out, w), z, w, rowmajor)
 
     def _apply(self, fn, *args, **kwargs):
         self.invalidate()
@@ -292,8 +332,9 @@ class VectorQuantizerEMA(VectorQuantizer):
     from its own shard; the statistics are not merged across ranks."""
 
     def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, rotation_trick=False,
-                 cosine_sim=False):
-        super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+                 cosine_sim=False, entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0):
+        super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim, entropy_weight=entropy_weight,
+                         entropy_diversity_gamma=entropy_diversity_gamma, entropy_inv_temperature=entropy_inv_temperature)
         self.decay = float(decay)
         self.eps = float(eps)
         self.restart_threshold = None if restart_threshold is None else float(restart_threshold)
@@ -349,6 +390,7 @@ class VectorQuantizerEMA(VectorQuantizer):
                                                                prepared=prepared, want_zq=want_zq)
             out = (mse * self.beta, z_q, perplexity, idx, hist)
         slot[1] = key
+        out = self._with_entropy(out, z, w.detach(), rowmajor)     # against the codebook as it was on entry; only z takes a gradient
         if self.training:
             self._ema_update(z.detach(), out[3], rowmajor)
         return out
@@ -368,12 +410,14 @@ class FactorizedVectorQuantizer(VectorQuantizer):
     _INNER = VectorQuantizer                  # the class whose quantize / init_codebook_ run on the projected rows
 
     def __init__(self, n_e, dim, codebook_dim, beta, *, rotation_trick=False, cosine_sim=False, orthogonal_reg_weight=0.0,
-                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None):
+                 orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, generator=None, entropy_weight=0.0,
+                 entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0):
         dim, codebook_dim = self._check_dims(dim, codebook_dim)
         super().__init__(n_e, codebook_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim,
                          orthogonal_reg_weight=orthogonal_reg_weight,
                          orthogonal_reg_active_codes_only=orthogonal_reg_active_codes_only,
-                         orthogonal_reg_max_codes=orthogonal_reg_max_codes, generator=generator)
+                         orthogonal_reg_max_codes=orthogonal_reg_max_codes, generator=generator, entropy_weight=entropy_weight,
+                         entropy_diversity_gamma=entropy_diversity_gamma, entropy_inv_temperature=entropy_inv_temperature)
         self._init_projections(dim, codebook_dim)
 
     @staticmethod
@@ -450,10 +494,13 @@ class FactorizedVectorQuantizerEMA(FactorizedVectorQuantizer, VectorQuantizerEMA
     _INNER = VectorQuantizerEMA
 
     def __init__(self, n_e, dim, codebook_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *,
-                 rotation_trick=False, cosine_sim=False):
+                 rotation_trick=False, cosine_sim=False, entropy_weight=0.0, entropy_diversity_gamma=1.0,
+                 entropy_inv_temperature=100.0):
         dim, codebook_dim = self._check_dims(dim, codebook_dim)
         VectorQuantizerEMA.__init__(self, n_e, codebook_dim, beta, decay, eps, restart_threshold, generator,
-                                    rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+                                    rotation_trick=rotation_trick, cosine_sim=cosine_sim, entropy_weight=entropy_weight,
+                                    entropy_diversity_gamma=entropy_diversity_gamma,
+                                    entropy_inv_temperature=entropy_inv_temperature)
         self._init_projections(dim, codebook_dim)
 
 
@@ -955,8 +1002,22 @@ class VQVAE(nn.Module):
                  save_img_embedding_map=False, *, ema_decay=None, ema_eps=1e-5, restart_threshold=None, n_quantizers=1,
                  shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1,
                  lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0,
-                 orthogonal_reg_weight=0.0, orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None, codebook_dim=None):
+                 orthogonal_reg_weight=0.0, orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None,
+                 entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0, codebook_dim=None):
         super().__init__()
+        # entropy_weight > 0: the code-entropy loss of the learned codebook (csrc/vq_entropy.hip) joins the training loss of the
+        # one-stage quantizers -- plain, EMA (only z takes its gradient), cosine_sim (on the unit rows: entropy_inv_temperature = 50
+        # is MaskGIT's temperature of 0.01), rotation_trick, codebook_dim (on the projected rows)
+        entropy_weight, entropy_diversity_gamma, entropy_inv_temperature = VectorQuantizer._check_entropy(
+            entropy_weight, entropy_diversity_gamma, entropy_inv_temperature)
+        if entropy_weight > 0.0:
+            for name, on in (("n_quantizers > 1", n_quantizers != 1), ("shared_codebook", shared_codebook),
+                             ("codebook_groups > 1", codebook_groups != 1), ("fsq_levels", fsq_levels is not None),
+                             ("lookup_free (which has its own entropy loss: lfq_entropy_weight)", lookup_free)):
+                if on:
+                    raise ValueError(f"entropy_weight > 0 does not combine with {name}")
+        ent = dict(entropy_weight=entropy_weight, entropy_diversity_gamma=entropy_diversity_gamma,
+                   entropy_inv_temperature=entropy_inv_temperature)
         orthogonal_reg_weight, orthogonal_reg_max_codes = VectorQuantizer._check_orthogonal(orthogonal_reg_weight,
                                                                                            orthogonal_reg_max_codes)
         if orthogonal_reg_weight > 0.0:
@@ -1042,22 +1103,24 @@ class VQVAE(nn.Module):
                 if restart_threshold is not None:
                     raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
                 self.vector_quantization = FactorizedVectorQuantizer(n_embeddings, embedding_dim, codebook_dim, beta,
-                                                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim, **orth)
+                                                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim, **orth,
+                                                                     **ent)
             else:
                 self.vector_quantization = FactorizedVectorQuantizerEMA(n_embeddings, embedding_dim, codebook_dim, beta,
                                                                         decay=ema_decay, eps=ema_eps,
                                                                         restart_threshold=restart_threshold,
-                                                                        rotation_trick=rotation_trick, cosine_sim=cosine_sim)
+                                                                        rotation_trick=rotation_trick, cosine_sim=cosine_sim,
+                                                                        **ent)
         elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
             self.vector_quantization = VectorQuantizer(n_embeddings, embedding_dim, beta, rotation_trick=rotation_trick,
-                                                       cosine_sim=cosine_sim, **orth)
+                                                       cosine_sim=cosine_sim, **orth, **ent)
         else:
             # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
             self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,
                                                           restart_threshold=restart_threshold, rotation_trick=rotation_trick,
-                                                          cosine_sim=cosine_sim)
+                                                          cosine_sim=cosine_sim, **ent)
         self.decoder = Decoder(embedding_dim, h_dim, n_res_layers, res_h_dim)
         if save_img_embedding_map:
             self.img_to_embedding_map = {i: [] for i in range(n_embeddings)}

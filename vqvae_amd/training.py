@@ -555,3 +555,35 @@ class OrthogonalLoss(torch.autograd.Function):
     def backward(ctx, g):
         saved, selected, count = ctx.saved_tensors
         return F_hip.vq_orthogonal_backward(saved, selected, count, g.contiguous()), None, None, None, None
+
+
+# ---- the code-entropy loss of a learned codebook (csrc/vq_entropy.hip) --------------------------------------------------------------
+
+class CodeEntropyLoss(torch.autograd.Function):
+    """(z, codebook) -> term = P - gamma * H of the rows' softmax over the codes, forward and backward on the HIP kernels
+    (functional.vq_entropy_forward / vq_entropy_backward): differentiable in z and in the codebook, and only the gradients that
+    needs_input_grad names are formed.  The forward saves avg (K) and the rows' log-sum-exp and entropy (N, 2), all fp64; the (N, K)
+    softmax never exists.  apply(z, codebook, inv_temperature, gamma, rowmajor, workspace) -> term (0-dim).  last_losses: the device
+    3-vector (term, P, H) of the latest forward in this process, for a caller that logs the two entropies."""
+
+    last_losses = None
+
+    @staticmethod
+    def forward(ctx, z, codebook, inv_temperature, gamma, rowmajor, workspace):
+        losses, avg, rowstat = F_hip.vq_entropy_forward(z.detach(), codebook.detach(), inv_temperature=inv_temperature, gamma=gamma,
+                                                        rowmajor=rowmajor, want_saved=True, workspace=workspace)
+        ctx.save_for_backward(z, codebook, avg, rowstat)
+        ctx.opts = (float(inv_temperature), float(gamma), bool(rowmajor), workspace)
+        CodeEntropyLoss.last_losses = losses
+        return losses[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        z, codebook, avg, rowstat = ctx.saved_tensors
+        s, gamma, rowmajor, ws = ctx.opts
+        want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if not any(want):
+            return None, None, None, None, None, None
+        gz, ge = F_hip.vq_entropy_backward(z.detach(), codebook.detach(), avg, rowstat, g.contiguous(), inv_temperature=s, gamma=gamma,
+                                           rowmajor=rowmajor, want=want, workspace=ws)
+        return gz, ge, None, None, None, None
