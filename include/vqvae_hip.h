@@ -342,6 +342,29 @@ VQVAE_API int vqvae_vq_ema_update_f32(const float *z_e, const int64_t *idx, int6
                                       float *ema_cluster_size, float *ema_w, float *codebook,
                                       void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
 
+/* The same update cut in two (csrc/vq_ema_merge.hip; its header is the numeric contract), so that the statistics of R shards --
+ * other ranks' batches, or earlier micro-batches of this rank -- are merged before the codebook moves.
+ * vqvae_vq_ema_stats_f32: one shard's record, stats (K, C) fp64, every element written: column 0 the count c_k (an exact integer),
+ *   columns 1 .. D the fp64 sum s_k of the code's rows exactly as vqvae_vq_ema_update_f32 forms it (unrounded), and, with
+ *   row_uniforms (K fp32 in [0, 1)), columns D + 1 .. 2 D the shard's restart candidate: row clamp(floor(u_k N_s), 0, N_s - 1) of
+ *   z_e as doubles.  C = D + 1 without row_uniforms, 2 D + 1 with them.  The same bits in either layout of z_e.
+ * vqvae_vq_ema_apply_f32: stats (R, K, C), shard-major.  c_k = sum_s c_{s,k}; S_k = ((s_0 + s_1) + ...) in fp64 in shard order;
+ *   then vqvae_vq_ema_update_f32's update, operation for operation.  Restart (shard_uniforms K fp32, threshold >= 0, C = 2 D + 1):
+ *   a code with N_k < threshold takes the candidate of shard clamp(floor(v_k R), 0, R - 1).  R = 1: the bits of
+ *   vqvae_vq_ema_update_f32 with row_uniforms as its uniforms.  codebook must not alias ema_w or stats.
+ * Envelope: stats as vqvae_vq_ema_update_f32 (flags: VQVAE_VQ_ROWMAJOR only); apply 1 <= R <= 1024, C in {D + 1, 2 D + 1}, decay in
+ * [0, 1], eps > 0, shard_uniforms only with C = 2 D + 1: VQVAE_ERR_UNSUPPORTED outside it and for a stats pointer that is not 8-byte
+ * aligned; the sizing calls then return 0.  No host sync, no allocation, no memset, no floating-point atomics; every launch on
+ * `stream` in one linear chain (capturable); the same bits in every run.                                                      */
+VQVAE_API size_t vqvae_vq_ema_stats_workspace_bytes(int64_t N, int K, int D);
+VQVAE_API int vqvae_vq_ema_stats_f32(const float *z_e, const int64_t *idx, int64_t B, int D, int H, int W, int K,
+                                     const float *row_uniforms, int flags, double *stats,
+                                     void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+VQVAE_API size_t vqvae_vq_ema_apply_workspace_bytes(int R, int K, int D);
+VQVAE_API int vqvae_vq_ema_apply_f32(const double *stats, int R, int K, int D, int C, double decay, double eps, double threshold,
+                                     const float *shard_uniforms, float *ema_cluster_size, float *ema_w, float *codebook,
+                                     void *workspace, size_t workspace_bytes, vqvae_stream_t stream);
+
 /* k-means initialisation of the codebook (csrc/vq_kmeans.hip; its header is the numeric contract): a data-dependent start instead of
  * uniform(-1/K, 1/K) (models/quantizer.py:26-27).  Both calls take z_e in the layout VQVAE_VQ_ROWMAJOR selects (no other flag); rows
  * are the N = B H W rows in the quantizer's order.  One workspace size serves both.  No RNG of their own: the caller supplies K fp32

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Training-step time (forward + loss + backward, no optimizer) of main.py:74-78: convs on the HIP kernels vs
 torch's conv autograd (MIOpen), the quantizer on the HIP forward/backward either way.
-    train_bench.py [B] [backends] [steps] [adam|hipadam|-] [rotation] [cosine] [fsq] [groups] [lfq] [factorized] [orth] [entropy]
+    train_bench.py [B] [backends] [steps] [adam|hipadam|-] [rotation] [cosine] [fsq] [groups] [lfq] [factorized] [orth] [entropy] [ema] [ema_accumulate]
+                                                     ema: VQVAE(..., ema_decay=0.99), the EMA codebook (one update per forward);
+                                                     ema_accumulate: + ema_accumulate=2, the codebook moves once per two forwards from
+                                                     their merged statistics (csrc/vq_ema_merge.hip); absent: the model as it always was
                                                      entropy: VQVAE(..., entropy_weight=0.1), the code-entropy loss of the codebook joins the training
                                                      loss (csrc/vq_entropy.hip); absent: the model as it always was
                                                      orth: VQVAE(..., orthogonal_reg_weight=10.0), the orthogonal regularization loss of
@@ -38,10 +41,13 @@ lfq = "lfq" in sys.argv[4:]
 factorized = "factorized" in sys.argv[4:]
 orth = "orth" in sys.argv[4:]
 entropy = "entropy" in sys.argv[4:]
+ema_acc = "ema_accumulate" in sys.argv[4:]
+ema = ema_acc or "ema" in sys.argv[4:]
 opts = {**({"rotation_trick": True} if rotation else {}), **({"cosine_sim": True} if cosine else {}),
         **({"fsq_levels": (8, 5, 5, 5)} if fsq else {}), **({"codebook_groups": 4} if groups else {}),
         **({"lookup_free": True} if lfq else {}), **({"codebook_dim": 8} if factorized else {}),
-        **({"orthogonal_reg_weight": 10.0} if orth else {}), **({"entropy_weight": 0.1} if entropy else {})}
+        **({"orthogonal_reg_weight": 10.0} if orth else {}), **({"entropy_weight": 0.1} if entropy else {}),
+        **({"ema_decay": 0.99} if ema else {}), **({"ema_accumulate": 2} if ema_acc else {})}
 model = VQVAE(128, 32, 2, 1000 if fsq else (1024 if lfq else 512), 64, 0.25, **opts).to(dev).train()
 x = torch.randn(B, 3, 32, 32, device=dev)
 backends = sys.argv[2].split(",") if len(sys.argv) > 2 else ["hip", "torch"]
@@ -72,5 +78,5 @@ for backend in backends:
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / n
-    print(f"backend={backend:5s} B={B}{' +' + which_adam if with_adam else ''}{' rotation_trick' if rotation else ''}{' cosine_sim' if cosine else ''}{' fsq_levels=(8,5,5,5)' if fsq else ''}{' codebook_groups=4' if groups else ''}{' lookup_free' if lfq else ''}{' codebook_dim=8' if factorized else ''}{' orthogonal_reg_weight=10' if orth else ''}{' entropy_weight=0.1' if entropy else ''}: {dt * 1e3:8.2f} ms per forward+backward   {B / dt / 1e3:8.1f} k img/s", flush=True)
+    print(f"backend={backend:5s} B={B}{' +' + which_adam if with_adam else ''}{' rotation_trick' if rotation else ''}{' cosine_sim' if cosine else ''}{' fsq_levels=(8,5,5,5)' if fsq else ''}{' codebook_groups=4' if groups else ''}{' lookup_free' if lfq else ''}{' codebook_dim=8' if factorized else ''}{' orthogonal_reg_weight=10' if orth else ''}{' entropy_weight=0.1' if entropy else ''}{' ema_decay=0.99' if ema else ''}{' ema_accumulate=2' if ema_acc else ''}: {dt * 1e3:8.2f} ms per forward+backward   {B / dt / 1e3:8.1f} k img/s", flush=True)
 conv.set_conv_backend("hip")

@@ -95,8 +95,15 @@ def parse(argv=None):
     p.add_argument("--entropy_weight", type=float, default=argparse.SUPPRESS, metavar="W")
     p.add_argument("--entropy_diversity_gamma", type=float, default=argparse.SUPPRESS, metavar="G")
     p.add_argument("--entropy_inv_temperature", type=float, default=argparse.SUPPRESS, metavar="S")
+    # opt-in merged EMA statistics (ema_accumulate=A: the codebook moves once per A forwards; ema_sync: merged across the process
+    # group's ranks; csrc/vq_ema_merge.hip); absent unless given
+    p.add_argument("--ema_accumulate", type=int, default=argparse.SUPPRESS, metavar="A")
+    p.add_argument("--ema_sync", action="store_true", default=argparse.SUPPRESS)
     args = p.parse_args(argv)
     ema_kw = {}
+    for name in ("ema_accumulate", "ema_sync"):
+        if hasattr(args, name):
+            ema_kw[name] = getattr(args, name)
     for name in ("entropy_weight", "entropy_diversity_gamma", "entropy_inv_temperature"):
         if hasattr(args, name):
             ema_kw[name] = getattr(args, name)

@@ -89,6 +89,11 @@ SIGNATURES = {
     "vqvae_vq_ema_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vqvae_vq_ema_update_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _i32,
                                        _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vqvae_vq_ema_stats_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vqvae_vq_ema_stats_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "vqvae_vq_ema_apply_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "vqvae_vq_ema_apply_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
+                                      _vp, _sz, _vp]),
     "vqvae_vq_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vqvae_vq_kmeans_seed_f32": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "vqvae_vq_kmeans_update_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),

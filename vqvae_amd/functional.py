@@ -173,6 +173,106 @@ def vq_ema_update(z_e: torch.Tensor, idx: torch.Tensor, ema_cluster_size: torch.
     return codebook
 
 
+def vq_ema_stats_workspace(N: int, K: int, D: int, device) -> torch.Tensor:
+    n = _lib.load().vqvae_vq_ema_stats_workspace_bytes(N, K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"EMA statistics: N={N}, K={K}, D={D} not supported (K <= 16384, D <= 256, 1 <= N < 2^31)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_ema_stats(z_e: torch.Tensor, idx: torch.Tensor, K: int, *, row_uniforms: torch.Tensor | None = None,
+                 rowmajor: bool = False, workspace: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One shard's sufficient statistics of the EMA codebook update (vqvae_vq_ema_stats_f32; csrc/vq_ema_merge.hip states the
+    record): -> stats (K, C) float64 with the counts in column 0, the fp64 per-code sums of the rows in columns 1 .. D and, with
+    row_uniforms (K fp32 in [0, 1)), the shard's restart candidates in columns D + 1 .. 2 D.  C = D + 1 or 2 D + 1.
+    z_e: (B,D,H,W), or (B,H,W,D) when rowmajor; idx: the forward's indices.  out: a contiguous (K, C) float64 tensor to write."""
+    _check_dev("z_e", z_e)
+    _check_dev("idx", idx, torch.int64)
+    if z_e.dim() != 4:
+        raise ValueError("z_e must be 4-D")
+    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
+    K = int(K)
+    if idx.numel() != B * H * W:
+        raise ValueError("idx must hold one index per row of z_e")
+    if row_uniforms is not None:
+        _check_dev("row_uniforms", row_uniforms)
+        row_uniforms = row_uniforms.contiguous()
+        if row_uniforms.numel() != K:
+            raise ValueError("row_uniforms must hold K values")
+    C = D + 1 if row_uniforms is None else 2 * D + 1
+    dev = z_e.device
+    if out is not None:
+        _check_dev("out", out, torch.float64)
+        if out.shape != (K, C) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous ({K}, {C}) tensor")
+    z_e = z_e.contiguous()
+    idx = idx.contiguous()
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_ema_stats_workspace(B * H * W, K, D, dev)
+        if out is None:
+            out = torch.empty((K, C), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().vqvae_vq_ema_stats_f32(
+            z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, row_uniforms.data_ptr() if row_uniforms is not None else None,
+            VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
+    return out
+
+
+def vq_ema_apply_workspace(R: int, K: int, D: int, device) -> torch.Tensor:
+    n = _lib.load().vqvae_vq_ema_apply_workspace_bytes(R, K, D)
+    if n == 0:
+        raise _lib.VqvaeHipError(f"EMA apply: R={R}, K={K}, D={D} not supported (1 <= R <= 1024, K <= 16384, D <= 256)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def vq_ema_apply(stats, ema_cluster_size: torch.Tensor, ema_w: torch.Tensor, codebook: torch.Tensor, decay: float,
+                 eps: float = 1e-5, *, threshold: float | None = None, shard_uniforms: torch.Tensor | None = None,
+                 workspace: torch.Tensor | None = None):
+    """One EMA codebook update from the statistics of R shards (vqvae_vq_ema_apply_f32): counts and sums are added in shard order
+    in fp64, then vq_ema_update's arithmetic.  stats: (R, K, C) float64, or a list of R (K, C) tensors (stacked here).  Writes
+    ema_cluster_size (K,), ema_w (K, D) and codebook (K, D) in place through their data pointers (no autograd version bump).
+    threshold / shard_uniforms (K fp32 in [0, 1)): a code whose averaged count is below threshold takes the candidate of shard
+    floor(v_k R) -- the records must carry candidates (C = 2 D + 1); both or neither."""
+    if isinstance(stats, (list, tuple)):
+        for s in stats:
+            _check_dev("stats", s, torch.float64)
+        if not stats or any(s.dim() != 2 or s.shape != stats[0].shape for s in stats):
+            raise ValueError("stats must be a (R, K, C) tensor or a non-empty list of (K, C) tensors of one shape")
+        stats = torch.stack(list(stats))
+    _check_dev("stats", stats, torch.float64)
+    for name, t in (("ema_cluster_size", ema_cluster_size), ("ema_w", ema_w), ("codebook", codebook)):
+        _check_dev(name, t)
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous (it is written in place)")
+    if stats.dim() != 3:
+        raise ValueError("stats must be (R, K, C)")
+    R, K, C = stats.shape
+    if codebook.dim() != 2 or codebook.shape[0] != K:
+        raise ValueError("shape mismatch between stats and codebook")
+    D = codebook.shape[1]
+    if C not in (D + 1, 2 * D + 1) or ema_w.shape != (K, D) or ema_cluster_size.shape != (K,):
+        raise ValueError("shape mismatch between stats, ema_cluster_size, ema_w and codebook")
+    if (threshold is None) != (shard_uniforms is None):
+        raise ValueError("restart needs both threshold and shard_uniforms")
+    if shard_uniforms is not None:
+        _check_dev("shard_uniforms", shard_uniforms)
+        shard_uniforms = shard_uniforms.contiguous()
+        if shard_uniforms.numel() != K:
+            raise ValueError("shard_uniforms must hold K values")
+        if C != 2 * D + 1:
+            raise ValueError("restart needs statistics taken with row_uniforms (C = 2 D + 1)")
+    stats = stats.contiguous()
+    dev = stats.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = vq_ema_apply_workspace(R, K, D, dev)
+        _lib.check(_lib.load().vqvae_vq_ema_apply_f32(
+            stats.data_ptr(), R, K, D, C, float(decay), float(eps), float(threshold) if threshold is not None else -1.0,
+            shard_uniforms.data_ptr() if shard_uniforms is not None else None, ema_cluster_size.data_ptr(), ema_w.data_ptr(),
+            codebook.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(stats)))
+    return codebook
+
+
 def vq_kmeans_workspace(N: int, K: int, D: int, device) -> torch.Tensor:
     """one workspace for vq_kmeans_seed and vq_kmeans_update at these sizes"""
     n = _lib.load().vqvae_vq_kmeans_workspace_bytes(N, K, D)

@@ -79,6 +79,11 @@ class GraphedStep:
     def __init__(self, model, step, *example_inputs, warmup: int = 3):
         if not example_inputs or not all(t.is_cuda for t in example_inputs):
             raise _lib.VqvaeHipError("GraphedStep needs CUDA(HIP) example inputs: there is no CPU path")
+        for mod in model.modules():
+            if getattr(mod, "_ema_merging", False):
+                # the pending count, the collective and the decision to apply are Python state: a replay would run none of it
+                raise _lib.VqvaeHipError("GraphedStep captures one forward, not a cycle of the EMA quantizer's sync / accumulate "
+                                         "options (ema_sync, ema_accumulate): step such a model eagerly")
         _lib.load()
         _lib.profile_enable(False)
         self.model = model

@@ -316,7 +316,130 @@ class VectorQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
-class VectorQuantizerEMA(VectorQuantizer):
+def _drop_pending_after_load(module, incompatible_keys):
+    """load_state_dict post-hook of an EMA quantizer with sync / accumulate (a module-level function: it must pickle)."""
+    _cache.drop(module, "ema_pending")
+
+
+class _EMAMerge:
+    """What the EMA quantizers share for `sync` / `accumulate`: instead of one update per training forward, a forward takes one
+    record of sufficient statistics per codebook (functional.vq_ema_stats) into a pending device buffer (A, G, K, C); on the A-th
+    record the records -- with `sync` and an initialised process group of W > 1 ranks, the records of every rank, rank-major --
+    are applied once (functional.vq_ema_apply, R = A or W A shards added in a fixed order) and the new codebooks are copied into
+    the parameters in place.  G: the codebooks of the module (1, or the groups).  Forwards inside a cycle all see one codebook.
+
+    The pending records live in the weak side table (never in the state_dict): load_state_dict, invalidate(), .to() and
+    init_codebook_ drop them.  The collectives are reached through `_ema_gather` and `_ema_broadcast`, which an instance may
+    replace (the defaults are sharding.all_gather_ema_stats and sharding.broadcast_ema_uniforms).
+
+    Restart: one torch.rand(2, K) per codebook, in group order, at the first record of a cycle, from `generator` or the default
+    CUDA generator; under `sync` overwritten by rank 0's.  Row 0 picks the shard (shard_uniforms), row 1 the row of every shard
+    (every record's row_uniforms).  Without a threshold nothing is drawn or broadcast."""
+
+    @staticmethod
+    def _ema_gather(stats, group=None):
+        from . import sharding
+        return sharding.all_gather_ema_stats(stats, group)
+
+    @staticmethod
+    def _ema_broadcast(u, group=None):
+        from . import sharding
+        return sharding.broadcast_ema_uniforms(u, group)
+
+    @staticmethod
+    def _check_accumulate(accumulate):
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or not 1 <= accumulate <= 1024:
+            raise ValueError(f"accumulate must be an int in [1, 1024], got {accumulate!r}")
+        return accumulate
+
+    def _init_ema_merge(self, sync, accumulate):
+        self.ema_sync = bool(sync)
+        self.ema_accumulate = self._check_accumulate(accumulate)
+        if self._ema_merging:
+            self.register_load_state_dict_post_hook(_drop_pending_after_load)
+
+    @property
+    def _ema_merging(self):
+        return self.ema_sync or self.ema_accumulate > 1
+
+    @property
+    def pending_ema_updates(self) -> int:
+        """records taken since the last apply"""
+        pend = _cache.side(self).get("ema_pending")
+        return pend["count"] if pend else 0
+
+    def _ema_states(self):
+        """[(ema_cluster_size (K,), ema_w (K, d), codebook parameter)] in group order"""
+        return [(self.ema_cluster_size, self.ema_w, self.embedding.weight)]
+
+    def _ema_side_ws(self, name, key, make):
+        table = _cache.side(self).setdefault(name, {})
+        ws = _cache.lru_get(table, key)
+        if ws is None:
+            ws = make()
+            _cache.lru_put(table, key, ws, 4)
+        return ws
+
+    def _ema_record(self, zs, idxs, rowmajor):
+        """one record per codebook from this forward's rows zs[g] and indices idxs[g]; the A-th record applies"""
+        states = self._ema_states()
+        w = states[0][2]
+        dev, (K, d), G, A = w.device, w.shape, len(states), self.ema_accumulate
+        restart = self.restart_threshold is not None
+        C = 2 * d + 1 if restart else d + 1
+        side = _cache.side(self)
+        pend = side.get("ema_pending")
+        if pend is None or pend["buf"].shape != (A, G, K, C) or pend["buf"].device != dev:
+            pend = side["ema_pending"] = {"count": 0, "uniforms": None,
+                                          "buf": torch.empty((A, G, K, C), dtype=torch.float64, device=dev)}
+        if pend["count"] == 0 and restart:
+            u = torch.stack([torch.rand(2, K, device=dev, generator=self.generator) for _ in range(G)])
+            if self.ema_sync:
+                got = self._ema_broadcast(u)
+                u = u if got is None else got
+            pend["uniforms"] = u
+        u = pend["uniforms"]
+        N = idxs[0].numel()
+        ws = self._ema_side_ws("ema_stats_ws", (str(dev), torch.cuda.current_stream(dev).cuda_stream, N),
+                               lambda: F_hip.vq_ema_stats_workspace(N, K, d, dev))
+        a = pend["count"]
+        for g in range(G):
+            F_hip.vq_ema_stats(zs[g], idxs[g], K, row_uniforms=u[g, 1] if restart else None, rowmajor=rowmajor, workspace=ws,
+                               out=pend["buf"][a, g])
+        pend["count"] = a + 1
+        if pend["count"] >= A:
+            self.flush_ema_()
+
+    @torch.no_grad()
+    def flush_ema_(self):
+        """Apply what is pending now, with R = pending (W * pending under `sync` with W > 1 ranks: every rank must then hold the
+        same number of records), and start a new cycle.  Nothing pending: nothing happens."""
+        pend = _cache.side(self).get("ema_pending")
+        if not pend or pend["count"] == 0:
+            return
+        A, (_, G, K, C) = pend["count"], pend["buf"].shape
+        stats = pend["buf"][:A].reshape(A, G * K, C)
+        if self.ema_sync:
+            stats = self._ema_gather(stats)
+        R = stats.shape[0]
+        stats = stats.reshape(R, G, K, C)
+        dev = stats.device
+        restart = self.restart_threshold is not None
+        u = pend["uniforms"]
+        states = self._ema_states()
+        d = states[0][2].shape[1]
+        ws = self._ema_side_ws("ema_apply_ws", (str(dev), torch.cuda.current_stream(dev).cuda_stream, R),
+                               lambda: F_hip.vq_ema_apply_workspace(R, K, d, dev))
+        for g, (cluster_size, ema_w, w) in enumerate(states):
+            new = torch.empty_like(w, memory_format=torch.contiguous_format)
+            F_hip.vq_ema_apply(stats[:, g], cluster_size, ema_w, new, self.decay, self.eps,
+                               threshold=self.restart_threshold, shard_uniforms=u[g, 0] if restart else None, workspace=ws)
+            w.copy_(new)
+        pend["count"] = 0
+        pend["uniforms"] = None
+
+
+class VectorQuantizerEMA(_EMAMerge, VectorQuantizer):
     """VectorQuantizer whose codebook follows exponential moving averages of the encoder outputs assigned to each code
     (arXiv 1711.00937 Appendix A.1; Sonnet's VectorQuantizerEMA) instead of a gradient.
 
@@ -328,11 +451,17 @@ class VectorQuantizerEMA(VectorQuantizer):
     is the commitment term only, beta * mean((z_q - z)^2), and the codebook gets no gradient.
 
     restart_threshold: codes whose N_k falls below it take a row of the batch instead (row floor(u_k N), u drawn on the device from
-    `generator`, or the default CUDA generator, on every update).  None: no restart.  Under data parallelism each replica updates
-    from its own shard; the statistics are not merged across ranks."""
+    `generator`, or the default CUDA generator, on every update).  None: no restart.
+
+    sync / accumulate (_EMAMerge): with the defaults every replica of a data-parallel run updates from its own shard after every
+    forward.  accumulate=A applies once per A training forwards, from the merged statistics of the A batches; sync=True merges
+    the statistics of all ranks of the initialised process group first (every rank must run the same number of training
+    forwards), after which all ranks hold bit-identical `embedding.weight`, `ema_cluster_size` and `ema_w`.  `pending_ema_updates`
+    counts the records of the open cycle and `flush_ema_()` applies them early."""
 
     def __init__(self, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, rotation_trick=False,
-                 cosine_sim=False, entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0):
+                 cosine_sim=False, entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0, sync=False,
+                 accumulate=1):
         super().__init__(n_e, e_dim, beta, rotation_trick=rotation_trick, cosine_sim=cosine_sim, entropy_weight=entropy_weight,
                          entropy_diversity_gamma=entropy_diversity_gamma, entropy_inv_temperature=entropy_inv_temperature)
         self.decay = float(decay)
@@ -342,8 +471,16 @@ class VectorQuantizerEMA(VectorQuantizer):
         self.embedding.weight.requires_grad_(False)
         self.register_buffer("ema_cluster_size", torch.zeros(n_e))
         self.register_buffer("ema_w", self.embedding.weight.detach().clone())
+        self._init_ema_merge(sync, accumulate)
+
+    def invalidate(self):
+        """VectorQuantizer.invalidate, and the pending statistics of an open sync / accumulate cycle are dropped."""
+        super().invalidate()
+        _cache.drop(self, "ema_pending")
 
     def _ema_update(self, z, idx, rowmajor):
+        if self._ema_merging:
+            return self._ema_record([z], [idx], rowmajor)
         w = self.embedding.weight
         side = _cache.side(self)
         N = idx.numel()
@@ -367,6 +504,7 @@ class VectorQuantizerEMA(VectorQuantizer):
         """VectorQuantizer.init_codebook_, and the EMA state continues from the clusters: ema_cluster_size = counts,
         ema_w = counts[:, None] * codebook."""
         codebook, counts = super().init_codebook_(z, iters, generator, rowmajor=rowmajor)
+        _cache.drop(self, "ema_pending")
         c = counts.to(torch.float32)
         self.ema_cluster_size.copy_(c)
         self.ema_w.copy_(c[:, None] * codebook)
@@ -489,18 +627,19 @@ class FactorizedVectorQuantizerEMA(FactorizedVectorQuantizer, VectorQuantizerEMA
     the two projections.  State: FactorizedVectorQuantizer's, and the buffers `ema_cluster_size` (K,) and `ema_w` (K, codebook_dim).
     The update runs from y = project_in(z) (from y^ with cosine_sim) and that forward's indices, in training mode only, after the
     inner quantizer's outputs are formed; the projections are trained by their gradients.  With init_codebook_ the EMA state
-    continues from the clusters, as VectorQuantizerEMA's does."""
+    continues from the clusters, as VectorQuantizerEMA's does.  sync / accumulate: VectorQuantizerEMA's, the records taken from y
+    (y^ with cosine_sim) exactly where the update reads."""
 
     _INNER = VectorQuantizerEMA
 
     def __init__(self, n_e, dim, codebook_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *,
                  rotation_trick=False, cosine_sim=False, entropy_weight=0.0, entropy_diversity_gamma=1.0,
-                 entropy_inv_temperature=100.0):
+                 entropy_inv_temperature=100.0, sync=False, accumulate=1):
         dim, codebook_dim = self._check_dims(dim, codebook_dim)
         VectorQuantizerEMA.__init__(self, n_e, codebook_dim, beta, decay, eps, restart_threshold, generator,
                                     rotation_trick=rotation_trick, cosine_sim=cosine_sim, entropy_weight=entropy_weight,
                                     entropy_diversity_gamma=entropy_diversity_gamma,
-                                    entropy_inv_temperature=entropy_inv_temperature)
+                                    entropy_inv_temperature=entropy_inv_temperature, sync=sync, accumulate=accumulate)
         self._init_projections(dim, codebook_dim)
 
 
@@ -708,7 +847,7 @@ class GroupedVectorQuantizer(nn.Module):
         return loss, z_q, perplexity, min_encodings, idx
 
 
-class GroupedVectorQuantizerEMA(GroupedVectorQuantizer):
+class GroupedVectorQuantizerEMA(_EMAMerge, GroupedVectorQuantizer):
     """GroupedVectorQuantizer whose codebooks follow exponential moving averages (VectorQuantizerEMA, per group) instead of a
     gradient.
 
@@ -718,9 +857,13 @@ class GroupedVectorQuantizerEMA(GroupedVectorQuantizer):
     indices, then copies the new codebooks in place.  Eval mode never updates.  The forward's outputs are those of the codebooks
     BEFORE the update; the loss is beta * the mean over the groups of the group's mse, and the codebooks get no gradient.
 
-    restart_threshold: as VectorQuantizerEMA's, per group: one torch.rand(K) per group and update, drawn in group order."""
+    restart_threshold: as VectorQuantizerEMA's, per group: one torch.rand(K) per group and update, drawn in group order.
 
-    def __init__(self, n_g, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None):
+    sync / accumulate: as VectorQuantizerEMA's (_EMAMerge): one record per group and training forward, one gather for all groups,
+    one apply per group in group order; with restart one torch.rand(2, K) per group, in group order, at a cycle's first record."""
+
+    def __init__(self, n_g, n_e, e_dim, beta, decay=0.99, eps=1e-5, restart_threshold=None, generator=None, *, sync=False,
+                 accumulate=1):
         super().__init__(n_g, n_e, e_dim, beta)
         self.decay = float(decay)
         self.eps = float(eps)
@@ -730,8 +873,19 @@ class GroupedVectorQuantizerEMA(GroupedVectorQuantizer):
             w.requires_grad_(False)
         self.register_buffer("ema_cluster_size", torch.zeros(self.n_g, n_e))
         self.register_buffer("ema_w", torch.stack([w.detach().clone() for w in self.codebooks()]))
+        self._init_ema_merge(sync, accumulate)
+
+    def invalidate(self):
+        """GroupedVectorQuantizer.invalidate, and the pending statistics of an open sync / accumulate cycle are dropped."""
+        super().invalidate()
+        _cache.drop(self, "ema_pending")
+
+    def _ema_states(self):
+        return [(self.ema_cluster_size[g], self.ema_w[g], w) for g, w in enumerate(self.codebooks())]
 
     def _ema_update(self, slabs, idx, rowmajor):
+        if self._ema_merging:
+            return self._ema_record(list(slabs), list(idx), rowmajor)
         books = self.codebooks()
         dev = books[0].device
         N = idx.shape[1]
@@ -756,6 +910,7 @@ class GroupedVectorQuantizerEMA(GroupedVectorQuantizer):
         """GroupedVectorQuantizer.init_codebook_, and the EMA state continues from the clusters: ema_cluster_size[g] = counts,
         ema_w[g] = counts[:, None] * codebook."""
         out = super().init_codebook_(z, iters, generator, rowmajor=rowmajor)
+        _cache.drop(self, "ema_pending")
         for g, (codebook, counts) in enumerate(out):
             c = counts.to(torch.float32)
             self.ema_cluster_size[g].copy_(c)
@@ -1003,8 +1158,15 @@ class VQVAE(nn.Module):
                  shared_codebook=False, rotation_trick=False, cosine_sim=False, fsq_levels=None, codebook_groups=1,
                  lookup_free=False, lfq_entropy_weight=0.1, lfq_diversity_gamma=1.0, lfq_inv_temperature=100.0,
                  orthogonal_reg_weight=0.0, orthogonal_reg_active_codes_only=False, orthogonal_reg_max_codes=None,
-                 entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0, codebook_dim=None):
+                 ema_sync=False, ema_accumulate=1, entropy_weight=0.0, entropy_diversity_gamma=1.0, entropy_inv_temperature=100.0,
+                 codebook_dim=None):
         super().__init__()
+        # ema_sync / ema_accumulate: the EMA quantizers' sync / accumulate (_EMAMerge): the codebook moves once per ema_accumulate
+        # training forwards, from the statistics of those batches merged -- with ema_sync across the process group's ranks too
+        ema_accumulate = _EMAMerge._check_accumulate(ema_accumulate)
+        if ema_decay is None and (ema_sync or ema_accumulate != 1):
+            raise ValueError("ema_sync / ema_accumulate need the EMA codebook (ema_decay)")
+        merge = dict(sync=bool(ema_sync), accumulate=ema_accumulate)
         # entropy_weight > 0: the code-entropy loss of the learned codebook (csrc/vq_entropy.hip) joins the training loss of the
         # one-stage quantizers -- plain, EMA (only z takes its gradient), cosine_sim (on the unit rows: entropy_inv_temperature = 50
         # is MaskGIT's temperature of 0.01), rotation_trick, codebook_dim (on the projected rows)
@@ -1087,7 +1249,7 @@ class VQVAE(nn.Module):
             else:
                 self.vector_quantization = GroupedVectorQuantizerEMA(codebook_groups, n_embeddings, embedding_dim, beta,
                                                                      decay=ema_decay, eps=ema_eps,
-                                                                     restart_threshold=restart_threshold)
+                                                                     restart_threshold=restart_threshold, **merge)
         elif fsq_levels is not None:
             self.vector_quantization = FiniteScalarQuantizer(fsq_levels, embedding_dim)       # (beta: accepted, unused)
         elif lookup_free:
@@ -1110,7 +1272,7 @@ class VQVAE(nn.Module):
                                                                         decay=ema_decay, eps=ema_eps,
                                                                         restart_threshold=restart_threshold,
                                                                         rotation_trick=rotation_trick, cosine_sim=cosine_sim,
-                                                                        **ent)
+                                                                        **ent, **merge)
         elif ema_decay is None:
             if restart_threshold is not None:
                 raise ValueError("restart_threshold needs the EMA codebook (ema_decay)")
@@ -1120,7 +1282,7 @@ class VQVAE(nn.Module):
             # the codebook by exponential moving averages (VectorQuantizerEMA); the random initialisation is VectorQuantizer's
             self.vector_quantization = VectorQuantizerEMA(n_embeddings, embedding_dim, beta, decay=ema_decay, eps=ema_eps,
                                                           restart_threshold=restart_threshold, rotation_trick=rotation_trick,
-                                                          cosine_sim=cosine_sim, **ent)
+                                                          cosine_sim=cosine_sim, **ent, **merge)
         self.decoder = Decoder(embedding_dim, h_dim, n_res_layers, res_h_dim)
         if save_img_embedding_map:
             self.img_to_embedding_map = {i: [] for i in range(n_embeddings)}
