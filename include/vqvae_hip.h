@@ -19,6 +19,21 @@
  *   - return value: 0 on success, a negative VQVAE_ERR_* on argument errors
  *     (nothing is launched), a positive hipError_t if a launch failed.
  *     No exceptions cross this boundary.  vqvae_strerror() names any of them.
+ *
+ * Pointer contract
+ *   - an fp32 or int32 pointer must be 4-byte aligned, an int64 or fp64 pointer 8-byte aligned.
+ *   - many kernels move sixteen bytes per access.  Where an entry's kernels do that on a caller's pointer, the entry
+ *     either takes an element-wise path that gives the same result when the pointer is not 16-byte aligned, or it
+ *     returns VQVAE_ERR_UNSUPPORTED before anything is launched.  No entry launches a 16-byte access on a pointer that
+ *     is not 16-byte aligned.  Which entry does which, pointer by pointer, is tabulated in profiles/pointer_contract.md
+ *     (tests/test_views_cpu.py holds the same table and calls every refusing row).
+ *   - the same holds for the device pointers inside VqvaeRawWeights and VqvaeWeights: the codebook (handed on unpacked, and
+ *     read 16 bytes at a time) and the packed images are 16-byte aligned, weights and biases 4-byte aligned;
+ *     vqvae_weights_pack_f32 and every entry that takes a VqvaeWeights test them before their first launch.
+ *   - workspaces and packed images are 16-byte aligned (the *_bytes() functions size them; any hipMalloc result is).
+ *   - a tensor is dense: a strided view has no meaning at this boundary.  The Python front end (vqvae_amd/_lib.py:
+ *     dense / written) copies a strided or under-aligned tensor to fresh storage where the entry behind a call would
+ *     refuse it, so every public Python call accepts any view and returns the bits of its dense copy.
  */
 #ifndef VQVAE_HIP_H
 #define VQVAE_HIP_H

@@ -265,6 +265,44 @@ def check(code: int):
         raise VqvaeHipError(f"libvqvae_hip: {load().vqvae_strerror(code).decode()} (code {code})")
 
 
+def dense(t, align: int = 16):
+    """The tensor a raw data pointer may be taken from: `t` itself where it is contiguous and its first element lies on an
+    `align`-byte boundary (the only case that costs nothing: one test on the host, no launch), else a fresh contiguous copy --
+    torch's allocators hand out blocks aligned far beyond sixteen bytes.  Every front-end call that takes a tensor's data pointer
+    takes it from what this returns, so a view (a slice of a batch, a parameter inside a flat buffer, a channels_last or expanded tensor) gives
+    the bits its dense copy gives.  The copy is detached: it is storage for a kernel, not a node of a graph.  align: what the entry behind the call needs of this pointer (include/vqvae_hip.h, "Pointer
+    contract"): 16 for the entries that refuse a narrower one, 4 or 8 for those that take an element-wise path themselves.
+    None passes through."""
+    if t is None or (t.is_contiguous() and not t.data_ptr() & (align - 1)):
+        return t
+    return t.detach().clone(memory_format=torch.contiguous_format)
+
+
+class written:
+    """`with written(t) as w:` -- the form of `dense` for a tensor an entry writes in place (EMA state, a codebook under EMA or
+    k-means, an out=): `w` is `t` itself where `dense(t)` is, else a dense copy that is copied back into `t` with copy_ when the
+    block ends without an exception.  The caller's tensor keeps its identity and its storage; where it was a view its _version
+    moves, as after any in-place write."""
+
+    def __init__(self, t, align: int = 16):
+        self.t, self.w = t, dense(t, align)
+
+    def __enter__(self):
+        return self.w
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None and self.w is not self.t:
+            with torch.no_grad():
+                self.t.copy_(self.w)
+        return False
+
+
+def vq_align(D: int) -> int:
+    """what vqvae_vq_forward_f32 needs of z_e and the codebook: 16 at the fixed widths (it refuses less), 4 at the others (the
+    any-width kernels take their element-wise forms)"""
+    return 16 if D in (32, 64, 128, 256) else 4
+
+
 def vq_kernel_name(K: int, D: int, flags: int = 0x1) -> str:
     """kernel vqvae_vq_forward_f32 launches for this shape (default flags: row-major rows, the fused path's layout)"""
     return load().vqvae_vq_kernel_name(K, D, flags).decode()

@@ -51,14 +51,14 @@ def _holder(mod, tag):
 
 
 def relu_backward(g, y):
-    g = g.contiguous()
+    g, y = _lib.dense(g), _lib.dense(y)
     out = torch.empty_like(g)
     _lib.check(_lib.load().vqvae_relu_backward_f32(g.data_ptr(), y.data_ptr(), g.numel(), out.data_ptr(), _sp(g)))
     return out
 
 
 def bias_grad(g, nchw=False):
-    g = g.contiguous()
+    g = _lib.dense(g, 4)               # (the entry loads element by element, in the same order, where g is not 16-byte aligned)
     if nchw:
         B, C, H, W = g.shape
     else:
@@ -73,8 +73,8 @@ def bias_grad(g, nchw=False):
 
 def conv_wgrad(a_rows, bt, k, stride, pad, bt_nchw=False):
     """grad_w[ca][cb][ky][kx] = sum a[b,y,x,ca] * bt[b, y*s+ky-p, x*s+kx-p, cb]  (see include/vqvae_hip.h)."""
-    a_rows = a_rows.contiguous()
-    bt = bt.contiguous()
+    a_rows = _lib.dense(a_rows)
+    bt = _lib.dense(bt)
     B, HA, WA, CA = a_rows.shape
     if bt_nchw:
         _, CB, HB, WB = bt.shape
@@ -97,10 +97,11 @@ class ConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, mod, kind, relu_out, x_is_relu=False, consumer_masks=False):
         k, s, p, transposed, _ = _GEOM[kind]
         Cin, Cout = (weight.shape[0], weight.shape[1]) if transposed else (weight.shape[1], weight.shape[0])
-        y = conv_hip.conv(kind, x.detach().contiguous(), mod, weight.detach(), bias.detach() if bias is not None else None,
+        x = _lib.dense(x.detach())
+        y = conv_hip.conv(kind, x, mod, weight.detach(), bias.detach() if bias is not None else None,
                           Cin, Cout, RELU_OUT if relu_out else 0)
         own_mask = relu_out and not consumer_masks           # the ReLU backward of this layer's output runs here
-        ctx.save_for_backward(x.detach().contiguous(), weight.detach(), y if own_mask else None)
+        ctx.save_for_backward(x, weight.detach(), y if own_mask else None)
         ctx.mod, ctx.kind, ctx.own_mask, ctx.has_bias, ctx.x_is_relu = mod, kind, own_mask, bias is not None, x_is_relu
         return y
 
@@ -109,7 +110,7 @@ class ConvFn(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         k, s, p, transposed, dkind = _GEOM[ctx.kind]
         Cin, Cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
-        gy = relu_backward(gy, y) if ctx.own_mask else gy.contiguous()
+        gy = relu_backward(gy, y) if ctx.own_mask else _lib.dense(gy)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             # data gradient: the mirrored conv, same weight tensor, channels swapped (+ the ReLU mask of the layer below)
@@ -128,13 +129,13 @@ class ConvInFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_nchw, weight, bias, mod, consumer_masks=False):
         L = _lib.load()
-        x = x_nchw.detach().contiguous()
+        x = _lib.dense(x_nchw.detach(), 4)
         B, Cin, H, W = x.shape
         C0 = weight.shape[0]
         p0 = conv_hip._packed(mod, ("conv_in",), weight, lambda: L.vqvae_conv_in_packed_bytes(Cin, C0),
                               lambda w, buf: L.vqvae_conv_in_pack_f32(w.data_ptr(), Cin, C0, buf.data_ptr(), _sp(w)))
         y = torch.empty((B, H // 2, W // 2, C0), dtype=torch.float32, device=x.device)
-        _lib.check(L.vqvae_conv_in_forward_f32(x.data_ptr(), p0.data_ptr(), bias.detach().data_ptr(), B, H, W, Cin, C0,
+        _lib.check(L.vqvae_conv_in_forward_f32(x.data_ptr(), p0.data_ptr(), _lib.dense(bias.detach(), 4).data_ptr(), B, H, W, Cin, C0,
                                                RELU_OUT, y.data_ptr(), _sp(x)))
         ctx.save_for_backward(x, None if consumer_masks else y)
         return y
@@ -142,7 +143,7 @@ class ConvInFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, y = ctx.saved_tensors
-        gy = relu_backward(gy, y) if y is not None else gy.contiguous()
+        gy = relu_backward(gy, y) if y is not None else _lib.dense(gy)
         gw = conv_wgrad(gy, x, 4, 2, 1, bt_nchw=True) if ctx.needs_input_grad[1] else None
         gb = bias_grad(gy) if ctx.needs_input_grad[2] else None
         return None, gw, gb, None, None
@@ -154,13 +155,13 @@ class ConvTOutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, weight, bias, mod, x_is_relu=False):
         L = _lib.load()
-        t = t.detach().contiguous()
+        t = _lib.dense(t.detach())
         B, H, W, C = t.shape
         Cout = weight.shape[1]
         p4 = conv_hip._packed(mod, ("convt_out",), weight, lambda: L.vqvae_convt_out_packed_bytes(C, Cout),
                               lambda w, buf: L.vqvae_convt_out_pack_f32(w.data_ptr(), C, Cout, buf.data_ptr(), _sp(w)))
         x_hat = torch.empty((B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=t.device)
-        _lib.check(L.vqvae_convt_out_forward_f32(t.data_ptr(), p4.data_ptr(), bias.detach().data_ptr(), B, H, W, C, Cout, 0,
+        _lib.check(L.vqvae_convt_out_forward_f32(t.data_ptr(), p4.data_ptr(), _lib.dense(bias.detach(), 4).data_ptr(), B, H, W, C, Cout, 0,
                                                  x_hat.data_ptr(), _sp(t)))
         ctx.save_for_backward(t, weight.detach())
         ctx.mod, ctx.x_is_relu = mod, x_is_relu
@@ -169,7 +170,7 @@ class ConvTOutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         t, w = ctx.saved_tensors
-        g = g.contiguous()
+        g = _lib.dense(g)
         B, H, W, C = t.shape
         Cout = w.shape[1]
         L = _lib.load()
@@ -206,9 +207,10 @@ class ResLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, w2, layer, relu_in, relu_out, x_is_relu=False, consumer_masks=False):
         flags = (RELU_IN if relu_in else 0) | (RELU_OUT if relu_out else 0)
-        y, hid = conv_hip.res_layer(x.detach().contiguous(), layer, flags, want_hidden=True)
+        x = _lib.dense(x.detach())
+        y, hid = conv_hip.res_layer(x, layer, flags, want_hidden=True)
         own_mask = relu_out and not consumer_masks
-        ctx.save_for_backward(x.detach().contiguous(), w1.detach(), w2.detach(), y if own_mask else None, hid)
+        ctx.save_for_backward(x, w1.detach(), w2.detach(), y if own_mask else None, hid)
         ctx.layer, ctx.relu_in, ctx.own_mask, ctx.x_is_relu = layer, relu_in, own_mask, x_is_relu
         return y
 
@@ -217,7 +219,7 @@ class ResLayerFn(torch.autograd.Function):
         x, w1, w2, y, h = ctx.saved_tensors
         c1, c2 = ctx.layer.res_block[1], ctx.layer.res_block[3]
         C, Rh = w1.shape[1], w1.shape[0]
-        g = relu_backward(gy, y) if ctx.own_mask else gy.contiguous()
+        g = relu_backward(gy, y) if ctx.own_mask else _lib.dense(gy)
         if h is None:
             # h = relu(W1 * r) again with the plain conv kernel (shapes whose fused forward kernel does not write it)
             h = conv_hip.conv(CONV_3x3_S1, x, _holder(ctx.layer, "w1_fwd"), w1, None, C, Rh,

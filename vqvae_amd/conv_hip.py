@@ -51,7 +51,7 @@ def _packed(mod, kind, weight, nbytes_fn, pack_fn):
     if n == 0:
         raise _lib.VqvaeHipError(f"layer shape {tuple(w.shape)} not supported by the gfx950 conv kernels")
     buf = torch.empty(n // 4, dtype=torch.float32, device=w.device)
-    _lib.check(pack_fn(w.contiguous(), buf))
+    _lib.check(pack_fn(_lib.dense(w, 4), buf))              # (the pack kernels read a weight one float at a time)
     cache[kind] = (key, buf, _cache.mark_ready(w.device))
     return buf
 
@@ -74,6 +74,7 @@ def conv(kind, x, mod, weight, bias, Cin, Cout, flags, addend=None, mask=None):
     separately (torch add, vqvae_relu_backward_f32)."""
     B, H, W, C = x.shape
     assert C == Cin
+    x = _lib.dense(x)
     packed = _pack_conv(mod, kind, weight, Cin, Cout)
     if kind == CONV_4x4_S2:
         Ho, Wo = H // 2, W // 2
@@ -82,12 +83,13 @@ def conv(kind, x, mod, weight, bias, Cin, Cout, flags, addend=None, mask=None):
     else:
         Ho, Wo = H, W
     y = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    b = bias.detach() if bias is not None else None
+    b = _lib.dense(bias.detach(), 4) if bias is not None else None       # (read as bias[n])
     L = _lib.load()
     if addend is not None or mask is not None:
         for t in (addend, mask):
-            if t is not None and (t.shape != y.shape or not t.is_contiguous()):
-                raise ValueError("addend / mask must be contiguous with the output's shape")
+            if t is not None and t.shape != y.shape:
+                raise ValueError("addend / mask must have the output's shape")
+        addend, mask = _lib.dense(addend), _lib.dense(mask)
         rc = L.vqvae_conv_forward_ep_f32(kind, x.data_ptr(), packed.data_ptr(), b.data_ptr() if b is not None else None,
                                          B, H, W, Cin, Cout, flags, addend.data_ptr() if addend is not None else None,
                                          mask.data_ptr() if mask is not None else None, y.data_ptr(), _sp(x))
@@ -117,7 +119,8 @@ def conv_taps(x, mod, weight, bias, taps, flags=0):
     if weight.shape[1] != Cin or weight.shape[2] * weight.shape[3] != n:
         raise ValueError("weight must be (Cout, Cin, kh, kw) with kh * kw taps")
     L = _lib.load()
-    b = bias.detach() if bias is not None else None
+    x = _lib.dense(x)
+    b = _lib.dense(bias.detach(), 4) if bias is not None else None       # (read as bias[n])
     nsl = (n + 15) // 16
     if nsl > 1 and (flags & RELU_OUT):
         raise ValueError("an output ReLU cannot ride on a chain of tap slices")
@@ -152,6 +155,7 @@ def res_layer(x, layer, flags, want_hidden=False):
         raise _lib.VqvaeHipError(f"residual layer C={C}, res_h={Rh}: the gfx950 kernels need multiples of 4 channels")
     p1 = _pack_conv(c1, CONV_3x3_S1, c1.weight, C, Rh)
     p2 = _pack_conv(c2, CONV_1x1, c2.weight, Rh, C)
+    x = _lib.dense(x)
     y = torch.empty_like(x)
     if Rh > 32 or C not in (32, 64, 128):
         # widths outside the fused kernel (round 4): 3x3 conv -> 1x1 conv -> skip + ReLU through the conv kernels
@@ -170,6 +174,7 @@ def res_layer(x, layer, flags, want_hidden=False):
 
 
 def transpose(x, batch, R, Cc):
+    x = _lib.dense(x)
     y = torch.empty_like(x)
     _lib.check(_lib.load().vqvae_transpose_f32(x.data_ptr(), batch, R, Cc, y.data_ptr(), _sp(x)))
     return y
@@ -177,12 +182,12 @@ def transpose(x, batch, R, Cc):
 
 def nchw_to_rows(x):
     B, C, H, W = x.shape
-    return transpose(x.contiguous(), B, C, H * W).view(B, H, W, C)
+    return transpose(x, B, C, H * W).view(B, H, W, C)
 
 
 def rows_to_nchw(x):
     B, H, W, C = x.shape
-    return transpose(x.contiguous(), B, H * W, C).view(B, C, H, W)
+    return transpose(x, B, H * W, C).view(B, C, H, W)
 
 
 def _res_stack_rows(t, layers, first_relu_in, final_relu):
@@ -210,7 +215,7 @@ def encoder_forward(enc, x, pre_quant):
     _dev_f32("x", x)
     cs = enc.conv_stack
     c0, c2, c4, stack = cs[0], cs[2], cs[4], cs[5]
-    x = x.contiguous()
+    x = _lib.dense(x, 4)                       # (conv_in takes its gather kernel for an under-aligned image)
     B, Cin, H, W = x.shape
     if Cin != c0.weight.shape[1]:
         raise ValueError(f"expected {c0.weight.shape[1]} input channels, got {Cin}")
@@ -220,7 +225,7 @@ def encoder_forward(enc, x, pre_quant):
                  lambda: L.vqvae_conv_in_packed_bytes(Cin, C0),
                  lambda w, buf: L.vqvae_conv_in_pack_f32(w.data_ptr(), Cin, C0, buf.data_ptr(), _sp(w)))
     a0 = torch.empty((B, H // 2, W // 2, C0), dtype=torch.float32, device=x.device)
-    _lib.check(L.vqvae_conv_in_forward_f32(x.data_ptr(), p0.data_ptr(), c0.bias.detach().data_ptr(), B, H, W, Cin,
+    _lib.check(L.vqvae_conv_in_forward_f32(x.data_ptr(), p0.data_ptr(), _lib.dense(c0.bias.detach(), 4).data_ptr(), B, H, W, Cin,
                                            C0, RELU_OUT, a0.data_ptr(), _sp(x)))                       # :29-31
     C1 = c2.weight.shape[0]
     a1 = conv(CONV_4x4_S2, a0, c2, c2.weight, c2.bias, C0, C1, RELU_OUT)                               # :32-34
@@ -239,7 +244,7 @@ def decoder_forward(dec, z_q, rowmajor_in):
     _dev_f32("z_q", z_q)
     ds = dec.inverse_conv_stack
     d0, stack, d2, d4 = ds[0], ds[1], ds[2], ds[4]
-    t = z_q.contiguous() if rowmajor_in else nchw_to_rows(z_q)
+    t = _lib.dense(z_q) if rowmajor_in else nchw_to_rows(z_q)
     Din = d0.weight.shape[0]
     if t.shape[3] != Din:
         raise ValueError(f"expected {Din} latent channels, got {t.shape[3]}")
@@ -255,6 +260,6 @@ def decoder_forward(dec, z_q, rowmajor_in):
                  lambda: L.vqvae_convt_out_packed_bytes(C2, Cout),
                  lambda w, buf: L.vqvae_convt_out_pack_f32(w.data_ptr(), C2, Cout, buf.data_ptr(), _sp(w)))
     x_hat = torch.empty((B, Cout, 2 * H2, 2 * W2), dtype=torch.float32, device=a2.device)
-    _lib.check(L.vqvae_convt_out_forward_f32(a2.data_ptr(), p4.data_ptr(), d4.bias.detach().data_ptr(), B, H2, W2,
+    _lib.check(L.vqvae_convt_out_forward_f32(a2.data_ptr(), p4.data_ptr(), _lib.dense(d4.bias.detach(), 4).data_ptr(), B, H2, W2,
                                              C2, Cout, 0, x_hat.data_ptr(), _sp(a2)))                     # :34-35
     return x_hat

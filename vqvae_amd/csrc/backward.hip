@@ -602,11 +602,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_img_kernel(const float *__rest
     }
 }
 
+// four consecutive channels of a row: one 16-byte load where the tensor's base allows it (wide, the host's test of the pointer),
+// four 4-byte loads otherwise -- the same values to the same thread, so the sums keep their order and their bits
+__device__ __forceinline__ f32x4 bias_grad_load4(const float *p, int wide) {
+    if (wide) return *reinterpret_cast<const f32x4 *>(p);
+    return f32x4{p[0], p[1], p[2], p[3]};
+}
+
 // per-channel sums of a (P, C) row-major tensor [or an NCHW one: (B, C, HW)] -- stage 1: one partial per block.
-// Row-major with C % 4 == 0: a thread owns four consecutive channels (16-byte loads), 1024 / C rows in flight per
+// Row-major with C % 4 == 0: a thread owns four consecutive channels (16-byte loads where `wide`), 1024 / C rows in flight per
 // block iteration, fp64 accumulators; otherwise one channel per thread.
 __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float *__restrict__ g, long long P, int C,
-                                                                long long HW, int nchw, long long rows_per_block,
+                                                                long long HW, int nchw, int wide, long long rows_per_block,
                                                                 double *__restrict__ partial) {
     __shared__ double red[1024];
     const int tid = threadIdx.x;
@@ -623,12 +630,12 @@ __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float *__r
             for (; p + 3 * G < hi; p += 4 * G) {             // four rows in flight; the sums keep their row order
                 f32x4 v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const f32x4 *>(g + (size_t)(p + j * G) * C + 4 * q);
+                for (int j = 0; j < 4; ++j) v[j] = bias_grad_load4(g + (size_t)(p + j * G) * C + 4 * q, wide);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { a0 += (double)v[j].x; a1 += (double)v[j].y; a2 += (double)v[j].z; a3 += (double)v[j].w; }
             }
             for (; p < hi; p += G) {
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(g + (size_t)p * C + 4 * q);
+                const f32x4 v = bias_grad_load4(g + (size_t)p * C + 4 * q, wide);
                 a0 += (double)v.x; a1 += (double)v.y; a2 += (double)v.z; a3 += (double)v.w;
             }
         }
@@ -828,13 +835,16 @@ int vqvae_bias_grad_f32(const float *grad_y, int64_t B, int HW, int C, int nchw,
     if (!grad_y || !grad_b) return VQVAE_ERR_NULL;
     if (B < 1 || HW < 1 || C < 1) return VQVAE_ERR_SHAPE;
     if (C > 256) return VQVAE_ERR_UNSUPPORTED;
+    if (((reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_b)) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return VQVAE_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < vqvae_bias_grad_workspace_bytes(C)) return VQVAE_ERR_WORKSPACE;
+    const int wide = (reinterpret_cast<uintptr_t>(grad_y) & 15) == 0;       // the four-channel path's 16-byte loads
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long P = (long long)B * HW;
     const ReducePlan p = bias_grad_plan(P);
     double *partial = static_cast<double *>(workspace);
     hipLaunchKernelGGL(bias_grad_partial_kernel, dim3((unsigned)p.splits), dim3(256), 0, st, grad_y, P, C, (long long)HW,
-                       nchw ? 1 : 0, p.per_split, partial);
+                       nchw ? 1 : 0, wide, p.per_split, partial);
     launch_colsum_final(partial, (int)p.splits, C, grad_b, st);
     return (int)hipGetLastError();
 }

@@ -165,6 +165,7 @@ extern "C" {
 int vqvae_calibration_mfma_f16(int iters, void *scratch, size_t scratch_bytes, vqvae_stream_t stream) {
     if (!scratch) return VQVAE_ERR_NULL;
     if (iters < 1) return VQVAE_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(scratch) & 7) return VQVAE_ERR_UNSUPPORTED;      // 8-byte clock counters in front of the floats
     if (scratch_bytes < vqvae_calibration_scratch_bytes()) return VQVAE_ERR_WORKSPACE;
     char *p = static_cast<char *>(scratch);
     hipLaunchKernelGGL(vqvae::calib_mfma_kernel, dim3(vqvae::kCalibBlocks), dim3(256), 0, static_cast<hipStream_t>(stream),

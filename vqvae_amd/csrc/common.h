@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/vqvae_hip.h"
 
 namespace vqvae {
@@ -147,6 +149,16 @@ inline size_t vq_filter_lds_bytes(int K, int D) {
 // vq_exact_kernel (exhaustive fp32 MFMA sweep); AnyD / GenericVector: other widths, vq_anyd_kernel / vq_generic_kernel (vq_generic.hip)
 enum class VqRoute { Track, TrackNchw, Chunk, Filter, Exact, AnyD, GenericVector, Unsupported };
 VqRoute vq_route(int K, int D, int HW, int flags);
+// The fixed-width routes (D = 32 / 64 / 128 / 256: every route but AnyD / GenericVector) move z_e, the codebook and z_q sixteen bytes
+// at a time, so vq_forward_impl refuses such a pointer that is not 16-byte aligned; the entries that call it once per stage or group
+// ask this first, before their own first launch.
+inline bool vq_needs_align16(int D) { return D == 32 || D == 64 || D == 128 || D == 256; }
+// is some pointer of the list (NULL entries pass) off a (mask + 1)-byte boundary?  The entries' test before their first launch.
+inline bool any_misaligned(uintptr_t mask, std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & mask) != 0;
+}
 
 inline VqPlan vq_plan(int K, int D) {
     VqPlan p;

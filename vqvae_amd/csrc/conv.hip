@@ -1261,6 +1261,7 @@ size_t vqvae_conv_packed_bytes(int kind, int Cin, int Cout) {
 int vqvae_conv_pack_f32(int kind, const float *w, int Cin, int Cout, float *packed, vqvae_stream_t stream) {
     if (!w || !packed) return VQVAE_ERR_NULL;
     if (Cin < 1 || Cout < 1) return VQVAE_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return VQVAE_ERR_UNSUPPORTED;      // the images are written and read 16 bytes at a time
     ConvGeom g;
     int rc = make_geom(kind, 1, 4, 4, Cin, Cout, 0, g);
     if (rc != VQVAE_OK) return rc;
@@ -1372,7 +1373,8 @@ int vqvae::conv_forward_impl(int kind, const float *x, const float *packed, cons
     }
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return VQVAE_ERR_SHAPE;
     if (Cin % 4) return VQVAE_ERR_UNSUPPORTED;          // float4 activation loads
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return VQVAE_ERR_UNSUPPORTED;   // 16-byte accesses
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(packed)) & 15)
+        return VQVAE_ERR_UNSUPPORTED;                   // 16-byte accesses (the bias is read one float at a time)
     if (B * (int64_t)H * W * 4 > (int64_t)INT32_MAX * 4 || B > INT32_MAX) return VQVAE_ERR_OVERFLOW;
     ConvGeom g;
     int rc = make_geom(kind, B, H, W, Cin, Cout, flags, g);

@@ -716,6 +716,7 @@ size_t vqvae_conv_in_packed_bytes(int Cin, int Cout) {
 int vqvae_conv_in_pack_f32(const float *w, int Cin, int Cout, float *packed, vqvae_stream_t stream) {
     if (!w || !packed) return VQVAE_ERR_NULL;
     if (vqvae_conv_in_packed_bytes(Cin, Cout) == 0) return VQVAE_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return VQVAE_ERR_UNSUPPORTED;        // the images are written 16 bytes at a time
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ntile = (Cout + 31) / 32;
     switch (Cin) {
@@ -757,6 +758,7 @@ int vqvae::conv_in_forward_impl(const float *x_nchw, const float *packed, const 
                                 int Cin, int Cout, int flags, float *y, hipStream_t stream, int *out_amax, const float *ep_mask) {
     if (!x_nchw || !packed || !y) return VQVAE_ERR_NULL;
     if (ep_mask && (ep_mask == y || (reinterpret_cast<uintptr_t>(ep_mask) & 15) || out_amax)) return VQVAE_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return VQVAE_ERR_UNSUPPORTED;        // the weight image is read 16 bytes at a time
     if (B < 1 || H < 2 || W < 2) return VQVAE_ERR_SHAPE;
     if (H % 2 || W % 2 || vqvae_conv_in_packed_bytes(Cin, Cout) == 0) return VQVAE_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -826,6 +828,7 @@ size_t vqvae_convt_out_packed_bytes(int Cin, int Cout) {
 int vqvae_convt_out_pack_f32(const float *w, int Cin, int Cout, float *packed, vqvae_stream_t stream) {
     if (!w || !packed) return VQVAE_ERR_NULL;
     if (vqvae_convt_out_packed_bytes(Cin, Cout) == 0) return VQVAE_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return VQVAE_ERR_UNSUPPORTED;        // the images are written 16 bytes at a time
     const int ntile_p = (16 * Cout + 31) / 32;
     hipLaunchKernelGGL(convt_out_pack_kernel, dim3(32), dim3(256), 0, static_cast<hipStream_t>(stream), w, packed,
                        Cin, Cout, ntile_p);
@@ -855,6 +858,8 @@ int vqvae::convt_out_forward_impl(const float *x, const float *packed, const flo
     if (!x || !packed || !y_nchw) return VQVAE_ERR_NULL;
     if (B < 1 || H < 1 || W < 1) return VQVAE_ERR_SHAPE;
     if (vqvae_convt_out_packed_bytes(Cin, Cout) == 0) return VQVAE_ERR_UNSUPPORTED;
+    // x is read with 16-byte buffer loads and the weight image 16 bytes at a time (y_nchw: the store width follows its alignment)
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) & 15) return VQVAE_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int halo_y = H > 16, halo_x = W > 16;
     const int TH = halo_y ? 14 : H, TW = halo_x ? 14 : W;

@@ -1286,6 +1286,7 @@ int vqvae::res_layer_forward_impl(const float *x, const float *packed_w1, const 
                                   int C, int Rh, int flags, float *y, hipStream_t stream, const int *in_amax, int *out_amax,
                                   float *hidden, float *hid_scratch) {
     if (!x || !packed_w1 || !packed_w2 || !y) return VQVAE_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(packed_w1) | reinterpret_cast<uintptr_t>(packed_w2)) & 15) return VQVAE_ERR_UNSUPPORTED;   // operand images
     // the hidden activation is written by the kernels that own whole 8x8 images only (full 32-wide hidden tile)
     if (hidden && (H != 8 || W != 8 || Rh != 32 || (flags & VQVAE_CONV_EXACT_FP32) || (reinterpret_cast<uintptr_t>(hidden) & 15)))
         return VQVAE_ERR_UNSUPPORTED;
@@ -1295,6 +1296,9 @@ int vqvae::res_layer_forward_impl(const float *x, const float *packed_w1, const 
         // goes through the caller's scratch (vqvae_res_layer_forward_ws_f32 / the whole-path workspace)
         if (C % 4 || Rh % 4 || !hid_scratch || hidden) return VQVAE_ERR_UNSUPPORTED;
         if (x == y) return VQVAE_ERR_UNSUPPORTED;
+        // what the two conv launches would refuse one after the other (16-byte accesses), before the first of them
+        if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(hid_scratch)) & 15)
+            return VQVAE_ERR_UNSUPPORTED;
         const int cf = flags & (VQVAE_CONV_BF16_SPLIT | VQVAE_CONV_EXACT_FP32);
         int rc = conv_forward_impl(VQVAE_CONV_3x3_S1, x, packed_w1, nullptr, B, H, W, C, Rh,
                                    (flags & VQVAE_CONV_RELU_IN) | VQVAE_CONV_RELU_OUT | cf, hid_scratch, stream, nullptr, nullptr);

@@ -197,9 +197,20 @@ size_t vqvae_weights_packed_bytes(const VqvaeDims *d) {
     return n;
 }
 
+// The device pointers inside a VqvaeWeights: the operand images and the codebook are read 16 bytes at a time (the codebook by the
+// prepare kernel, the quantizing encoder kernel and the gathering decoder kernel), a bias one float at a time.  The whole-path
+// entries ask this before their first launch.  NULL struct or fields pass: the NULL checks are the callee's.
+static bool weights_misaligned(const VqvaeWeights *w) {
+    if (!w) return false;
+    return any_misaligned(15, {w->enc0, w->enc2, w->enc4, w->enc_res_w1, w->enc_res_w2, w->pre, w->codebook, w->dec0, w->dec_res_w1,
+                               w->dec_res_w2, w->dec2, w->dec4}) ||
+           any_misaligned(3, {w->enc0_b, w->enc2_b, w->enc4_b, w->pre_b, w->dec0_b, w->dec2_b, w->dec4_b});
+}
+
 int vqvae_weights_pack_f32(const VqvaeDims *d, const VqvaeRawWeights *raw, void *packed, size_t packed_bytes,
                            VqvaeWeights *out, vqvae_stream_t stream) {
     if (!d || !raw || !packed || !out) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {packed})) return VQVAE_ERR_UNSUPPORTED;      // every layer's image is carved from it: here, not in a later layer's pack
     const size_t need = vqvae_weights_packed_bytes(d);
     if (need == 0) return VQVAE_ERR_UNSUPPORTED;
     if (packed_bytes < need) return VQVAE_ERR_WORKSPACE;
@@ -208,6 +219,11 @@ int vqvae_weights_pack_f32(const VqvaeDims *d, const VqvaeRawWeights *raw, void 
                           raw->dec_res_w2, raw->dec2_w, raw->dec2_b, raw->dec4_w, raw->dec4_b};
     for (const float *q : req)
         if (!q) return VQVAE_ERR_NULL;
+    // the codebook and the biases are not packed: the struct hands the caller's pointers on, the codebook to kernels that read it 16
+    // bytes at a time.  The weights are read one float at a time by the pack kernels.
+    if (any_misaligned(15, {raw->codebook})) return VQVAE_ERR_UNSUPPORTED;
+    for (const float *q : req)
+        if (any_misaligned(3, {q})) return VQVAE_ERR_UNSUPPORTED;
     const int h = d->h_dim, D = d->embedding_dim, Rh = d->res_h_dim;
     Carve c{static_cast<char *>(packed), packed_bytes};
     int rc;
@@ -305,6 +321,7 @@ int vqvae_resstack_f32(const float *packed_w1, const float *packed_w2, const flo
     if (!packed_w1 || !packed_w2 || !x || !y) return VQVAE_ERR_NULL;
     if (n_layers > 1 && !tmp) return VQVAE_ERR_NULL;
     if (n_layers < 1) return VQVAE_ERR_SHAPE;
+    if (any_misaligned(15, {packed_w1, packed_w2, x, y, tmp})) return VQVAE_ERR_UNSUPPORTED;      // before the first layer, not in a later one
     const float *res = nullptr;
     return res_stack(packed_w1, packed_w2, x, B, H, W, C, Rh, n_layers, flags & VQVAE_CONV_RELU_IN, flags & VQVAE_CONV_RELU_OUT,
                      y, tmp, static_cast<hipStream_t>(stream), &res);
@@ -385,6 +402,7 @@ int vqvae_encoder_ex_f32(const VqvaeWeights *w, const float *x, int64_t B, int H
                          size_t workspace_bytes, vqvae_stream_t stream) {
     const FwdPlan p = fwd_plan(w ? &w->dims : nullptr, H, W, flags);
     if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
+    if (any_misaligned(15, {x, z_e, workspace}) || weights_misaligned(w)) return VQVAE_ERR_UNSUPPORTED;         // images and maps move 16 bytes per access
     return encoder_run(w, x, B, H, W, z_e, workspace, workspace_bytes, static_cast<hipStream_t>(stream), p, nullptr);
 }
 
@@ -467,6 +485,7 @@ int vqvae_decoder_ex_f32(const VqvaeWeights *w, const float *z_q, int64_t B, int
                          size_t workspace_bytes, vqvae_stream_t stream) {
     const FwdPlan p = fwd_plan(w ? &w->dims : nullptr, 4 * h4, 4 * w4, flags);
     if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
+    if (any_misaligned(15, {z_q, x_hat, workspace}) || weights_misaligned(w)) return VQVAE_ERR_UNSUPPORTED;
     return decoder_run(w, z_q, B, h4, w4, x_hat, workspace, workspace_bytes, static_cast<hipStream_t>(stream), p, nullptr);
 }
 
@@ -518,6 +537,11 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
                       float *loss, float *perplexity, int64_t *idx, void *workspace, size_t workspace_bytes,
                       void *vq_workspace, size_t vq_workspace_bytes, vqvae_stream_t stream) {
     if (!w || !x || !x_hat || !loss || !perplexity || !workspace) return VQVAE_ERR_NULL;
+    // images, workspaces: 16 bytes per access in some kernel of every route; idx as 8-byte words; the two scalars as floats.  Here,
+    // before the codebook prepare and the encoder are launched, not where a later kernel's launch would find out
+    if (any_misaligned(15, {x, x_hat, workspace, vq_workspace}) || any_misaligned(7, {idx}) || any_misaligned(3, {loss, perplexity}) ||
+        weights_misaligned(w))
+        return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     FwdWs f;
     {
@@ -593,6 +617,7 @@ int vqvae_forward_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, i
 int vqvae_encode_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, int W, int vq_flags, int64_t *idx, void *workspace,
                      size_t workspace_bytes, void *vq_workspace, size_t vq_workspace_bytes, vqvae_stream_t stream) {
     if (!w || !x || !idx || !workspace) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {x, workspace, vq_workspace}) || any_misaligned(7, {idx}) || weights_misaligned(w)) return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     FwdWs f;
     {
@@ -625,6 +650,7 @@ int vqvae_encode_f32(const VqvaeWeights *w, const float *x, int64_t B, int H, in
 int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h4, int w4, int flags, float *x_hat, void *workspace,
                      size_t workspace_bytes, vqvae_stream_t stream) {
     if (!w || !idx || !x_hat || !workspace) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {x_hat, workspace}) || any_misaligned(7, {idx}) || weights_misaligned(w)) return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     const FwdPlan p = fwd_plan(d, 4 * h4, 4 * w4, flags);
     if (p.cf < 0 || (flags & ~(VQVAE_FWD_CONV_BF16_SPLIT | VQVAE_FWD_CONV_EXACT_FP32))) return VQVAE_ERR_UNSUPPORTED;
@@ -664,6 +690,7 @@ int vqvae_decode_f32(const VqvaeWeights *w, const int64_t *idx, int64_t B, int h
 int vqvae_forward_begin_f32(const VqvaeWeights *w, int64_t B, int H, int W, int vq_flags, void *workspace, size_t workspace_bytes,
                             void *vq_workspace, size_t vq_workspace_bytes, vqvae_stream_t stream) {
     if (!w || !workspace) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {workspace, vq_workspace}) || weights_misaligned(w)) return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     FwdWs f;
     int rc = carve_forward(d, B, H, W, workspace, workspace_bytes, vq_workspace, vq_workspace_bytes, vq_flags, f);
@@ -683,6 +710,8 @@ int vqvae_forward_part_f32(const VqvaeWeights *w, const float *x, int64_t B, int
                            float *x_hat, int64_t *idx, void *workspace, size_t workspace_bytes, void *vq_workspace,
                            size_t vq_workspace_bytes, vqvae_stream_t stream) {
     if (!w || !x || !x_hat || !workspace) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {x, x_hat, workspace, vq_workspace}) || any_misaligned(7, {idx}) || weights_misaligned(w))
+        return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     // whole 64-image blocks per part (the last part takes what is left): the parts' slices of the maxima region stay aligned
     if (B < 1 || b0 < 0 || Bc < 1 || b0 + Bc > B || b0 % 64 || (b0 + Bc < B && Bc % 64)) return VQVAE_ERR_SHAPE;
@@ -741,6 +770,7 @@ int vqvae_forward_abort_f32(void *workspace) {
 int vqvae_forward_end_f32(const VqvaeWeights *w, int64_t B, int H, int W, float *loss, float *perplexity, void *workspace,
                           size_t workspace_bytes, vqvae_stream_t stream) {
     if (!w || !loss || !perplexity || !workspace) return VQVAE_ERR_NULL;
+    if (any_misaligned(15, {workspace}) || any_misaligned(3, {loss, perplexity})) return VQVAE_ERR_UNSUPPORTED;
     const VqvaeDims *d = &w->dims;
     FwdWs f;
     int flags = 0;

@@ -520,6 +520,7 @@ int vqvae_conv_taps_pack_dgrad_f32(const float *w, int wtaps, int t0, int ntaps,
     if (!w || !dy || !dx || !packed) return VQVAE_ERR_NULL;
     if (Cin < 1 || Cout < 1 || ntaps < 1 || wtaps < 1 || t0 < 0 || t0 + ntaps > wtaps) return VQVAE_ERR_SHAPE;
     if (ntaps > 16 || Cin % 4 || Cout % 4) return VQVAE_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return VQVAE_ERR_UNSUPPORTED;        // (before the staging launch, not behind it)
     int8_t ndy[16], ndx[16];
     for (int i = 0; i < ntaps; ++i) {
         if (dy[i] < -7 || dy[i] > 7 || dx[i] < -7 || dx[i] > 7) return VQVAE_ERR_UNSUPPORTED;

@@ -626,6 +626,14 @@ int vqvae::vq_forward_impl(const float *z_e, const float *codebook, int64_t B, i
     const int HW = H * W;
     const VqRoute route = vq_route(K, D, HW, flags);
     if (route == VqRoute::Unsupported) return VQVAE_ERR_UNSUPPORTED;
+    // the fixed-width routes read z_e and the codebook and write z_q sixteen bytes at a time (the any-width kernels of
+    // vq_generic.hip pick their element-wise forms by the pointers themselves); idx is written as 8-byte words
+    if (vq_needs_align16(D) &&
+        ((reinterpret_cast<uintptr_t>(z_e) | reinterpret_cast<uintptr_t>(codebook) | reinterpret_cast<uintptr_t>(z_q)) & 15))
+        return VQVAE_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(idx) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||     // (the workspace's images)
+        ((reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(perplexity)) & 3))
+        return VQVAE_ERR_UNSUPPORTED;
     const size_t need = vqvae_vq_workspace_bytes(N, K, D);
     if (!workspace || workspace_bytes < need) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);

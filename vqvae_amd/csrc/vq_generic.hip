@@ -666,7 +666,9 @@ int launch_vq_generic(const float *z, const float *cb, long long N, int HW, int 
     long long grid = ntiles < 8LL * num_cus() ? ntiles : 8LL * num_cus();     // (latency-bound tiles: eight workgroups per CU)
     if (grid > kGenMaxGrid) grid = kGenMaxGrid;
     const size_t lds = (size_t)kGenRows * ((D + 3) & ~3) * sizeof(float) + (size_t)K * sizeof(int);
-    const bool vec4 = D % 4 == 0 && (reinterpret_cast<uintptr_t>(cb) & 15) == 0;
+    // VEC4 reads the codebook rows 16 bytes at a time and, on row-major rows, z_e too (NCHW maps go through an LDS tile one float at a
+    // time); both forms add in the same order
+    const bool vec4 = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(rowmajor ? z : nullptr)) & 15) == 0;
     prof_begin(VQVAE_PROF_VQ_MAIN, st);
 #define GEN_LAUNCH(NCHW_, VEC4_)                                                                                                    \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(vq_generic_kernel<NCHW_, VEC4_>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes - 4096); \

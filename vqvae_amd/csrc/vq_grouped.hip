@@ -129,12 +129,6 @@ struct GrpSpan {                          // a tensor as the bytes it covers (p 
     size_t bytes;
 };
 
-static bool grp_misaligned(std::initializer_list<const void *> ptrs, uintptr_t mask) {
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);           // (NULL contributes nothing)
-    return (bits & mask) != 0;
-}
-
 static bool grp_overlap(const GrpSpan &a, const GrpSpan &b) {
     if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
@@ -176,7 +170,7 @@ static int grp_books(const float *const *codebooks, int G, GrpBooks &books) {
 
 // may a launch move 16 bytes per access?  `ptrs`: every tensor it touches that way
 static bool grp_vec4(const GrpArgs &a, std::initializer_list<const void *> ptrs) {
-    if (grp_misaligned(ptrs, 15)) return false;
+    if (any_misaligned(15, ptrs)) return false;
     return a.rowmajor ? (a.d & 3) == 0 : (a.HW & 3) == 0;
 }
 
@@ -262,7 +256,13 @@ int vqvae_vq_grouped_forward_f32(const float *z_e, const float *const *codebooks
     GrpPlan p;
     if (!grp_plan(N, K, D, G, p)) return VQVAE_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
-    if (grp_misaligned({z_e, z_q, hist, loss_group, perplexity_group, loss, slabs_out}, 3) || grp_misaligned({idx, workspace}, 7))
+    // the per-group quantizer reads a codebook sixteen bytes at a time at the fixed slab widths (the slabs themselves lie aligned
+    // in the workspace): refused here, before the split kernel, not by the quantizer of some later group
+    if (vq_needs_align16(D / G))
+        for (int g = 0; g < G; ++g)
+            if (reinterpret_cast<uintptr_t>(books.cb[g]) & 15) return VQVAE_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return VQVAE_ERR_UNSUPPORTED;      // (the groups' quantizer workspaces and slabs)
+    if (any_misaligned(3, {z_e, z_q, hist, loss_group, perplexity_group, loss, slabs_out}) || any_misaligned(7, {idx, workspace}))
         return VQVAE_ERR_UNSUPPORTED;
     const int d = D / G;
     const size_t map_bytes = (size_t)N * D * sizeof(float), book_bytes = (size_t)K * d * sizeof(float);
@@ -278,7 +278,7 @@ int vqvae_vq_grouped_forward_f32(const float *z_e, const float *const *codebooks
     // The quantizers read the caller's slabs where those are 16-byte aligned, as every slab in the workspace is (a slab is a multiple
     // of 16 bytes wherever a layout allows 16-byte accesses); a less aligned slabs_out gets a second copy.
     float *ws_slabs = reinterpret_cast<float *>(ws + p.off_slabs);
-    const bool direct = slabs_out && !grp_misaligned({slabs_out}, 15);
+    const bool direct = slabs_out && !any_misaligned(15, {slabs_out});
     float *slabs = direct ? slabs_out : ws_slabs;
     grp_launch_split(base, z_e, 0, G, slabs, (slabs_out && !direct) ? slabs_out : nullptr, st);
     for (int g = 0; g < G; ++g) {
@@ -310,7 +310,7 @@ int vqvae_vq_grouped_decode_f32(const int64_t *idx, const float *const *codebook
     GrpBooks books;
     const int rcb = grp_books(codebooks, G, books);
     if (rcb != VQVAE_OK) return rcb;
-    if (grp_misaligned({z_q}, 3) || grp_misaligned({idx}, 7)) return VQVAE_ERR_UNSUPPORTED;
+    if (any_misaligned(3, {z_q}) || any_misaligned(7, {idx})) return VQVAE_ERR_UNSUPPORTED;
     if (grp_any_overlap({GrpSpan{z_q, (size_t)N * D * sizeof(float)}}, {GrpSpan{idx, (size_t)G * N * sizeof(int64_t)}}, books, nullptr, G,
                         (size_t)K * (D / G) * sizeof(float)))
         return VQVAE_ERR_UNSUPPORTED;
@@ -348,7 +348,7 @@ int vqvae_vq_grouped_backward_f32(const float *z_e, const float *const *codebook
     GrpBwdPlan p;
     if (!grp_bwd_plan(N, K, D, G, p)) return VQVAE_ERR_UNSUPPORTED;
     if (grad_codebooks && (!workspace || workspace_bytes < p.total)) return VQVAE_ERR_WORKSPACE;
-    if (grp_misaligned({z_e, grad_zq, grad_loss, grad_z}, 3) || grp_misaligned({idx, grad_codebooks ? workspace : nullptr}, 7))
+    if (any_misaligned(3, {z_e, grad_zq, grad_loss, grad_z}) || any_misaligned(7, {idx, grad_codebooks ? workspace : nullptr}))
         return VQVAE_ERR_UNSUPPORTED;
     const int d = D / G;
     const size_t map_bytes = (size_t)N * D * sizeof(float);

@@ -123,15 +123,9 @@ static int rvq_check(int64_t B, int D, int H, int W, int K, int Q, long long &HW
     return VQVAE_OK;
 }
 
-static bool rvq_aligned16(std::initializer_list<const void *> ptrs) {
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);           // (NULL contributes nothing)
-    return (bits & 15) == 0;
-}
-
 // may this launch move 16 bytes per access?  `ptrs`: every tensor the kernel touches with such an access, codebooks included
 static bool rvq_vec4(const RvqArgs &a, const RvqBooks &books, std::initializer_list<const void *> ptrs) {
-    if (!rvq_aligned16(ptrs)) return false;
+    if (any_misaligned(15, ptrs)) return false;
     if (!a.rowmajor) return (a.HW & 3) == 0;                                      // (the codebooks are read element by element)
     if (a.D & 3) return false;
     for (int q = a.q0; q < a.q1; ++q)
@@ -203,6 +197,13 @@ int vqvae_vq_residual_forward_f32(const float *z_e, const float *const *codebook
     if (!rvq_books(codebooks, Q, shared, books)) return VQVAE_ERR_NULL;
     RvqPlan p;
     if (!rvq_plan(N, K, D, Q, shared, p)) return VQVAE_ERR_UNSUPPORTED;
+    // what the per-stage quantizer would refuse (16-byte accesses on z_e and the codebooks at the fixed widths), before stage 0 runs
+    if (vq_needs_align16(D)) {
+        if (any_misaligned(15, {z_e})) return VQVAE_ERR_UNSUPPORTED;
+        for (int q = 0; q < Q; ++q)
+            if (any_misaligned(15, {books.cb[q]})) return VQVAE_ERR_UNSUPPORTED;
+    }
+    if ((reinterpret_cast<uintptr_t>(idx) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return VQVAE_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < p.total) return VQVAE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);

@@ -68,8 +68,8 @@ def vq_forward(z_e: torch.Tensor, codebook: torch.Tensor, beta: float, *, rowmaj
     if Dc != D:
         # the reference silently mis-reshapes here (view(-1, e_dim), quantizer.py:46); be strict
         raise ValueError(f"channel dim {D} != embedding dim {Dc}")
-    z_e = z_e.contiguous()
-    codebook = codebook.contiguous()
+    z_e = _lib.dense(z_e, _lib.vq_align(D))
+    codebook = _lib.dense(codebook, _lib.vq_align(D))
     dev = z_e.device
     with torch.cuda.device(dev):
         if workspace is None:
@@ -95,7 +95,7 @@ def vq_forward(z_e: torch.Tensor, codebook: torch.Tensor, beta: float, *, rowmaj
 def vq_onehot(idx: torch.Tensor, K: int) -> torch.Tensor:
     """min_encodings (N,K) fp32 (models/quantizer.py:55-57)."""
     _check_dev("idx", idx, torch.int64)
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, 8)
     N = idx.numel()
     out = torch.empty((N, K), dtype=torch.float32, device=idx.device)
     with torch.cuda.device(idx.device):
@@ -108,8 +108,8 @@ def vq_decode_indices(idx: torch.Tensor, codebook: torch.Tensor, B: int, H: int,
     quantizer; the kernel never reads outside the codebook, a bad index shows as NaN rows)."""
     _check_dev("idx", idx, torch.int64)
     _check_dev("codebook", codebook)
-    idx = idx.contiguous()
-    codebook = codebook.contiguous()
+    idx = _lib.dense(idx, 8)
+    codebook = _lib.dense(codebook, 4)
     K, D = codebook.shape
     if idx.numel() != B * H * W:
         raise ValueError("idx must hold B*H*W indices")
@@ -138,14 +138,13 @@ def vq_ema_update(z_e: torch.Tensor, idx: torch.Tensor, ema_cluster_size: torch.
                   uniforms: torch.Tensor | None = None, rowmajor: bool = False, workspace: torch.Tensor | None = None):
     """One EMA codebook update (arXiv 1711.00937 Appendix A.1; vqvae_vq_ema_update_f32) from the rows z_e and the indices the
     forward assigned them.  Writes ema_cluster_size (K,), ema_w (K, D) and codebook (K, D) in place through their data pointers
-    (no autograd version bump: the caller owns that).  threshold / uniforms: restart codes whose averaged count is below
+    (no autograd version bump: the caller owns that; a strided one is computed in a dense temporary and copied back
+    with copy_).  threshold / uniforms: restart codes whose averaged count is below
     threshold on the rows floor(u_k N) of z_e; both or neither.  z_e: (B,D,H,W), or (B,H,W,D) when rowmajor."""
     _check_dev("z_e", z_e)
     _check_dev("idx", idx, torch.int64)
     for name, t in (("ema_cluster_size", ema_cluster_size), ("ema_w", ema_w), ("codebook", codebook)):
         _check_dev(name, t)
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous (it is written in place)")
     if z_e.dim() != 4:
         raise ValueError("z_e must be 4-D")
     B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
@@ -156,19 +155,19 @@ def vq_ema_update(z_e: torch.Tensor, idx: torch.Tensor, ema_cluster_size: torch.
         raise ValueError("restart needs both threshold and uniforms")
     if uniforms is not None:
         _check_dev("uniforms", uniforms)
-        uniforms = uniforms.contiguous()
+        uniforms = _lib.dense(uniforms, 4)
         if uniforms.numel() != K:
             raise ValueError("uniforms must hold K values")
-    z_e = z_e.contiguous()
-    idx = idx.contiguous()
+    z_e = _lib.dense(z_e, 4)
+    idx = _lib.dense(idx, 8)
     dev = z_e.device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), _lib.written(ema_cluster_size, 4) as cs, _lib.written(ema_w, 4) as ew, _lib.written(codebook, 4) as cb:
         if workspace is None:
             workspace = vq_ema_workspace(B * H * W, K, D, dev)
         _lib.check(_lib.load().vqvae_vq_ema_update_f32(
             z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, float(decay), float(eps),
             float(threshold) if threshold is not None else -1.0, uniforms.data_ptr() if uniforms is not None else None,
-            VQ_ROWMAJOR if rowmajor else 0, ema_cluster_size.data_ptr(), ema_w.data_ptr(), codebook.data_ptr(),
+            VQ_ROWMAJOR if rowmajor else 0, cs.data_ptr(), ew.data_ptr(), cb.data_ptr(),
             workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
     return codebook
 
@@ -196,25 +195,26 @@ def vq_ema_stats(z_e: torch.Tensor, idx: torch.Tensor, K: int, *, row_uniforms: 
         raise ValueError("idx must hold one index per row of z_e")
     if row_uniforms is not None:
         _check_dev("row_uniforms", row_uniforms)
-        row_uniforms = row_uniforms.contiguous()
+        row_uniforms = _lib.dense(row_uniforms, 4)
         if row_uniforms.numel() != K:
             raise ValueError("row_uniforms must hold K values")
     C = D + 1 if row_uniforms is None else 2 * D + 1
     dev = z_e.device
     if out is not None:
         _check_dev("out", out, torch.float64)
-        if out.shape != (K, C) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous ({K}, {C}) tensor")
-    z_e = z_e.contiguous()
-    idx = idx.contiguous()
+        if out.shape != (K, C):
+            raise ValueError(f"out must be a ({K}, {C}) tensor")
+    z_e = _lib.dense(z_e, 4)
+    idx = _lib.dense(idx, 8)
     with torch.cuda.device(dev):
         if workspace is None:
             workspace = vq_ema_stats_workspace(B * H * W, K, D, dev)
         if out is None:
             out = torch.empty((K, C), dtype=torch.float64, device=dev)
-        _lib.check(_lib.load().vqvae_vq_ema_stats_f32(
-            z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, row_uniforms.data_ptr() if row_uniforms is not None else None,
-            VQ_ROWMAJOR if rowmajor else 0, out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
+        with _lib.written(out, 8) as o:
+            _lib.check(_lib.load().vqvae_vq_ema_stats_f32(
+                z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, row_uniforms.data_ptr() if row_uniforms is not None else None,
+                VQ_ROWMAJOR if rowmajor else 0, o.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(z_e)))
     return out
 
 
@@ -242,8 +242,6 @@ def vq_ema_apply(stats, ema_cluster_size: torch.Tensor, ema_w: torch.Tensor, cod
     _check_dev("stats", stats, torch.float64)
     for name, t in (("ema_cluster_size", ema_cluster_size), ("ema_w", ema_w), ("codebook", codebook)):
         _check_dev(name, t)
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous (it is written in place)")
     if stats.dim() != 3:
         raise ValueError("stats must be (R, K, C)")
     R, K, C = stats.shape
@@ -256,20 +254,20 @@ def vq_ema_apply(stats, ema_cluster_size: torch.Tensor, ema_w: torch.Tensor, cod
         raise ValueError("restart needs both threshold and shard_uniforms")
     if shard_uniforms is not None:
         _check_dev("shard_uniforms", shard_uniforms)
-        shard_uniforms = shard_uniforms.contiguous()
+        shard_uniforms = _lib.dense(shard_uniforms, 4)
         if shard_uniforms.numel() != K:
             raise ValueError("shard_uniforms must hold K values")
         if C != 2 * D + 1:
             raise ValueError("restart needs statistics taken with row_uniforms (C = 2 D + 1)")
-    stats = stats.contiguous()
+    stats = _lib.dense(stats, 8)
     dev = stats.device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), _lib.written(ema_cluster_size, 4) as cs, _lib.written(ema_w, 4) as ew, _lib.written(codebook, 4) as cb:
         if workspace is None:
             workspace = vq_ema_apply_workspace(R, K, D, dev)
         _lib.check(_lib.load().vqvae_vq_ema_apply_f32(
             stats.data_ptr(), R, K, D, C, float(decay), float(eps), float(threshold) if threshold is not None else -1.0,
-            shard_uniforms.data_ptr() if shard_uniforms is not None else None, ema_cluster_size.data_ptr(), ema_w.data_ptr(),
-            codebook.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(stats)))
+            shard_uniforms.data_ptr() if shard_uniforms is not None else None, cs.data_ptr(), ew.data_ptr(),
+            cb.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream_ptr(stats)))
     return codebook
 
 
@@ -296,10 +294,10 @@ def vq_kmeans_seed(z_e: torch.Tensor, K: int, uniforms: torch.Tensor, *, rowmajo
     rowmajor.  The numeric contract is the header of csrc/vq_kmeans.hip."""
     B, H, W, D = _kmeans_rows(z_e, rowmajor)
     _check_dev("uniforms", uniforms)
-    uniforms = uniforms.contiguous()
+    uniforms = _lib.dense(uniforms, 4)
     if uniforms.numel() != K:
         raise ValueError("uniforms must hold K values")
-    z_e = z_e.contiguous()
+    z_e = _lib.dense(z_e, 4)
     dev = z_e.device
     with torch.cuda.device(dev):
         if workspace is None:
@@ -321,26 +319,24 @@ def vq_kmeans_update(z_e: torch.Tensor, idx: torch.Tensor, codebook: torch.Tenso
     B, H, W, D = _kmeans_rows(z_e, rowmajor)
     _check_dev("idx", idx, torch.int64)
     _check_dev("codebook", codebook)
-    if not codebook.is_contiguous():
-        raise ValueError("codebook must be contiguous (it is written in place)")
     K = codebook.shape[0]
     if codebook.shape != (K, D) or idx.numel() != B * H * W:
         raise ValueError("shape mismatch between z_e, idx and codebook")
     if uniforms is not None:
         _check_dev("uniforms", uniforms)
-        uniforms = uniforms.contiguous()
+        uniforms = _lib.dense(uniforms, 4)
         if uniforms.numel() != K:
             raise ValueError("uniforms must hold K values")
-    z_e = z_e.contiguous()
-    idx = idx.contiguous()
+    z_e = _lib.dense(z_e, 4)
+    idx = _lib.dense(idx, 8)
     dev = z_e.device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), _lib.written(codebook, 4) as cb:
         if workspace is None:
             workspace = vq_kmeans_workspace(B * H * W, K, D, dev)
         counts = torch.empty((K,), dtype=torch.int32, device=dev)
         _lib.check(_lib.load().vqvae_vq_kmeans_update_f32(
             z_e.data_ptr(), idx.data_ptr(), B, D, H, W, K, uniforms.data_ptr() if uniforms is not None else None,
-            VQ_ROWMAJOR if rowmajor else 0, codebook.data_ptr(), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            VQ_ROWMAJOR if rowmajor else 0, cb.data_ptr(), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
             _stream_ptr(z_e)))
     return counts
 
@@ -355,7 +351,7 @@ def vq_kmeans(z_e: torch.Tensor, K: int, iters: int = 10, *, generator: torch.Ge
     B, H, W, D = _kmeans_rows(z_e, rowmajor)
     if iters < 0:
         raise ValueError("iters must be >= 0")
-    z_e = z_e.contiguous()
+    z_e = _lib.dense(z_e, _lib.vq_align(D))            # (the rows go to the quantizer every round)
     dev = z_e.device
     with torch.cuda.device(dev):
         ws = vq_kmeans_workspace(B * H * W, K, D, dev)
@@ -390,7 +386,7 @@ def l2norm_rows(x: torch.Tensor, *, rowmajor: bool = False, eps: float = 1e-12):
     -> (y like x, denom (N,) fp32 = max(||row||, eps)).  x: (B,D,H,W), (B,H,W,D) when rowmajor, or a 2-D (K, D) tensor -- a codebook,
     rows as they stand.  The numeric contract is the header of csrc/vq_cosine.hip."""
     B, D, H, W, rm = _l2norm_dims("x", x, rowmajor)
-    x = x.contiguous()
+    x = _lib.dense(x, 4)
     dev = x.device
     with torch.cuda.device(dev):
         y = torch.empty_like(x)
@@ -409,7 +405,7 @@ def l2norm_rows_backward(y: torch.Tensor, denom: torch.Tensor, grad_y: torch.Ten
     _check_dev("grad_y", grad_y)
     if grad_y.shape != y.shape or denom.numel() != B * H * W:
         raise ValueError("shape mismatch between y, denom and grad_y")
-    y, denom, grad_y = y.contiguous(), denom.contiguous(), grad_y.contiguous()
+    y, denom, grad_y = _lib.dense(y, 4), _lib.dense(denom, 4), _lib.dense(grad_y, 4)
     with torch.cuda.device(y.device):
         grad_x = torch.empty_like(y)
         _lib.check(_lib.load().vqvae_l2norm_backward_f32(y.data_ptr(), denom.data_ptr(), grad_y.data_ptr(), B, D, H, W, float(eps),
@@ -427,7 +423,7 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def _residual_books(codebooks, shared):
+def _residual_books(codebooks, shared, align=4):
     """-> (contiguous (K, D) codebooks, one per distinct codebook; stage count, None when only the caller knows it)"""
     if isinstance(codebooks, torch.Tensor):
         codebooks = [codebooks] if codebooks.dim() == 2 else list(codebooks.unbind(0))
@@ -441,7 +437,7 @@ def _residual_books(codebooks, shared):
     n = len(books)
     if shared:                                    # one codebook and n_q, or the same codebook listed once per stage
         books = books[:1]
-    return [c.contiguous() for c in books], (None if shared and n == 1 else n)
+    return [_lib.dense(c, align) for c in books], (None if shared and n == 1 else n)
 
 
 def vq_residual_workspace(N: int, K: int, D: int, Q: int, device, *, shared: bool = False) -> torch.Tensor:
@@ -466,7 +462,7 @@ def vq_residual_forward(z_e: torch.Tensor, codebooks, beta: float, *, rowmajor: 
     _check_dev("z_e", z_e)
     if z_e.dim() != 4:
         raise ValueError("z_e must be 4-D")
-    books, Q = _residual_books(codebooks, shared)
+    books, Q = _residual_books(codebooks, shared, _lib.vq_align(z_e.shape[3 if rowmajor else 1]))     # (the stages' quantizer)
     if Q is None:
         Q = 1 if n_q is None else int(n_q)
     elif n_q is not None and n_q != Q:
@@ -475,7 +471,7 @@ def vq_residual_forward(z_e: torch.Tensor, codebooks, beta: float, *, rowmajor: 
     K, Dc = books[0].shape
     if Dc != D:
         raise ValueError(f"channel dim {D} != embedding dim {Dc}")
-    z_e = z_e.contiguous()
+    z_e = _lib.dense(z_e, _lib.vq_align(D))
     dev = z_e.device
     N = B * H * W
     with torch.cuda.device(dev):
@@ -511,7 +507,7 @@ def vq_residual_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, 
     Q = idx.numel() // N
     if nb is not None and Q != nb:
         raise ValueError(f"{Q} stages of indices for {nb} codebooks")
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, 8)
     if validate and not torch.cuda.is_current_stream_capturing():
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= K:
@@ -527,7 +523,7 @@ def vq_residual_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, 
 
 # ---- grouped (product) vector quantization (csrc/vq_grouped.hip) -----------------------------------------------------------------
 
-def _grouped_books(codebooks):
+def _grouped_books(codebooks, align=4):
     """-> contiguous (K, d) codebooks, one per group"""
     if isinstance(codebooks, torch.Tensor):
         codebooks = [codebooks] if codebooks.dim() == 2 else list(codebooks.unbind(0))
@@ -538,7 +534,7 @@ def _grouped_books(codebooks):
         _check_dev(f"codebooks[{i}]", c)
         if c.dim() != 2 or c.shape != books[0].shape:
             raise ValueError("every codebook must be (K, d) with the same K and d")
-    return [c.contiguous() for c in books]
+    return [_lib.dense(c, align) for c in books]
 
 
 def vq_grouped_workspace(N: int, K: int, D: int, G: int, device) -> torch.Tensor:
@@ -568,7 +564,8 @@ def vq_grouped_forward(z_e: torch.Tensor, codebooks, beta: float, *, rowmajor: b
     K, d = books[0].shape
     if d * G != D:
         raise ValueError(f"channel dim {D} != {G} groups of embedding dim {d}")
-    z_e = z_e.contiguous()
+    books = [_lib.dense(c, _lib.vq_align(d)) for c in books]                 # (the groups' quantizer reads the codebooks)
+    z_e = _lib.dense(z_e, 4)
     dev = z_e.device
     N = B * H * W
     with torch.cuda.device(dev):
@@ -602,7 +599,7 @@ def vq_grouped_decode(idx: torch.Tensor, codebooks, B: int, H: int, W: int, *, r
     N = B * H * W
     if idx.numel() != G * N:
         raise ValueError(f"idx must hold G*B*H*W = {G * N} indices, group-major")
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, 8)
     if validate and not torch.cuda.is_current_stream_capturing():
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= K:
@@ -638,7 +635,7 @@ def _fsq_params(D, d, **params):
         _check_dev(name, t)
         if tuple(t.shape) != shapes[name]:
             raise ValueError(f"{name} must be {shapes[name]}, got {tuple(t.shape)}")
-        out.append(t.contiguous())
+        out.append(_lib.dense(t, 4))
     return out
 
 
@@ -655,7 +652,7 @@ def fsq_forward(z_e: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, w_out
     B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     lv, c_lv, K = _fsq_levels(levels)
     w_in, b_in, w_out, b_out = _fsq_params(D, len(lv), w_in=w_in, b_in=b_in, w_out=w_out, b_out=b_out)
-    z_e = z_e.contiguous()
+    z_e = _lib.dense(z_e, 4)
     dev = z_e.device
     with torch.cuda.device(dev):
         z_q = torch.empty_like(z_e) if want_zq else None
@@ -683,7 +680,7 @@ def fsq_decode_indices(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tens
     w_out, b_out = _fsq_params(D, len(lv), w_out=w_out, b_out=b_out)
     if idx.numel() != B * H * W:
         raise ValueError("idx must hold B*H*W indices")
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, 8)
     if validate and not torch.cuda.is_current_stream_capturing():
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= K:
@@ -738,7 +735,7 @@ def lfq_forward(z_e: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, w_out
     B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     d = _lfq_bits(n_e)
     w_in, b_in, w_out, b_out = _fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out, b_out=b_out)
-    z_e = z_e.contiguous()
+    z_e = _lib.dense(z_e, 4)
     dev = z_e.device
     with torch.cuda.device(dev):
         z_q = torch.empty_like(z_e) if want_zq else None
@@ -773,7 +770,7 @@ def lfq_decode_indices(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tens
     w_out, b_out = _fsq_params(D, d, w_out=w_out, b_out=b_out)
     if idx.numel() != B * H * W:
         raise ValueError("idx must hold B*H*W indices")
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, 8)
     if validate and not torch.cuda.is_current_stream_capturing():
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= n_e:
@@ -797,7 +794,7 @@ def _linear_weight(w, Cin=None):
     _check_dev("w", w)
     if w.dim() != 2 or (Cin is not None and w.shape[1] != Cin):
         raise ValueError(f"w must be (Cout, Cin = {Cin}) as nn.Linear holds it, got {tuple(w.shape)}")
-    return w.contiguous()
+    return _lib.dense(w, 4)
 
 
 def _linear_like(x, C, rm):
@@ -821,7 +818,7 @@ def linear_rows(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, rowmajor: 
     Cout = w.shape[0]
     if tuple(b.shape) != (Cout,):
         raise ValueError(f"b must be ({Cout},), got {tuple(b.shape)}")
-    x, b = x.contiguous(), b.contiguous()
+    x, b = _lib.dense(x, 4), _lib.dense(b, 4)
     with torch.cuda.device(x.device):
         y = _linear_like(x, Cout, rm)
         _lib.check(_lib.load().vqvae_linear_rows_forward_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), B, Cin, H, W, Cout,
@@ -847,7 +844,7 @@ def linear_rows_backward(x: torch.Tensor, grad_y: torch.Tensor, w: torch.Tensor,
     w = _linear_weight(w, Cin)
     Cout = w.shape[0]
     _check_dev("grad_y", grad_y)
-    x, grad_y = x.contiguous(), grad_y.contiguous()
+    x, grad_y = _lib.dense(x, 4), _lib.dense(grad_y, 4)
     y_shape = (x.shape[0], Cout) if x.dim() == 2 else ((*x.shape[:3], Cout) if rm else (x.shape[0], Cout, *x.shape[2:]))
     if tuple(grad_y.shape) != y_shape:
         raise ValueError(f"grad_y must have y's shape {y_shape}, got {tuple(grad_y.shape)}")
@@ -894,15 +891,15 @@ def vq_orthogonal_forward(rows: torch.Tensor, hist: torch.Tensor | None = None, 
         _check_dev("hist", hist, torch.int32)
         if hist.shape != (K,):
             raise ValueError("hist must be (K,)")
-        hist = hist.contiguous()
+        hist = _lib.dense(hist, 4)
     if max_codes is not None and uniforms is None:
         raise ValueError("max_codes needs uniforms: one value in [0, 1) per code")
     if uniforms is not None:
         _check_dev("uniforms", uniforms)
         if uniforms.shape != (K,):
             raise ValueError("uniforms must be (K,)")
-        uniforms = uniforms.contiguous()
-    rows = rows.contiguous()
+        uniforms = _lib.dense(uniforms, 4)
+    rows = _lib.dense(rows, 4)
     dev = rows.device
     with torch.cuda.device(dev):
         ws = workspace if workspace is not None else vq_orthogonal_workspace(K, D, dev)
@@ -933,8 +930,8 @@ def vq_orthogonal_backward(saved: torch.Tensor, selected: torch.Tensor, count: t
         _check_dev("grad_loss", grad_loss)
         if grad_loss.numel() != 1:
             raise ValueError("grad_loss must be a scalar")
-        grad_loss = grad_loss.contiguous()
-    saved, selected = saved.contiguous(), selected.contiguous()
+        grad_loss = _lib.dense(grad_loss, 4)
+    saved, selected = _lib.dense(saved, 8), _lib.dense(selected, 4)
     with torch.cuda.device(saved.device):
         grad_rows = torch.empty((K, D), dtype=torch.float32, device=saved.device)
         _lib.check(_lib.load().vqvae_vq_orthogonal_backward_f32(
@@ -972,7 +969,7 @@ def vq_entropy_forward(z: torch.Tensor, codebook: torch.Tensor, *, inv_temperatu
     log-sum-exp and entropy for vq_entropy_backward, or None without want_saved).  No (N, K) array, no host sync.  The numeric
     contract is the header of csrc/vq_entropy.hip."""
     B, H, W, D, K = _vq_entropy_dims(z, codebook, rowmajor)
-    z, codebook = z.contiguous(), codebook.contiguous()
+    z, codebook = _lib.dense(z, 4), _lib.dense(codebook, 4)
     dev, N = z.device, B * H * W
     with torch.cuda.device(dev):
         ws = workspace if workspace is not None else vq_entropy_workspace(N, K, D, dev)
@@ -1004,8 +1001,8 @@ def vq_entropy_backward(z: torch.Tensor, codebook: torch.Tensor, avg: torch.Tens
         _check_dev("grad_loss", grad_loss)
         if grad_loss.numel() != 1:
             raise ValueError("grad_loss must be a scalar")
-        grad_loss = grad_loss.contiguous()
-    z, codebook, avg, rowstat = z.contiguous(), codebook.contiguous(), avg.contiguous(), rowstat.contiguous()
+        grad_loss = _lib.dense(grad_loss, 4)
+    z, codebook, avg, rowstat = _lib.dense(z, 4), _lib.dense(codebook, 4), _lib.dense(avg, 8), _lib.dense(rowstat, 8)
     dev = z.device
     with torch.cuda.device(dev):
         ws = workspace if workspace is not None else vq_entropy_workspace(N, K, D, dev)

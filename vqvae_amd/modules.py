@@ -1355,7 +1355,7 @@ class VQVAE(nn.Module):
         nbytes = L.vqvae_weights_packed_bytes(dims)
         if nbytes == 0:
             raise VqvaeHipError("model dimensions not supported by the gfx950 whole-path entry points")
-        keep = {f: t.detach().contiguous() for f, t in tensors.items()}
+        keep = {f: _lib.dense(t.detach()) for f, t in tensors.items()}
         raw = _lib.VqvaeRawWeights(**{f: t.data_ptr() for f, t in keep.items()})
         packed = torch.empty(nbytes, dtype=torch.uint8, device=w0.device)
         cw = _lib.VqvaeWeights()
@@ -1463,7 +1463,7 @@ class VQVAE(nn.Module):
         what vqvae_weights_range_check_f32 recommends for this checkpoint (scheme_hint())."""
         from . import _lib
         L = _lib.load()
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, Cin, H, W = x.shape
         cw, _keep = self._c_weights()
         if fwd_flags is None:
@@ -1651,7 +1651,7 @@ class VQVAE(nn.Module):
             _, _, _, idx, _ = VectorQuantizer.quantize(self.vector_quantization, z_e, rowmajor=True, want_zq=False)
             return idx
         L = _lib.load()
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, Cin, H, W = x.shape
         cw, _keep = self._c_weights()
         if Cin != cw.dims.in_ch or H % 4 or W % 4:
@@ -1748,7 +1748,7 @@ class VQVAE(nn.Module):
         if C_hip.get_conv_backend() != "hip" or not idx.is_cuda:
             z_q = F_hip.vq_decode_indices(idx, self.vector_quantization.embedding.weight.detach(), B, H, W)
             return self.decoder(z_q)
-        idx = idx.contiguous().view(-1).to(torch.int64)
+        idx = _lib.dense(idx.contiguous().view(-1).to(torch.int64), 8)
         if validate and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= K):
             raise IndexError(f"code index out of range [0, {K})")
         L = _lib.load()

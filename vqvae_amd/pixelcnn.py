@@ -70,15 +70,16 @@ class _Holder:
 
 
 def _gather_rows(idx, table):
-    idx = idx.contiguous().view(-1)
+    idx = _lib.dense(idx, 8).view(-1)
     n, Cc = idx.numel(), table.shape[1]
     out = torch.empty((n, Cc), dtype=torch.float32, device=table.device)
-    _lib.check(_lib.load().vqvae_gather_rows_f32(idx.data_ptr(), table.detach().contiguous().data_ptr(), n, Cc,
+    _lib.check(_lib.load().vqvae_gather_rows_f32(idx.data_ptr(), _lib.dense(table.detach()).data_ptr(), n, Cc,
                                                  table.shape[0], out.data_ptr(), _sp(out)))
     return out
 
 
 def _im2col(x_rows, taps):
+    x_rows = _lib.dense(x_rows)
     B, H, W, Cc = x_rows.shape
     n = len(taps)
     dy = (C.c_int8 * n)(*[t[0] for t in taps])
@@ -90,6 +91,7 @@ def _im2col(x_rows, taps):
 
 
 def _gate(t1, t2, cond, dim):
+    t1, t2, cond = _lib.dense(t1, 4), _lib.dense(t2, 4), _lib.dense(cond, 4)     # (element-wise kernels)
     B, H, W, _ = t1.shape
     out = torch.empty((B, H, W, dim), dtype=torch.float32, device=t1.device)
     _lib.check(_lib.load().vqvae_gated_activation_f32(t1.data_ptr(), t2.data_ptr() if t2 is not None else None,
@@ -99,6 +101,7 @@ def _gate(t1, t2, cond, dim):
 
 
 def _add(a, b):
+    a, b = _lib.dense(a), _lib.dense(b)
     out = torch.empty_like(a)
     _lib.check(_lib.load().vqvae_add_f32(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _sp(a)))
     return out
@@ -123,7 +126,7 @@ def _taps_arrays(taps, sign=1):
 
 def bias_grad(g):
     """per-channel sums over all pixels of a row-major gradient (vqvae_bias_grad_wide_f32: any width)"""
-    g = g.contiguous()
+    g = _lib.dense(g, 4)
     Cc = g.shape[-1]
     L = _lib.load()
     n = L.vqvae_bias_grad_wide_workspace_bytes(Cc)
@@ -135,7 +138,7 @@ def bias_grad(g):
 
 def taps_wgrad(gy, x, taps):
     """(Cout, Cin, ntaps): grad_w[co][ci][t] = sum gy[b,y,x,co] x[b, y+dy_t, x+dx_t, ci]  (vqvae_conv_taps_wgrad_f32)"""
-    gy, x = gy.contiguous(), x.contiguous()
+    gy, x = _lib.dense(gy), _lib.dense(x)
     B, H, W, Cin = x.shape
     Cout, n = gy.shape[3], len(taps)
     L = _lib.load()
@@ -154,14 +157,14 @@ def taps_dgrad(gy, mod, weight, taps, addend=None):
     """grad_x of conv_hip.conv_taps: the tap kernels over the negated taps with the per-tap transposed weight, packed per weight
     version on a holder of `mod` (vqvae_conv_taps_pack_dgrad_f32); lists longer than 16 taps run as the forward's slices, each
     launch adding to the previous one's result; `addend` rides in the first launch's epilogue."""
-    gy = gy.contiguous()
+    gy = _lib.dense(gy)
     B, H, W, Cout = gy.shape
     Cin, n = weight.shape[1], len(taps)
     L = _lib.load()
     hold = _holder(mod, ("taps_dgrad", tuple(taps)))
     nsl = (n + 15) // 16
     per = (n + nsl - 1) // nsl
-    y = addend.contiguous() if addend is not None else None
+    y = _lib.dense(addend) if addend is not None else None
     for s0 in range(0, n, per):
         sl = taps[s0:s0 + per]
         k = len(sl)
@@ -182,9 +185,10 @@ def taps_dgrad(gy, mod, weight, taps, addend=None):
 
 def gate_backward(t1, cond, go, dim, gcond=None, accumulate=False):
     """grad of (a|g) -> tanh(a) sigmoid(g) at (a|g) = t1 + cond[b]; with gcond (B, 2 dim): [+]= the per-image sums over HW"""
+    t1, cond = _lib.dense(t1, 4), _lib.dense(cond, 4)
     B, H, W, _ = t1.shape
     gpre = torch.empty((B, H, W, 2 * dim), dtype=torch.float32, device=t1.device)
-    go = go.contiguous()
+    go = _lib.dense(go, 4)
     _lib.check(_lib.load().vqvae_gated_activation_backward_f32(
         t1.data_ptr(), None, cond.data_ptr() if cond is not None else None, go.data_ptr(), B, H * W, dim, gpre.data_ptr(),
         gcond.data_ptr() if (gcond is not None and accumulate) else None, gcond.data_ptr() if gcond is not None else None, _sp(go)))
@@ -193,7 +197,7 @@ def gate_backward(t1, cond, go, dim, gcond=None, accumulate=False):
 
 def gather_rows_backward(idx, g, rows):
     """grad_table (rows, C) of out = table[idx]: fixed-order segmented sums (vqvae_gather_rows_backward_f32)"""
-    idx, g = idx.contiguous().view(-1), g.contiguous()
+    idx, g = _lib.dense(idx, 8).view(-1), _lib.dense(g, 4)
     n, Cc = idx.numel(), g.shape[-1]
     L = _lib.load()
     nb = L.vqvae_gather_rows_backward_workspace_bytes(n, Cc, rows)
@@ -246,7 +250,7 @@ class _Conv1x1Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, relu_out, mask_input):
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         Cout, Cin = weight.shape[0], weight.shape[1]
         y = conv_hip.conv(CONV_1x1, x, mod, weight.detach(), bias.detach(), Cin, Cout, RELU_OUT if relu_out else 0)
         ctx.save_for_backward(x, weight.detach())
@@ -256,7 +260,7 @@ class _Conv1x1Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gy = gy.contiguous()
+        gy = _lib.dense(gy)
         Cout, Cin = w.shape[0], w.shape[1]
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
@@ -281,7 +285,7 @@ class _GatedLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_v, x_h, cond, layer, same, *params):
-        x_v, x_h, cond = x_v.detach().contiguous(), x_h.detach().contiguous(), cond.detach()
+        x_v, x_h, cond = _lib.dense(x_v.detach()), _lib.dense(x_h.detach()), cond.detach()
         out_v, out_h, h_vert, v2h, out = layer._forward_parts(x_v, x_h, cond)
         ctx.save_for_backward(x_v, x_h, cond, h_vert, v2h, out)
         ctx.layer, ctx.same = layer, same
@@ -295,7 +299,7 @@ class _GatedLayerFn(torch.autograd.Function):
         vs, vh, hs, hr = L.vert_stack, L.vert_to_horiz, L.horiz_stack, L.horiz_resid
         if g_oh is None:
             g_oh = torch.zeros_like(out)
-        g_oh = g_oh.contiguous()
+        g_oh = _lib.dense(g_oh)
         g_out = conv_hip.conv(CONVT_1x1, g_oh, _holder(L, ("dgrad", "horiz_resid")), hr.weight.detach(), None, dim, dim, 0)
         gw_hr, gb_hr = conv_wgrad(g_oh, out, 1, 1, 0), bias_grad(g_oh)
         B = x_v.shape[0]
@@ -316,7 +320,7 @@ class _GatedLayerFn(torch.autograd.Function):
 class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rows, targets):
-        rows, targets = rows.detach().contiguous(), targets.contiguous().view(-1)
+        rows, targets = _lib.dense(rows.detach(), 4), _lib.dense(targets, 8).view(-1)
         N, K = rows.shape
         L = _lib.load()
         nb = L.vqvae_cross_entropy_workspace_bytes(N)
@@ -330,7 +334,7 @@ class _CrossEntropyFn(torch.autograd.Function):
     def backward(ctx, g):
         rows, targets = ctx.saved_tensors
         N, K = rows.shape
-        g = g.detach().reshape(1).contiguous()
+        g = _lib.dense(g.detach().reshape(1), 4)
         gx = torch.empty_like(rows)
         _lib.check(_lib.load().vqvae_cross_entropy_backward_f32(rows.data_ptr(), targets.data_ptr(), N, K, g.data_ptr(), gx.data_ptr(),
                                                                 _sp(rows)))
@@ -539,7 +543,7 @@ class GatedPixelCNN(nn.Module):
             if nb == 0:
                 raise VqvaeHipError(f"cached sampler: K={K}, dim={dim}, n_layers={n_layers} not supported")
             img = _ws(nb, p0.device)
-            keep = [p.detach().contiguous() for p in params]             # alive until the pack launches are queued
+            keep = [_lib.dense(p.detach(), 4) for p in params]             # alive until the pack launches are queued
             ptrs = (C.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
             _lib.check(L.vqvae_pixelcnn_sample_pack_f32(ptrs, len(params), K, dim, n_layers, n_classes, img.data_ptr(), nb,
                                                         _sp(p0)))
@@ -585,7 +589,7 @@ class GatedPixelCNN(nn.Module):
             if not torch.is_tensor(given) or not given.is_cuda or given.dtype != torch.int64 or tuple(given.shape) != (B, H, W):
                 raise ValueError(f"given must be a CUDA(HIP) int64 tensor of shape ({B}, {H}, {W})")
         dev = p0.device
-        label = label.to(device=dev, dtype=torch.int64).contiguous()
+        label = _lib.dense(label.to(device=dev, dtype=torch.int64), 8)
         if label.shape != (B,):
             raise ValueError(f"label must have shape ({B},), got {tuple(label.shape)}")
         if self.output_conv[0].weight.shape[0] != 512:
@@ -602,13 +606,13 @@ class GatedPixelCNN(nn.Module):
                 uniforms = torch.rand((B, H, W), generator=generator, device=dev)
             elif not uniforms.is_cuda or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (B, H, W):
                 raise VqvaeHipError(f"uniforms must be a CUDA(HIP) float32 tensor of shape ({B}, {H}, {W})")
-            uniforms = uniforms.to(dev).contiguous()
+            uniforms = _lib.dense(uniforms.to(dev), 4)
             out = torch.empty((B, H, W), dtype=torch.int64, device=dev)
             logits = torch.empty((B, K, H, W), dtype=torch.float32, device=dev) if return_logits else None
             status = torch.empty(B, dtype=torch.int32, device=dev)
             ws = _ws(nws, dev)
             if given is not None:
-                given = given.to(dev).contiguous()
+                given = _lib.dense(given.to(dev), 8)
             # (1, 0, 1, NULL) is vqvae_pixelcnn_sample_f32: the plain kernel
             _lib.check(L.vqvae_pixelcnn_sample_ex_f32(img.data_ptr(), img.numel(), label.data_ptr(), uniforms.data_ptr(), B, H, W, K,
                                                       dim, n_layers, n_classes, temperature, top_k, top_p,

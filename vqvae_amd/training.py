@@ -46,9 +46,9 @@ def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False,
     F_hip._check_dev("z_e", z_e)
     F_hip._check_dev("codebook", codebook)
     F_hip._check_dev("idx", idx, torch.int64)
-    z_e = z_e.contiguous()
-    codebook = codebook.contiguous()
-    idx = idx.contiguous()
+    z_e = _lib.dense(z_e, 4)                   # (the entry picks its kernels' width by these pointers)
+    codebook = _lib.dense(codebook, 4)
+    idx = _lib.dense(idx, 8)
     if rowmajor:
         B, H, W, D = z_e.shape
     else:
@@ -58,12 +58,12 @@ def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False,
         raise ValueError("shape mismatch between z_e, codebook and idx")
     if grad_zq is not None:
         F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = grad_zq.contiguous()
+        grad_zq = _lib.dense(grad_zq, 4)
         if grad_zq.shape != z_e.shape:
             raise ValueError("grad_zq must have z_e's shape")
     if grad_loss is not None:
         F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = grad_loss.reshape(1).contiguous()
+        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
     dev = z_e.device
     L = _lib.load()
     with torch.cuda.device(dev):
@@ -93,8 +93,8 @@ class VQStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared, rotation=False):
-        z = z_e.detach().contiguous()
-        w = codebook.detach().contiguous()
+        z = _lib.dense(z_e.detach(), _lib.vq_align(codebook.shape[1]))
+        w = _lib.dense(codebook.detach(), _lib.vq_align(codebook.shape[1]))
         loss, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w, beta, rowmajor=rowmajor, workspace=workspace,
                                                             prepared=prepared)
         ctx.save_for_backward(z, w, idx)
@@ -121,8 +121,8 @@ class VQEMAStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, codebook, beta, rowmajor, workspace, prepared, rotation=False):
-        z = z_e.detach().contiguous()
-        w = codebook.detach().contiguous()
+        z = _lib.dense(z_e.detach(), _lib.vq_align(codebook.shape[1]))
+        w = _lib.dense(codebook.detach(), _lib.vq_align(codebook.shape[1]))
         mse, z_q, perplexity, idx, hist = F_hip.vq_forward(z, w, 0.0, rowmajor=rowmajor, workspace=workspace, prepared=prepared)
         ctx.save_for_backward(z, w.clone(), idx)
         ctx.beta, ctx.rowmajor, ctx.rotation = beta, rowmajor, bool(rotation)
@@ -164,7 +164,7 @@ class _StepLosses(torch.autograd.Function):
     def forward(ctx, x_hat, x, embedding_loss, perplexity, inv_var):
         F_hip._check_dev("x_hat", x_hat)
         F_hip._check_dev("x", x)
-        xh, xx = x_hat.detach().contiguous(), x.detach().contiguous()
+        xh, xx = _lib.dense(x_hat.detach()), _lib.dense(x.detach())
         if xh.shape != xx.shape:
             raise ValueError("x_hat and x must have the same shape")
         dev = xh.device
@@ -172,8 +172,8 @@ class _StepLosses(torch.autograd.Function):
         with torch.cuda.device(dev):
             out = torch.empty(3, dtype=torch.float32, device=dev)
             ws = torch.empty(L.vqvae_recon_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
-            el = embedding_loss.detach().reshape(1).contiguous() if embedding_loss is not None else None
-            pp = perplexity.detach().reshape(1).contiguous() if perplexity is not None else None
+            el = _lib.dense(embedding_loss.detach().reshape(1), 4) if embedding_loss is not None else None
+            pp = _lib.dense(perplexity.detach().reshape(1), 4) if perplexity is not None else None
             _lib.check(L.vqvae_recon_loss_f32(xh.data_ptr(), xx.data_ptr(), xh.numel(), float(inv_var),
                                               el.data_ptr() if el is not None else None,
                                               pp.data_ptr() if pp is not None else None,
@@ -187,7 +187,7 @@ class _StepLosses(torch.autograd.Function):
         xh, xx = ctx.saved_tensors
         gx = gel = None
         if ctx.needs_input_grad[0]:
-            gsum = (g[0] + g[1]).reshape(1).contiguous()       # recon_loss feeds out[0] and out[1]
+            gsum = _lib.dense((g[0] + g[1]).reshape(1), 4)       # recon_loss feeds out[0] and out[1]
             gx = torch.empty_like(xh)
             with torch.cuda.device(xh.device):
                 _lib.check(_lib.load().vqvae_recon_loss_backward_f32(xh.data_ptr(), xx.data_ptr(), xh.numel(),
@@ -218,8 +218,8 @@ def vq_residual_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowma
     F_hip._check_dev("z_e", z_e)
     F_hip._check_dev("idx", idx, torch.int64)
     books, nb = F_hip._residual_books(codebooks, shared)
-    z_e = z_e.contiguous()
-    idx = idx.contiguous()
+    z_e = _lib.dense(z_e, 4)
+    idx = _lib.dense(idx, 8)
     B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     K = books[0].shape[0]
     N = B * H * W
@@ -230,12 +230,12 @@ def vq_residual_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowma
         raise ValueError(f"{Q} stages of indices for {nb} codebooks")
     if grad_zq is not None:
         F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = grad_zq.contiguous()
+        grad_zq = _lib.dense(grad_zq, 4)
         if grad_zq.shape != z_e.shape:
             raise ValueError("grad_zq must have z_e's shape")
     if grad_loss is not None:
         F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = grad_loss.reshape(1).contiguous()
+        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
     if not (need_z or need_codebooks):
         return None, None
     dev = z_e.device
@@ -265,8 +265,9 @@ class RVQStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, beta, rowmajor, shared, n_q, workspace, prepared, *codebooks):
-        z = z_e.detach().contiguous()
-        books = [c.detach().contiguous() for c in codebooks]
+        al = _lib.vq_align(codebooks[0].shape[1])
+        z = _lib.dense(z_e.detach(), al)
+        books = [_lib.dense(c.detach(), al) for c in codebooks]
         loss, z_q, perplexity, idx, hist, loss_stage = F_hip.vq_residual_forward(
             z, books, beta, rowmajor=rowmajor, shared=shared, n_q=n_q, workspace=workspace, prepared=prepared)
         ctx.save_for_backward(z, idx, *books)
@@ -304,8 +305,8 @@ def vq_grouped_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowmaj
     F_hip._check_dev("idx", idx, torch.int64)
     books = F_hip._grouped_books(codebooks)
     G = len(books)
-    z_e = z_e.contiguous()
-    idx = idx.contiguous()
+    z_e = _lib.dense(z_e, 4)
+    idx = _lib.dense(idx, 8)
     B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     K, d = books[0].shape
     N = B * H * W
@@ -313,12 +314,12 @@ def vq_grouped_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowmaj
         raise ValueError("shape mismatch between z_e, the codebooks and idx")
     if grad_zq is not None:
         F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = grad_zq.contiguous()
+        grad_zq = _lib.dense(grad_zq, 4)
         if grad_zq.shape != z_e.shape:
             raise ValueError("grad_zq must have z_e's shape")
     if grad_loss is not None:
         F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = grad_loss.reshape(1).contiguous()
+        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
     if not (need_z or need_codebooks):
         return None, None
     dev = z_e.device
@@ -351,8 +352,8 @@ class GroupedStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, beta, rowmajor, commitment, want_slabs, workspace, prepared, *codebooks):
-        z = z_e.detach().contiguous()
-        books = [c.detach().contiguous() for c in codebooks]
+        z = _lib.dense(z_e.detach(), 4)
+        books = [_lib.dense(c.detach(), 4) for c in codebooks]
         out = F_hip.vq_grouped_forward(z, books, 0.0 if commitment else beta, rowmajor=rowmajor, want_slabs=want_slabs,
                                        workspace=workspace, prepared=prepared)
         loss, z_q, perplexity, idx, hist, loss_group = out[:6]
@@ -397,7 +398,7 @@ def fsq_backward(z_e, grad_zq, w_in, b_in, w_out, levels, *, rowmajor=False, nee
     lv, c_lv, _ = F_hip._fsq_levels(levels)
     d = len(lv)
     w_in, b_in, w_out = F_hip._fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out)
-    z_e, grad_zq = z_e.contiguous(), grad_zq.contiguous()
+    z_e, grad_zq = _lib.dense(z_e, 4), _lib.dense(grad_zq, 4)
     dev = z_e.device
     with torch.cuda.device(dev):
         gz = torch.empty_like(z_e) if need_z else None
@@ -419,8 +420,8 @@ class FSQStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, w_in, b_in, w_out, b_out, levels, rowmajor):
-        z = z_e.detach().contiguous()
-        params = [t.detach().contiguous() for t in (w_in, b_in, w_out, b_out)]
+        z = _lib.dense(z_e.detach(), 4)
+        params = [_lib.dense(t.detach(), 4) for t in (w_in, b_in, w_out, b_out)]
         z_q, perplexity, idx, hist = F_hip.fsq_forward(z, *params, levels, rowmajor=rowmajor)
         ctx.save_for_backward(z, *params[:3])
         ctx.levels, ctx.rowmajor = tuple(levels), rowmajor
@@ -458,12 +459,12 @@ def lfq_backward(z_e, grad_zq, grad_loss, avg, w_in, b_in, w_out, n_e, *, beta=0
         F_hip._check_dev("avg", avg, torch.float64)
         if avg.numel() != n_e:
             raise ValueError("avg must hold n_e values")
-        avg = avg.contiguous()
+        avg = _lib.dense(avg, 8)
     if grad_loss is not None:
         F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = grad_loss.contiguous()
-    z_e = z_e.contiguous()
-    grad_zq = grad_zq.contiguous() if grad_zq is not None else None
+        grad_loss = _lib.dense(grad_loss, 4)
+    z_e = _lib.dense(z_e, 4)
+    grad_zq = _lib.dense(grad_zq, 4) if grad_zq is not None else None
     dev = z_e.device
     with torch.cuda.device(dev):
         gz = torch.empty_like(z_e) if need_z else None
@@ -487,8 +488,8 @@ class LFQStraightThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_e, w_in, b_in, w_out, b_out, n_e, weights, rowmajor):
-        z = z_e.detach().contiguous()
-        params = [t.detach().contiguous() for t in (w_in, b_in, w_out, b_out)]
+        z = _lib.dense(z_e.detach(), 4)
+        params = [_lib.dense(t.detach(), 4) for t in (w_in, b_in, w_out, b_out)]
         beta, we, gamma, inv_t = (float(v) for v in weights)
         z_q, perplexity, idx, hist, losses, avg = F_hip.lfq_forward(
             z, *params, n_e, beta=beta, entropy_weight=we, diversity_gamma=gamma, inv_temperature=inv_t, rowmajor=rowmajor)
@@ -521,7 +522,7 @@ class LinearRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, rowmajor=False):
-        x_, w_ = x.detach().contiguous(), w.detach().contiguous()
+        x_, w_ = _lib.dense(x.detach(), 4), _lib.dense(w.detach(), 4)
         y = F_hip.linear_rows(x_, w_, b.detach(), rowmajor=rowmajor)
         ctx.save_for_backward(x_, w_)
         ctx.rowmajor = rowmajor
@@ -554,7 +555,7 @@ class OrthogonalLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         saved, selected, count = ctx.saved_tensors
-        return F_hip.vq_orthogonal_backward(saved, selected, count, g.contiguous()), None, None, None, None
+        return F_hip.vq_orthogonal_backward(saved, selected, count, _lib.dense(g, 4)), None, None, None, None
 
 
 # ---- the code-entropy loss of a learned codebook (csrc/vq_entropy.hip) --------------------------------------------------------------
@@ -584,6 +585,6 @@ class CodeEntropyLoss(torch.autograd.Function):
         want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if not any(want):
             return None, None, None, None, None, None
-        gz, ge = F_hip.vq_entropy_backward(z.detach(), codebook.detach(), avg, rowstat, g.contiguous(), inv_temperature=s, gamma=gamma,
+        gz, ge = F_hip.vq_entropy_backward(z.detach(), codebook.detach(), avg, rowstat, _lib.dense(g, 4), inv_temperature=s, gamma=gamma,
                                            rowmajor=rowmajor, want=want, workspace=ws)
         return gz, ge, None, None, None, None
