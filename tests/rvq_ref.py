@@ -94,6 +94,12 @@ def grad_z_mirror(rows, books, idx, grad_zq, g):
     return out
 
 
+def grad_z_bound(Q, abs_grad_zq, cz, abs_diffs):
+    """grad_z's per-element bound against the fp64 value: 2 (Q + 2) 2^-24 (|grad_zq| + |c| sum_q |r_q - e_q|), c = g 2 / (N D); plain
+    arithmetic on arrays of any kind (the GPU test of the 4-wide kernels evaluates it on device tensors)"""
+    return 2.0 * (Q + 2) * 2.0 ** -24 * (abs_grad_zq + abs(cz) * abs_diffs)
+
+
 def grads(rows, books, idx, grad_zq, g, beta, shared=False):
     """fp64 gradients of the closed forms, from the contract's fp32 residuals r_q and codes e_q:
          grad_z      = grad_zq + g 2/(N D) sum_q (r_q - e_q)
@@ -107,7 +113,7 @@ def grads(rows, books, idx, grad_zq, g, beta, shared=False):
     diffs = [c.r[q].astype(np.float64) - c.e[q].astype(np.float64) for q in range(Q)]
     gzq = np.zeros((N, D)) if grad_zq is None else np.asarray(grad_zq, np.float64)
     gz = gzq + cz * sum(diffs)
-    bound = 2.0 * (Q + 2) * 2.0 ** -24 * (np.abs(gzq) + abs(cz) * sum(np.abs(d) for d in diffs))
+    bound = grad_z_bound(Q, np.abs(gzq), cz, sum(np.abs(d) for d in diffs))
     ge = []
     for q in range(Q):
         acc = np.zeros((K, D))

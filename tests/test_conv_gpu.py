@@ -233,27 +233,32 @@ def test_residual_layer_large_batch(C, B):
     assert torch.equal(torch.cat(halves), y), "results must not depend on how the batch is sliced"
 
 
-def test_convt_out_vs_torch_cpu():
+def convt_out_case(Cin, Cout, B, H, W):
+    """the last layer on one shape against torch's CPU op (tests/test_grid_caps_gpu.py runs a shape of its own through it)"""
     from vqvae_amd import _lib, conv_hip
+    m = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1)
+    x = torch.randn(B, Cin, H, W)
+    with torch.no_grad():
+        ref = m(x)
+    md = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1).to(dev())
+    md.load_state_dict(m.state_dict())
+    L = _lib.load()
+    xr = rows(x.to(dev()))
+    p = conv_hip._packed(md, ("convt_out",), md.weight, lambda: L.vqvae_convt_out_packed_bytes(Cin, Cout),
+                         lambda w, buf: L.vqvae_convt_out_pack_f32(w.data_ptr(), Cin, Cout, buf.data_ptr(), None))
+    for flags in (0, 4):                       # split-bf16 products (default) and VQVAE_CONV_EXACT_FP32
+        y = torch.empty((B, Cout, 2 * H, 2 * W), device=dev())
+        _lib.check(L.vqvae_convt_out_forward_f32(xr.data_ptr(), p.data_ptr(), md.bias.data_ptr(), B, H, W, Cin, Cout,
+                                                 flags, y.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        close(y.cpu().numpy(), ref.numpy())
+
+
+def test_convt_out_vs_torch_cpu():
     torch.manual_seed(9)
     for Cin, Cout, B, H, W in [(64, 3, 3, 16, 16), (32, 3, 2, 5, 7), (16, 1, 1, 4, 4), (64, 3, 2, 20, 37),
                                   (128, 4, 1, 33, 16), (8, 2, 1, 17, 17)]:
-        m = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1)
-        x = torch.randn(B, Cin, H, W)
-        with torch.no_grad():
-            ref = m(x)
-        md = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1).to(dev())
-        md.load_state_dict(m.state_dict())
-        L = _lib.load()
-        xr = rows(x.to(dev()))
-        p = conv_hip._packed(md, ("convt_out",), md.weight, lambda: L.vqvae_convt_out_packed_bytes(Cin, Cout),
-                             lambda w, buf: L.vqvae_convt_out_pack_f32(w.data_ptr(), Cin, Cout, buf.data_ptr(), None))
-        for flags in (0, 4):                       # split-bf16 products (default) and VQVAE_CONV_EXACT_FP32
-            y = torch.empty((B, Cout, 2 * H, 2 * W), device=dev())
-            _lib.check(L.vqvae_convt_out_forward_f32(xr.data_ptr(), p.data_ptr(), md.bias.data_ptr(), B, H, W, Cin, Cout,
-                                                     flags, y.data_ptr(), torch.cuda.current_stream().cuda_stream))
-            torch.cuda.synchronize()
-            close(y.cpu().numpy(), ref.numpy())
+        convt_out_case(Cin, Cout, B, H, W)
 
 
 def test_transpose_roundtrip():

@@ -11,6 +11,16 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+# the tolerances of the header, by name: tests/test_grid_caps_gpu.py checks the same entries past their launch caps under the same ones
+GRAD_Z_TOL = dict(rtol=1e-5, atol=1e-9)
+RECON_TOL = dict(rtol=2e-6, atol=0)
+RECON_GRAD_TOL = dict(rtol=1e-5, atol=1e-12)
+
+
+def grad_codebook_tol(ref):
+    return dict(rtol=1e-4, atol=1e-5 * float(ref.abs().max()))
+
+
 CASES = [  # B, D, H, W, K
     (4, 64, 8, 8, 512),
     (3, 32, 5, 7, 100),
@@ -50,9 +60,8 @@ def test_vq_backward_vs_autograd(B, D, H, W, K, rowmajor):
     gz, ge = T.vq_backward(zd, cb.to(dev), idx, gd, g_loss.to(dev), 0.25, rowmajor=rowmajor)
     if rowmajor:
         gz = gz.permute(0, 3, 1, 2)
-    torch.testing.assert_close(gz.cpu(), gz_ref, rtol=1e-5, atol=1e-9)
-    scale = float(ge_ref.abs().max())
-    torch.testing.assert_close(ge.cpu(), ge_ref, rtol=1e-4, atol=1e-5 * scale)
+    torch.testing.assert_close(gz.cpu(), gz_ref, **GRAD_Z_TOL)
+    torch.testing.assert_close(ge.cpu(), ge_ref, **grad_codebook_tol(ge_ref))
     # codes nobody chose get exactly zero gradient
     unused = torch.bincount(idx_ref.view(-1), minlength=K) == 0
     assert (ge.cpu()[unused] == 0).all()
@@ -85,9 +94,8 @@ def test_module_backward_matches_reference_structure():
     assert not perplexity.requires_grad and not min_encodings.requires_grad and not idx.requires_grad
     (loss + (z_q * w_cpu.to(dev)).sum()).backward()
     gz_ref, ge_ref, _ = _ref_grads(z_cpu, vq.embedding.weight.detach().cpu(), 0.25, w_cpu, torch.tensor(1.0))
-    torch.testing.assert_close(z.grad.cpu(), gz_ref, rtol=1e-5, atol=1e-9)
-    torch.testing.assert_close(vq.embedding.weight.grad.cpu(), ge_ref, rtol=1e-4,
-                               atol=1e-5 * float(ge_ref.abs().max()))
+    torch.testing.assert_close(z.grad.cpu(), gz_ref, **GRAD_Z_TOL)
+    torch.testing.assert_close(vq.embedding.weight.grad.cpu(), ge_ref, **grad_codebook_tol(ge_ref))
     # straight-through: d(sum z_q)/dz == 1 exactly
     z2 = z_cpu.to(dev).requires_grad_(True)
     vq(z2)[1].sum().backward()
@@ -112,11 +120,11 @@ def test_step_losses_vs_main_py(shape):
     stats = T.step_losses(eld, xh, pp.to(dev), x.to(dev), var)
     assert stats.shape == (3,)
     got = stats.detach().cpu()
-    torch.testing.assert_close(got[0], recon_ref.detach(), rtol=2e-6, atol=0)
-    torch.testing.assert_close(got[1], loss_ref.detach(), rtol=2e-6, atol=0)
+    torch.testing.assert_close(got[0], recon_ref.detach(), **RECON_TOL)
+    torch.testing.assert_close(got[1], loss_ref.detach(), **RECON_TOL)
     assert got[2] == pp
     stats[1].backward()
-    torch.testing.assert_close(xh.grad.cpu(), xh_ref.grad, rtol=1e-5, atol=1e-12)
+    torch.testing.assert_close(xh.grad.cpu(), xh_ref.grad, **RECON_GRAD_TOL)
     assert float(eld.grad) == 1.0
 
 

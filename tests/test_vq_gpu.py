@@ -222,7 +222,11 @@ def _oracle_vq_chunked(z, cb, beta, n_chunks=64, workers=32):
     return np.concatenate([o["idx"] for o in outs]), np.concatenate([o["z_q"] for o in outs])
 
 
-@pytest.mark.parametrize("B,H,W", [(4096, 8, 8), (2100, 7, 9)], ids=["config3_262144rows", "ragged_132300rows"])
+HEADLINE_SHAPES = [(4096, 8, 8), (2100, 7, 9)]             # (tests/grid_caps.py reads the shapes from here)
+GROUPS_CASE = (640, 64, 17 * (1 << 18) + 333)             # K, D, rows of the test of more than one group of slabs
+
+
+@pytest.mark.parametrize("B,H,W", HEADLINE_SHAPES, ids=["config3_262144rows", "ragged_132300rows"])
 def test_vq_headline_size_bit_exact_vs_oracle(B, H, W):
     """BASELINE config-3 size against the ORACLE (not against the kernels themselves): 262 144 rows of the benchmark
     distribution, and a ragged row count above 131 072 (rows % 64 != 0, several pairs per wave) -- indices and z_q
@@ -407,8 +411,7 @@ def test_vq_stream_more_than_one_group_of_slabs_equals_the_exhaustive_kernel():
     against the exhaustive fp32 kernel.  A few rows are made hard (many codes within the bound) in BOTH groups."""
     from vqvae_amd import functional as F
     g = torch.Generator(device=_dev()).manual_seed(5)
-    K, D = 640, 64
-    n = 17 * (1 << 18) + 333
+    K, D, n = GROUPS_CASE
     cb = ((torch.rand(K, D, generator=g, device=_dev()) * 2 - 1) / K)
     z = torch.randn(n // 3, 1, 3, D, generator=g, device=_dev()) * 0.066              # (B, H, W, D) row-major, 3 rows per "image"
     rows = z.view(-1, D)

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import graph_replay as GP
+from tests import grid_caps as GC
 from tests import vq_grouped_ref as GR
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +27,9 @@ BETA = 0.25
 KDG = [(512, 64, 2), (96, 64, 4), (64, 48, 3), (5, 6, 3), (5, 3, 3), (2048, 256, 2)]
 # (B, H, W): 192 rows; H W = 32; H W = 15 -- NCHW maps that are no multiple of four pixels: the element path
 SHAPES = [(3, 8, 8), (5, 4, 8), (2, 3, 5)]
+# (K, D, G, B, H, W) past the element-wise kernels' launch cap (tests/grid_caps.py reads the shape from here)
+CAP_SHAPE = (16, 256, 2, 17477, 3, 5)
+CAP_SHAPE_ELEMENT = (5, 6, 3, 186414, 3, 5)
 
 
 def _bits(t):
@@ -172,17 +176,43 @@ def test_both_access_widths_give_the_same_bits(K, D, G, B, H, W, rowmajor):
     assert _same(ga[0], gb[0]) and all(_same(x, y) for x, y in zip(ga[1], gb[1]))
 
 
-@pytest.mark.parametrize("rowmajor", [False, True])
-def test_grid_stride_past_the_launch_cap(rowmajor):
-    """more units than the stream kernels' 65536 workgroups of 256 threads cover in one step, in both access widths (H W = 15: NCHW
-    maps go element by element)"""
-    from vqvae_amd import functional as F
-    K, D, G, B, H, W = 16, 256, 2, 17477, 3, 5
-    assert B * H * W * D // 4 > 65536 * 256
+def _past_the_cap(shape, rowmajor):
+    """the forward against the slices, then the backward direction past the same cap: grad_z in the header's order, into a buffer
+    that starts as NaNs between guards"""
+    from vqvae_amd import functional as F, training as T
+    K, D, G, B, H, W = shape
     rows, books = _case(K, D, G, B, H, W)
     z, dbooks = _layout(rows, B, H, W, rowmajor), _dev(books)
     out = F.vq_grouped_forward(z, dbooks, BETA, rowmajor=rowmajor, want_slabs=True)
-    _check_against_the_slices(out, z, dbooks, rows, books, B, H, W, rowmajor, f"262155 rows, rowmajor={rowmajor}")
+    _check_against_the_slices(out, z, dbooks, rows, books, B, H, W, rowmajor, f"{B * H * W} rows, rowmajor={rowmajor}")
+    idx = out[3]
+    del out
+    gzq = torch.randn(z.shape, generator=torch.Generator().manual_seed(K + G)).to(DEV)
+    g = np.float32(0.7)
+    with GC.guarded() as guard:
+        gz, none = T.vq_grouped_backward(z, dbooks, idx, gzq, torch.tensor(float(g), device=DEV), BETA, rowmajor=rowmajor,
+                                         need_codebooks=False)
+    guard.check()
+    assert none is None
+    assert np.array_equal(_bits(_rows(gz, rowmajor)), _bits(GR.grad_z_mirror(rows, books, idx.cpu().numpy(), _rows(gzq, rowmajor), g)))
+
+
+@pytest.mark.parametrize("rowmajor", [False, True])
+def test_grid_stride_past_the_launch_cap(rowmajor):
+    """more units than the stream kernels' 65536 workgroups of 256 threads cover in one step, in both access widths (H W = 15: NCHW
+    maps go element by element), forward and backward"""
+    K, D, G, B, H, W = CAP_SHAPE
+    assert B * H * W * D // 4 > 65536 * 256
+    _past_the_cap(CAP_SHAPE, rowmajor)
+
+
+@pytest.mark.parametrize("rowmajor", [False, True])
+def test_grid_stride_past_the_launch_cap_element_path(rowmajor):
+    """the element path with a last lap that ends inside a workgroup: groups of two channels go element by element in both layouts,
+    and 6 channels make an element count that is no multiple of 256 (CAP_SHAPE's 256 channels always give one)"""
+    K, D, G, B, H, W = CAP_SHAPE_ELEMENT
+    assert B * H * W * D > 65536 * 256 and (B * H * W * D) % 256 != 0 and (D // G) % 4 != 0
+    _past_the_cap(CAP_SHAPE_ELEMENT, rowmajor)
 
 
 def test_decode_past_32_bit_element_counts_16GiB():

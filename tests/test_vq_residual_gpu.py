@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grid_caps as GC
 from tests import rvq_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -121,16 +122,131 @@ def test_forward_without_zq_and_on_a_prepared_workspace():
     assert out[1] is None and len(out) == 6 and torch.equal(out[3], first[3]) and torch.equal(out[0], first[0])
 
 
+def _check_backward(gz, ge, rows, books, idx, grad_zq, gl, rowmajor, what, shared=False):
+    """grad_z inside the header's bound of the fp64 value and bitwise the mirrored fp32 order; codebook gradients at
+    vqvae_vq_backward_f32's contract"""
+    want_gz, bound, _, want_ge = R.grads(rows, books, idx, grad_zq, gl, BETA, shared)
+    got = _rows(gz, rowmajor)
+    err = np.abs(got.astype(np.float64) - want_gz)
+    print(f"{what}: max grad_z error / bound = {float((err / np.maximum(bound, 1e-300)).max()):.3f}")
+    assert (err <= bound).all(), what
+    assert np.array_equal(_bits(got), _bits(R.grad_z_mirror(rows, books, idx, grad_zq, gl))), f"{what}: grad_z, the header's order"
+    assert len(ge) == len(want_ge)
+    for a, w in zip(ge, want_ge):
+        assert np.abs(w).max() > 0
+        np.testing.assert_allclose(a.cpu().numpy(), w, rtol=1e-4, atol=1e-5 * np.abs(w).max(), err_msg=what)
+
+
+# (B, H, W, D, K) past the launch cap of the element-wise kernels, 65536 workgroups of 256 threads (tests/grid_caps.py reads the
+# shapes from here): NCHW maps of 15 pixels go element by element; row-major rows of 8 channels go four elements per thread, so
+# the same cap lies four times as many elements out
+CAP_SHAPE = (17477, 3, 5, 64, 16)
+CAP_SHAPE_WIDE = (8388743, 1, 1, 8, 16)
+
+
 def test_grid_stride_past_the_launch_cap():
-    """more elements than the element-wise kernels' 65536 workgroups of 256 threads cover in one step"""
-    from vqvae_amd import functional as F
-    B, H, W, D, K = 17477, 3, 5, 64, 16
+    """more elements than the element-wise kernels' 65536 workgroups of 256 threads cover in one step: the forward, and the backward
+    (grad_z and both codebook gradients) into buffers that start as NaNs between guards"""
+    from vqvae_amd import functional as F, training as T
+    B, H, W, D, K = CAP_SHAPE
     assert B * H * W * D > 65536 * 256
     rows = np.random.default_rng(1).standard_normal((B * H * W, D)).astype(np.float32)
     books = R.draw_books(rows, K, 2, False, 2)
     c = R.chain(rows, books, BETA)
-    out = F.vq_residual_forward(_layout(rows, B, H, W, False), _dev(books), BETA, want_residual=True)
+    z, dbooks = _layout(rows, B, H, W, False), _dev(books)
+    out = F.vq_residual_forward(z, dbooks, BETA, want_residual=True)
     _check_forward(out, c, False, K, "262155 rows, NCHW")
+    del out
+    # codes moved off the rows they were drawn from (as _backward_case does), the forward's indices kept: any indices are the entry's input
+    g = np.random.default_rng(3)
+    moved = [(E + 0.05 * g.standard_normal(E.shape)).astype(np.float32) for E in books]
+    grad_zq, gl = g.standard_normal(rows.shape).astype(np.float32), np.float32(0.7)
+    with GC.guarded() as guard:
+        gz, ge = T.vq_residual_backward(z, _dev(moved), torch.from_numpy(c.idx).to(DEV), _layout(grad_zq, B, H, W, False),
+                                        torch.tensor(float(gl), device=DEV), BETA)
+    guard.check()
+    _check_backward(gz, ge, rows, moved, c.idx, grad_zq, gl, False, "262155 rows, NCHW, backward")
+
+
+def _wide_case():
+    """(z, books, idx, grad_zq) of CAP_SHAPE_WIDE on the device: two stages, indices drawn (decode and backward take any)"""
+    B, H, W, D, K = CAP_SHAPE_WIDE
+    N = B * H * W
+    assert N * D // 4 > 65536 * 256 and (N * D // 4) % 256 != 0
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    z = torch.randn((B, H, W, D), device=DEV, generator=gen)
+    books = [torch.randn((K, D), device=DEV, generator=gen) * 0.5 ** q for q in range(2)]
+    idx = torch.randint(0, K, (2, N), device=DEV, generator=gen)
+    return z, books, idx, torch.randn((B, H, W, D), device=DEV, generator=gen)
+
+
+def _wide_blocks(z, books, idx, step=1 << 21):
+    """a block of rows at a time: (rows, [e_0, e_1], [r_0, r_1, r_2]) -- the chain of tests/rvq_ref.py in torch's fp32 ops"""
+    B, H, W, D, K = CAP_SHAPE_WIDE
+    N = B * H * W
+    for r0 in range(0, N, step):
+        sl = slice(r0, min(N, r0 + step))
+        e = [books[q][idx[q, sl]] for q in range(2)]
+        r = [z.view(N, D)[sl]]
+        for q in range(2):
+            r.append(r[q] - e[q])
+        yield sl, e, r
+
+
+def test_grid_stride_past_the_launch_cap_4_wide():
+    """the same cap in the kernels' 4-wide forms (row-major rows, D % 4 == 0, aligned tensors), on 67 M elements: rvq_finish_kernel<4>
+    through the decode and rvq_gradz_kernel<4> through the backward.  The restatement's arithmetic (tests/rvq_ref.py: chain,
+    grad_z_mirror, grads) is evaluated here with torch's elementwise ops on the device, a block of rows at a time -- one IEEE
+    operation per op, nothing fused, as numpy's -- because the numpy form would take a minute at this size; the bounds are
+    test_backward_against_the_restatement's."""
+    from vqvae_amd import functional as F, training as T
+    B, H, W, D, K = CAP_SHAPE_WIDE
+    N, Q = B * H * W, 2
+    z, books, idx, grad_zq = _wide_case()
+    gl = np.float32(0.7)
+    with GC.guarded() as guard:
+        s = F.vq_residual_decode(idx, books, B, H, W, rowmajor=True, validate=False)
+        gz, none = T.vq_residual_backward(z, books, idx, grad_zq, torch.tensor(float(gl), device=DEV), BETA, rowmajor=True,
+                                          need_codebooks=False)
+    guard.check()
+    assert none is None and z.data_ptr() % 16 == 0 and gz.data_ptr() % 16 == 0 and s.data_ptr() % 16 == 0
+    gs = float(np.float32(gl * np.float32(2.0 / (float(N) * float(D)))))
+    cz = float(gl) * 2.0 / (N * D)
+    worst = 0.0
+    gr, sr, gzr = grad_zq.view(N, D), s.view(N, D), gz.view(N, D)
+    for sl, e, r in _wide_blocks(z, books, idx):
+        assert torch.equal(sr[sl].view(torch.int32), (e[0] + e[1]).view(torch.int32)), f"decode: rows from {sl.start}"
+        mirror = gr[sl] + gs * (r[1] + r[2])
+        assert torch.equal(gzr[sl].view(torch.int32), mirror.view(torch.int32)), f"grad_z, the header's order: rows from {sl.start}"
+        diffs = [r[q].double() - e[q].double() for q in range(Q)]
+        want = gr[sl].double() + cz * (diffs[0] + diffs[1])
+        bound = R.grad_z_bound(Q, gr[sl].double().abs(), cz, diffs[0].abs() + diffs[1].abs())
+        err = (gzr[sl].double() - want).abs()
+        assert bool((err <= bound).all()), f"grad_z against fp64: rows from {sl.start}"
+        worst = max(worst, float((err / bound.clamp_min(1e-300)).max()))
+    print(f"{N} rows, row-major, 4-wide: max grad_z error / bound = {worst:.3f}")
+
+
+def test_grid_stride_past_the_launch_cap_4_wide_codebooks():
+    """... and rvq_advance_kernel<4> in front of the second stage's segmented sum: both codebook gradients,
+    grad_E_q[k] = g 2 beta / (N D) sum_{i: idx_q,i = k} (e_k - r_q,i) in fp64, at vqvae_vq_backward_f32's contract"""
+    from vqvae_amd import training as T
+    B, H, W, D, K = CAP_SHAPE_WIDE
+    N, Q = B * H * W, 2
+    z, books, idx, _ = _wide_case()
+    gl = 0.7
+    with GC.guarded() as guard:
+        none, ge = T.vq_residual_backward(z, books, idx, None, torch.tensor(gl, device=DEV), BETA, rowmajor=True, need_z=False)
+    guard.check()
+    assert none is None and len(ge) == Q
+    sums = [torch.zeros((K, D), dtype=torch.float64, device=DEV) for _ in range(Q)]
+    for sl, e, r in _wide_blocks(z, books, idx):
+        for q in range(Q):                                    # the rows of every code, added up as one product per block
+            sums[q] += torch.nn.functional.one_hot(idx[q, sl], K).double().T @ (e[q].double() - r[q].double())
+    for a, w in zip(ge, sums):
+        w = (gl * 2.0 * BETA / (N * D) * w).cpu().numpy()
+        assert np.abs(w).max() > 0
+        np.testing.assert_allclose(a.cpu().numpy(), w, rtol=1e-4, atol=1e-5 * np.abs(w).max())
 
 
 # ---- 2. one stage is the quantizer ---------------------------------------------------------------------------------------------------
@@ -234,16 +350,8 @@ def test_backward_against_the_restatement(K, D, B, H, W, rowmajor):
         gz2, ge2 = T.vq_residual_backward(z, dbooks, idx_d, gzq_d, gl_d, BETA, rowmajor=rowmajor, shared=shared)
         torch.cuda.synchronize()
         assert np.array_equal(_bits(gz), _bits(gz2)) and all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(ge, ge2))
-        want_gz, bound, per_stage, want_ge = R.grads(rows, books, idx, grad_zq, gl, BETA, shared)
-        got = _rows(gz, rowmajor)
-        err = np.abs(got.astype(np.float64) - want_gz)
-        print(f"K={K} D={D} shared={shared}: max grad_z error / bound = {float((err / np.maximum(bound, 1e-300)).max()):.3f}")
-        assert (err <= bound).all()
-        assert np.array_equal(_bits(got), _bits(R.grad_z_mirror(rows, books, idx, grad_zq, gl))), "grad_z: the header's order"
-        assert len(ge) == len(want_ge) == (1 if shared else Q)
-        for a, w in zip(ge, want_ge):
-            assert np.abs(w).max() > 0
-            np.testing.assert_allclose(a.cpu().numpy(), w, rtol=1e-4, atol=1e-5 * np.abs(w).max())
+        assert len(ge) == (1 if shared else Q)
+        _check_backward(gz, ge, rows, books, idx, grad_zq, gl, rowmajor, f"K={K} D={D} shared={shared}", shared)
         if shared:
             # the shared codebook's gradient is the stage results added in stage order: the same codebook listed per stage gives them
             _, stages = T.vq_residual_backward(z, dbooks * Q, idx_d, gzq_d, gl_d, BETA, rowmajor=rowmajor, need_z=False)
