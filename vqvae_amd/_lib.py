@@ -303,6 +303,126 @@ def vq_align(D: int) -> int:
     return 16 if D in (32, 64, 128, 256) else 4
 
 
+# ---- front-end helpers: the argument plumbing every tensor-taking wrapper shares ------------------------------------------------
+# None of them launches a kernel, allocates on the device or synchronises, but for the allocation `workspace` and `like_map` exist
+# to make and the min / max `check_index_range` exists to make; every pointer they hand out is taken from what `dense` returned.
+
+def stream_ptr(t) -> int:
+    """the current HIP stream of t's device, as the entries take it"""
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def check_dev(name, t, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise VqvaeHipError(f"{name} must be a CUDA(HIP) tensor on the GPU: the MI355X path has no CPU path and no fallback")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype} (the reference path is fp32 only)")
+
+
+def ptr(t):
+    """t's data pointer; None passes through (an optional argument of an entry)"""
+    return None if t is None else t.data_ptr()
+
+
+def ptr_array(tensors):
+    """the HOST array of device pointers an entry takes for a list of tensors (read during the call only); None passes through"""
+    return None if tensors is None else (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def ws_args(ws):
+    """(pointer, bytes) of a workspace of any dtype, (None, 0) of none"""
+    return (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+
+
+def workspace(bytes_fn_name, what, envelope, dims, device):
+    """a uint8 workspace of the size the entry `bytes_fn_name` gives for dims (a dict, in the entry's argument order); a size of 0
+    says the dimensions are outside the kernels' envelope: VqvaeHipError, nothing allocated"""
+    n = getattr(load(), bytes_fn_name)(*dims.values())
+    if n == 0:
+        raise VqvaeHipError(f"{what}: {', '.join(f'{k}={v}' for k, v in dims.items())} not supported by the gfx950 kernels ({envelope})")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def map_dims(name, x, rowmajor, allow_2d=False):
+    """-> (B, D, H, W) of x, a device fp32 map: (B,D,H,W), or (B,H,W,D) when rowmajor.  allow_2d: a 2-D (K, D) table counts as K
+    row-major rows, and the layout the entry is to be told comes back as a fifth value.  ValueError for any other rank."""
+    check_dev(name, x)
+    if allow_2d and x.dim() == 2:
+        return x.shape[0], x.shape[1], 1, 1, True
+    if x.dim() != 4:
+        raise ValueError(f"{name} must be a 4-D map: (B, D, H, W), or (B, H, W, D) when rowmajor" + (", or a 2-D (K, D) tensor" * allow_2d))
+    B, D, H, W = (x.shape[0], x.shape[3], x.shape[1], x.shape[2]) if rowmajor else x.shape
+    return (B, D, H, W, bool(rowmajor)) if allow_2d else (B, D, H, W)
+
+
+def like_map(x, C, rowmajor, bhw=None, device=None):
+    """an empty fp32 tensor of x's rows and layout with C channels (x: a map, or a 2-D table); bhw: the map's (B, H, W) where x is
+    no map (a decoder's indices) and gives the device alone; device: "meta" for the shape alone"""
+    if bhw is not None:
+        shape = (bhw[0], bhw[1], bhw[2], C) if rowmajor else (bhw[0], C, bhw[1], bhw[2])
+    elif x.dim() == 2:
+        shape = (x.shape[0], C)
+    else:
+        shape = (*x.shape[:3], C) if rowmajor else (x.shape[0], C, *x.shape[2:])
+    return torch.empty(shape, dtype=torch.float32, device=device or x.device)
+
+
+def check_index_range(idx, K, who):
+    """IndexError unless every index lies in [0, K): the reference's embedding lookup raises on an index out of range, the kernels
+    cannot (they write NaN rows and read nothing out of range).  One host sync, skipped while a graph is being captured."""
+    if torch.cuda.is_current_stream_capturing():
+        return
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= K:
+        raise IndexError(f"index out of range in {who}: [{lo}, {hi}] not within [0, {K})")
+
+
+def k_values(name, t, K):
+    """K values in a device fp32 tensor (a draw of uniforms, one per code), dense; None passes through"""
+    if t is None:
+        return None
+    check_dev(name, t)
+    if t.numel() != K:
+        raise ValueError(f"{name} must hold K = {K} values")
+    return dense(t, 4)
+
+
+def device_scalar(name, t):
+    """one fp32 value on the device (an upstream loss gradient), dense; None passes through"""
+    if t is None:
+        return None
+    check_dev(name, t)
+    if t.numel() != 1:
+        raise ValueError(f"{name} must be a scalar")
+    return dense(t, 4)
+
+
+def same_shape(name, t, like):
+    """a device fp32 tensor of `like`'s shape (an upstream gradient), dense for an entry that picks its width by the pointer; None
+    passes through"""
+    if t is None:
+        return None
+    check_dev(name, t)
+    if t.shape != like.shape:
+        raise ValueError(f"{name} must have the shape {tuple(like.shape)}, got {tuple(t.shape)}")
+    return dense(t, 4)
+
+
+def books(codebooks, lo, hi, align):
+    """-> the dense (K, D) codebooks of a residual or grouped quantizer: a sequence of tensors, one (K, D) tensor, or one (n, K, D)
+    tensor; between lo and hi (None: no bound) of them, all device fp32 of one shape"""
+    if isinstance(codebooks, torch.Tensor):
+        codebooks = [codebooks] if codebooks.dim() == 2 else list(codebooks.unbind(0))
+    out = list(codebooks)
+    if len(out) < lo or (hi is not None and len(out) > hi):
+        raise ValueError(f"{len(out)} codebooks: at least {lo}" + (f" and at most {hi}" if hi is not None else ""))
+    for i, c in enumerate(out):
+        check_dev(f"codebooks[{i}]", c)
+        if c.dim() != 2 or c.shape != out[0].shape:
+            raise ValueError("every codebook must be (K, D) with the same K and D")
+    return [dense(c, align) for c in out]
+
+
 def vq_kernel_name(K: int, D: int, flags: int = 0x1) -> str:
     """kernel vqvae_vq_forward_f32 launches for this shape (default flags: row-major rows, the fused path's layout)"""
     return load().vqvae_vq_kernel_name(K, D, flags).decode()

@@ -21,7 +21,8 @@ from __future__ import annotations
 import torch
 
 from . import _cache, _lib, conv_hip
-from .conv_hip import (CONV_1x1, CONV_3x3_S1, CONV_4x4_S2, CONVT_3x3_S1, CONVT_4x4_S2, RELU_IN, RELU_OUT, _sp)
+from ._lib import stream_ptr as _sp
+from .conv_hip import CONV_1x1, CONV_3x3_S1, CONV_4x4_S2, CONVT_3x3_S1, CONVT_4x4_S2, RELU_IN, RELU_OUT
 
 CONVT_1x1 = 5
 # kind -> (kernel size, stride, pad, is_transposed, kind of the data-gradient conv)
@@ -66,8 +67,7 @@ def bias_grad(g, nchw=False):
     L = _lib.load()
     ws = torch.empty(L.vqvae_bias_grad_workspace_bytes(C), dtype=torch.uint8, device=g.device)
     out = torch.empty(C, dtype=torch.float32, device=g.device)
-    _lib.check(L.vqvae_bias_grad_f32(g.data_ptr(), B, H * W, C, 1 if nchw else 0, out.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _sp(g)))
+    _lib.check(L.vqvae_bias_grad_f32(g.data_ptr(), B, H * W, C, 1 if nchw else 0, out.data_ptr(), *_lib.ws_args(ws), _sp(g)))
     return out
 
 
@@ -81,12 +81,11 @@ def conv_wgrad(a_rows, bt, k, stride, pad, bt_nchw=False):
     else:
         _, HB, WB, CB = bt.shape
     L = _lib.load()
-    n = L.vqvae_conv_wgrad_workspace_bytes(CA, CB, k)
-    ws = torch.empty(n, dtype=torch.uint8, device=a_rows.device)
+    ws = torch.empty(L.vqvae_conv_wgrad_workspace_bytes(CA, CB, k), dtype=torch.uint8, device=a_rows.device)
     gw = torch.empty((CA, CB, k, k), dtype=torch.float32, device=a_rows.device)
     _lib.check(L.vqvae_conv_wgrad_ex_f32(a_rows.data_ptr(), bt.data_ptr(), B, HA, WA, CA, HB, WB, CB, k, stride, pad,
                                          1 if bt_nchw else 0, conv_hip.EXACT_FP32 if WGRAD_EXACT_FP32 else 0, gw.data_ptr(),
-                                         ws.data_ptr(), n, _sp(a_rows)))
+                                         *_lib.ws_args(ws), _sp(a_rows)))
     return gw
 
 

@@ -9,21 +9,11 @@ from __future__ import annotations
 import torch
 
 from . import _cache, _lib
+from ._lib import check_dev, ptr, stream_ptr as _sp
 
 CONV_4x4_S2, CONV_3x3_S1, CONV_1x1, CONVT_3x3_S1, CONVT_4x4_S2 = range(5)
 RELU_IN, RELU_OUT = 1, 2
 EXACT_FP32 = 4                 # VQVAE_CONV_EXACT_FP32
-
-
-def _sp(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _dev_f32(name, t):
-    if not t.is_cuda:
-        raise _lib.VqvaeHipError(f"{name} must be on the GPU: the HIP path has no CPU fallback")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (the reference path is fp32 only)")
 
 
 def _packed(mod, kind, weight, nbytes_fn, pack_fn):
@@ -90,15 +80,13 @@ def conv(kind, x, mod, weight, bias, Cin, Cout, flags, addend=None, mask=None):
             if t is not None and t.shape != y.shape:
                 raise ValueError("addend / mask must have the output's shape")
         addend, mask = _lib.dense(addend), _lib.dense(mask)
-        rc = L.vqvae_conv_forward_ep_f32(kind, x.data_ptr(), packed.data_ptr(), b.data_ptr() if b is not None else None,
-                                         B, H, W, Cin, Cout, flags, addend.data_ptr() if addend is not None else None,
-                                         mask.data_ptr() if mask is not None else None, y.data_ptr(), _sp(x))
+        rc = L.vqvae_conv_forward_ep_f32(kind, x.data_ptr(), packed.data_ptr(), ptr(b), B, H, W, Cin, Cout, flags, ptr(addend),
+                                         ptr(mask), y.data_ptr(), _sp(x))
         if rc == 0:
             return y
         if rc != _lib.ERR_UNSUPPORTED:
             _lib.check(rc)
-    _lib.check(L.vqvae_conv_forward_f32(kind, x.data_ptr(), packed.data_ptr(), b.data_ptr() if b is not None else None,
-                                        B, H, W, Cin, Cout, flags, y.data_ptr(), _sp(x)))
+    _lib.check(L.vqvae_conv_forward_f32(kind, x.data_ptr(), packed.data_ptr(), ptr(b), B, H, W, Cin, Cout, flags, y.data_ptr(), _sp(x)))
     if addend is not None:
         y = y + addend
     if mask is not None:
@@ -138,9 +126,9 @@ def conv_taps(x, mod, weight, bias, taps, flags=0):
             return rc                  # (a slice's temporary is freed in stream order behind the pack launch: same stream)
         packed = _packed(mod, key, weight, lambda k=k: L.vqvae_conv_taps_packed_bytes(k, Cin, Cout), pack)
         out = torch.empty((B, H, W, Cout), dtype=torch.float32, device=x.device)
-        _lib.check(L.vqvae_conv_taps_forward_ep_f32(x.data_ptr(), packed.data_ptr(), b.data_ptr() if (b is not None and y is None) else None,
+        _lib.check(L.vqvae_conv_taps_forward_ep_f32(x.data_ptr(), packed.data_ptr(), ptr(b) if y is None else None,
                                                     B, H, W, Cin, Cout, k, C.cast(dy, C.c_void_p), C.cast(dx, C.c_void_p), flags,
-                                                    y.data_ptr() if y is not None else None, None, out.data_ptr(), _sp(x)))
+                                                    ptr(y), None, out.data_ptr(), _sp(x)))
         y = out
     return y
 
@@ -161,7 +149,7 @@ def res_layer(x, layer, flags, want_hidden=False):
         # widths outside the fused kernel (round 4): 3x3 conv -> 1x1 conv -> skip + ReLU through the conv kernels
         scratch = torch.empty((B, H, W, Rh), dtype=torch.float32, device=x.device)
         _lib.check(_lib.load().vqvae_res_layer_forward_ws_f32(x.data_ptr(), p1.data_ptr(), p2.data_ptr(), B, H, W, C, Rh, flags,
-                                                              y.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, _sp(x)))
+                                                              y.data_ptr(), *_lib.ws_args(scratch), _sp(x)))
         return (y, None) if want_hidden else y
     if want_hidden and H == 8 and W == 8 and Rh == 32:
         hid = torch.empty((B, H, W, Rh), dtype=torch.float32, device=x.device)
@@ -205,14 +193,14 @@ def _res_stack_rows(t, layers, first_relu_in, final_relu):
 
 
 def residual_stack_nchw(x, layers, final_relu):
-    _dev_f32("x", x)
+    check_dev("x", x)
     t = _res_stack_rows(nchw_to_rows(x), layers, True, final_relu)
     return rows_to_nchw(t)
 
 
 def encoder_forward(enc, x, pre_quant):
     """models/encoder.py:28-43 (+ models/vqvae.py:33 when pre_quant is given)."""
-    _dev_f32("x", x)
+    check_dev("x", x)
     cs = enc.conv_stack
     c0, c2, c4, stack = cs[0], cs[2], cs[4], cs[5]
     x = _lib.dense(x, 4)                       # (conv_in takes its gather kernel for an under-aligned image)
@@ -241,7 +229,7 @@ def encoder_forward(enc, x, pre_quant):
 
 def decoder_forward(dec, z_q, rowmajor_in):
     """models/decoder.py:27-39."""
-    _dev_f32("z_q", z_q)
+    check_dev("z_q", z_q)
     ds = dec.inverse_conv_stack
     d0, stack, d2, d4 = ds[0], ds[1], ds[2], ds[4]
     t = _lib.dense(z_q) if rowmajor_in else nchw_to_rows(z_q)

@@ -196,12 +196,12 @@ class Adam(torch.optim.Optimizer):
         if pl is None or pl.key != key or (pl.norm is None) != (self.max_grad_norm is None) or not self._states_unchanged(pl):
             pl = self._plan = self._build(entries, key)
         L = _lib.load()
-        stream = torch.cuda.current_stream(pl.dev.device).cuda_stream
+        stream = _lib.stream_ptr(pl.dev)
         clip = None
         if self.max_grad_norm is not None:
             out = pl.norm
             _lib.check(L.vqvae_grad_norm_f32(pl.dev.data_ptr(), pl.nbytes, pl.n_tensors, pl.n_chunks, float(self.max_grad_norm),
-                                             out.data_ptr(), out.data_ptr() + 4, pl.ws.data_ptr(), pl.ws.numel(), stream))
+                                             out.data_ptr(), out.data_ptr() + 4, *_lib.ws_args(pl.ws), stream))
             self.last_grad_norm = out[0]
             clip = out.data_ptr() + 4
         _lib.check(L.vqvae_adam_step_f32(pl.dev.data_ptr(), pl.nbytes, pl.n_tensors, pl.n_chunks, hyper, len(self.param_groups),

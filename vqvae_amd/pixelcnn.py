@@ -41,9 +41,9 @@ import torch
 import torch.nn as nn
 
 from . import _cache, _lib, conv_hip
-from ._lib import VqvaeHipError
+from ._lib import VqvaeHipError, ptr, ws_args, stream_ptr as _sp
 from .autograd_conv import CONVT_1x1, _holder, conv_wgrad, relu_backward
-from .conv_hip import CONV_1x1, RELU_OUT, _sp
+from .conv_hip import CONV_1x1, RELU_OUT
 
 
 SAMPLE_NONFINITE, SAMPLE_GIVEN_RANGE = 1, 2          # VQVAE_SAMPLE_* status bits of the cached sampler (include/vqvae_hip.h)
@@ -94,9 +94,7 @@ def _gate(t1, t2, cond, dim):
     t1, t2, cond = _lib.dense(t1, 4), _lib.dense(t2, 4), _lib.dense(cond, 4)     # (element-wise kernels)
     B, H, W, _ = t1.shape
     out = torch.empty((B, H, W, dim), dtype=torch.float32, device=t1.device)
-    _lib.check(_lib.load().vqvae_gated_activation_f32(t1.data_ptr(), t2.data_ptr() if t2 is not None else None,
-                                                      cond.data_ptr() if cond is not None else None, B, H * W, dim,
-                                                      out.data_ptr(), _sp(out)))
+    _lib.check(_lib.load().vqvae_gated_activation_f32(t1.data_ptr(), ptr(t2), ptr(cond), B, H * W, dim, out.data_ptr(), _sp(out)))
     return out
 
 
@@ -142,14 +140,12 @@ def taps_wgrad(gy, x, taps):
     B, H, W, Cin = x.shape
     Cout, n = gy.shape[3], len(taps)
     L = _lib.load()
-    nb = L.vqvae_conv_taps_wgrad_workspace_bytes(n, Cin, Cout)
-    if nb == 0:
-        raise VqvaeHipError(f"tap-list weight gradient: {n} taps, Cin={Cin}, Cout={Cout} not supported")
-    ws = _ws(nb, x.device)
+    ws = _lib.workspace("vqvae_conv_taps_wgrad_workspace_bytes", "tap-list weight gradient", "1 to 32 taps, Cin and Cout multiples of 4",
+                        dict(taps=n, Cin=Cin, Cout=Cout), x.device)
     gw = torch.empty((Cout, Cin, n), dtype=torch.float32, device=x.device)
     dy, dx = _taps_arrays(taps)
     _lib.check(L.vqvae_conv_taps_wgrad_f32(gy.data_ptr(), x.data_ptr(), B, H, W, Cin, Cout, n, C.cast(dy, C.c_void_p),
-                                           C.cast(dx, C.c_void_p), gw.data_ptr(), ws.data_ptr(), nb, _sp(x)))
+                                           C.cast(dx, C.c_void_p), gw.data_ptr(), *ws_args(ws), _sp(x)))
     return gw
 
 
@@ -178,7 +174,7 @@ def taps_dgrad(gy, mod, weight, taps, addend=None):
         out = torch.empty((B, H, W, Cin), dtype=torch.float32, device=gy.device)
         _lib.check(L.vqvae_conv_taps_forward_ep_f32(gy.data_ptr(), packed.data_ptr(), None, B, H, W, Cout, Cin, k,
                                                     C.cast(ndy, C.c_void_p), C.cast(ndx, C.c_void_p), 0,
-                                                    y.data_ptr() if y is not None else None, None, out.data_ptr(), _sp(gy)))
+                                                    ptr(y), None, out.data_ptr(), _sp(gy)))
         y = out
     return y
 
@@ -190,8 +186,8 @@ def gate_backward(t1, cond, go, dim, gcond=None, accumulate=False):
     gpre = torch.empty((B, H, W, 2 * dim), dtype=torch.float32, device=t1.device)
     go = _lib.dense(go, 4)
     _lib.check(_lib.load().vqvae_gated_activation_backward_f32(
-        t1.data_ptr(), None, cond.data_ptr() if cond is not None else None, go.data_ptr(), B, H * W, dim, gpre.data_ptr(),
-        gcond.data_ptr() if (gcond is not None and accumulate) else None, gcond.data_ptr() if gcond is not None else None, _sp(go)))
+        t1.data_ptr(), None, ptr(cond), go.data_ptr(), B, H * W, dim, gpre.data_ptr(), ptr(gcond) if accumulate else None, ptr(gcond),
+        _sp(go)))
     return gpre
 
 
@@ -200,12 +196,10 @@ def gather_rows_backward(idx, g, rows):
     idx, g = _lib.dense(idx, 8).view(-1), _lib.dense(g, 4)
     n, Cc = idx.numel(), g.shape[-1]
     L = _lib.load()
-    nb = L.vqvae_gather_rows_backward_workspace_bytes(n, Cc, rows)
-    if nb == 0:
-        raise VqvaeHipError(f"embedding backward: n={n}, C={Cc}, rows={rows} not supported")
-    ws = _ws(nb, g.device)
+    ws = _lib.workspace("vqvae_gather_rows_backward_workspace_bytes", "embedding backward", "1 <= n < 2^31, C >= 1, 1 <= rows <= 2^24",
+                        dict(n=n, C=Cc, rows=rows), g.device)
     out = torch.empty((rows, Cc), dtype=torch.float32, device=g.device)
-    _lib.check(L.vqvae_gather_rows_backward_f32(idx.data_ptr(), g.data_ptr(), n, Cc, rows, out.data_ptr(), ws.data_ptr(), nb, _sp(g)))
+    _lib.check(L.vqvae_gather_rows_backward_f32(idx.data_ptr(), g.data_ptr(), n, Cc, rows, out.data_ptr(), *ws_args(ws), _sp(g)))
     return out
 
 
@@ -616,8 +610,7 @@ class GatedPixelCNN(nn.Module):
             # (1, 0, 1, NULL) is vqvae_pixelcnn_sample_f32: the plain kernel
             _lib.check(L.vqvae_pixelcnn_sample_ex_f32(img.data_ptr(), img.numel(), label.data_ptr(), uniforms.data_ptr(), B, H, W, K,
                                                       dim, n_layers, n_classes, temperature, top_k, top_p,
-                                                      given.data_ptr() if given is not None else None, out.data_ptr(),
-                                                      logits.data_ptr() if logits is not None else None, status.data_ptr(),
+                                                      ptr(given), out.data_ptr(), ptr(logits), status.data_ptr(),
                                                       ws.data_ptr(), nws, _sp(out)))
             bad = bad_given = 0
             if int((status != 0).sum()):

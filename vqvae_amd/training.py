@@ -26,8 +26,31 @@ from . import _lib
 from . import functional as F_hip
 
 
-def _sp(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+def _bwd_args(z_e, idx, grad_zq, grad_loss, rowmajor):
+    """what the three quantizer backwards share in front of their codebooks: -> ((B, D, H, W), and the dense forms of z_e, idx,
+    grad_zq -- z_e's shape, or None -- and grad_loss -- a device scalar, or None)"""
+    dims = _lib.map_dims("z_e", z_e, rowmajor)
+    _lib.check_dev("idx", idx, torch.int64)
+    z_e = _lib.dense(z_e, 4)                   # (the entries pick their kernels' width by these pointers)
+    return dims, z_e, _lib.dense(idx, 8), _lib.same_shape("grad_zq", grad_zq, z_e), _lib.device_scalar("grad_loss", grad_loss)
+
+
+def _bwd_launch(entry, what, dims, z_e, books, idx, grad_zq, grad_loss, beta, flags, need_z, need_books, **count):
+    """... and behind them: the gradients' and the workspace's allocation and the launch of vqvae_<entry>_f32.  count: Q=stages or
+    G=groups of an entry that takes a list of codebooks, nothing for the one-codebook entry.  -> (grad_z, codebook gradients)"""
+    B, D, H, W = dims
+    K, multi = books[0].shape[0], bool(count)
+    dev = z_e.device
+    with torch.cuda.device(dev):
+        gz = torch.empty_like(z_e) if need_z else None
+        ge = [torch.empty_like(c) for c in books] if need_books else None
+        ws = _lib.workspace(f"vqvae_{entry}_workspace_bytes", what, "1 <= K <= 16384, 1 <= D <= 256, 1 <= N < 2^31, at most 16 stages or groups",
+                            dict(N=B * H * W, K=K, D=D, **count), dev) if need_books else None
+        _lib.check(getattr(_lib.load(), f"vqvae_{entry}_f32")(
+            z_e.data_ptr(), _lib.ptr_array(books) if multi else books[0].data_ptr(), idx.data_ptr(), _lib.ptr(grad_zq),
+            _lib.ptr(grad_loss), B, D, H, W, K, *count.values(), float(beta), flags, _lib.ptr(gz),
+            _lib.ptr_array(ge) if multi else _lib.ptr(ge and ge[0]), *_lib.ws_args(ws), _lib.stream_ptr(z_e)))
+    return gz, ge
 
 
 def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False, need_z=True, need_codebook=True,
@@ -43,47 +66,15 @@ def vq_backward(z_e, codebook, idx, grad_zq, grad_loss, beta, *, rowmajor=False,
         raise ValueError("the commitment-only gradient has no codebook term")
     if rotation and not need_z:
         raise ValueError("the rotation trick changes grad_z only: need_z must be set")
-    F_hip._check_dev("z_e", z_e)
-    F_hip._check_dev("codebook", codebook)
-    F_hip._check_dev("idx", idx, torch.int64)
-    z_e = _lib.dense(z_e, 4)                   # (the entry picks its kernels' width by these pointers)
-    codebook = _lib.dense(codebook, 4)
-    idx = _lib.dense(idx, 8)
-    if rowmajor:
-        B, H, W, D = z_e.shape
-    else:
-        B, D, H, W = z_e.shape
-    K = codebook.shape[0]
-    if codebook.shape[1] != D or idx.numel() != B * H * W:
+    dims, z_e, idx, grad_zq, grad_loss = _bwd_args(z_e, idx, grad_zq, grad_loss, rowmajor)
+    _lib.check_dev("codebook", codebook)
+    if codebook.dim() != 2 or codebook.shape[1] != dims[1] or idx.numel() != z_e.numel() // dims[1]:
         raise ValueError("shape mismatch between z_e, codebook and idx")
-    if grad_zq is not None:
-        F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = _lib.dense(grad_zq, 4)
-        if grad_zq.shape != z_e.shape:
-            raise ValueError("grad_zq must have z_e's shape")
-    if grad_loss is not None:
-        F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
-    dev = z_e.device
-    L = _lib.load()
-    with torch.cuda.device(dev):
-        gz = torch.empty_like(z_e) if need_z else None
-        ge = torch.empty_like(codebook) if need_codebook else None
-        ws = None
-        if need_codebook:
-            n = L.vqvae_vq_backward_workspace_bytes(B * H * W, K, D)
-            if n == 0:
-                raise _lib.VqvaeHipError(f"VQ backward: shape N={B * H * W}, K={K}, D={D} not supported")
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        _lib.check(L.vqvae_vq_backward_f32(
-            z_e.data_ptr(), codebook.data_ptr(), idx.data_ptr(),
-            grad_zq.data_ptr() if grad_zq is not None else None,
-            grad_loss.data_ptr() if grad_loss is not None else None,
-            B, D, H, W, K, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0) |
-            (F_hip.VQ_BWD_ROTATION if rotation else 0),
-            gz.data_ptr() if gz is not None else None, ge.data_ptr() if ge is not None else None,
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
-    return gz, ge
+    flags = (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0) | \
+        (F_hip.VQ_BWD_ROTATION if rotation else 0)
+    gz, ge = _bwd_launch("vq_backward", "VQ backward", dims, z_e, [_lib.dense(codebook, 4)], idx, grad_zq, grad_loss, beta, flags,
+                         need_z, need_codebook)
+    return gz, ge and ge[0]
 
 
 class VQStraightThrough(torch.autograd.Function):
@@ -162,8 +153,8 @@ class L2NormRows(torch.autograd.Function):
 class _StepLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_hat, x, embedding_loss, perplexity, inv_var):
-        F_hip._check_dev("x_hat", x_hat)
-        F_hip._check_dev("x", x)
+        _lib.check_dev("x_hat", x_hat)
+        _lib.check_dev("x", x)
         xh, xx = _lib.dense(x_hat.detach()), _lib.dense(x.detach())
         if xh.shape != xx.shape:
             raise ValueError("x_hat and x must have the same shape")
@@ -174,10 +165,8 @@ class _StepLosses(torch.autograd.Function):
             ws = torch.empty(L.vqvae_recon_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
             el = _lib.dense(embedding_loss.detach().reshape(1), 4) if embedding_loss is not None else None
             pp = _lib.dense(perplexity.detach().reshape(1), 4) if perplexity is not None else None
-            _lib.check(L.vqvae_recon_loss_f32(xh.data_ptr(), xx.data_ptr(), xh.numel(), float(inv_var),
-                                              el.data_ptr() if el is not None else None,
-                                              pp.data_ptr() if pp is not None else None,
-                                              out.data_ptr(), ws.data_ptr(), ws.numel(), _sp(xh)))
+            _lib.check(L.vqvae_recon_loss_f32(xh.data_ptr(), xx.data_ptr(), xh.numel(), float(inv_var), _lib.ptr(el), _lib.ptr(pp),
+                                              out.data_ptr(), *_lib.ws_args(ws), _lib.stream_ptr(xh)))
         ctx.save_for_backward(xh, xx)
         ctx.inv_var = float(inv_var)
         return out
@@ -192,7 +181,7 @@ class _StepLosses(torch.autograd.Function):
             with torch.cuda.device(xh.device):
                 _lib.check(_lib.load().vqvae_recon_loss_backward_f32(xh.data_ptr(), xx.data_ptr(), xh.numel(),
                                                                      ctx.inv_var, gsum.data_ptr(), gx.data_ptr(),
-                                                                     _sp(xh)))
+                                                                     _lib.stream_ptr(xh)))
         if ctx.needs_input_grad[2]:
             gel = g[1].reshape(())
         return gx, None, gel, None, None
@@ -215,48 +204,19 @@ def vq_residual_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowma
 
     z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.  idx: the forward's (Q, N) indices.  grad_loss: 0-dim device tensor or
     None (= 1).  -> (grad_z or None, list of codebook gradients -- one per codebook, one in all when shared -- or None)."""
-    F_hip._check_dev("z_e", z_e)
-    F_hip._check_dev("idx", idx, torch.int64)
+    dims, z_e, idx, grad_zq, grad_loss = _bwd_args(z_e, idx, grad_zq, grad_loss, rowmajor)
     books, nb = F_hip._residual_books(codebooks, shared)
-    z_e = _lib.dense(z_e, 4)
-    idx = _lib.dense(idx, 8)
-    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
-    K = books[0].shape[0]
-    N = B * H * W
-    if books[0].shape[1] != D or idx.numel() % N or idx.numel() == 0:
+    N = z_e.numel() // dims[1]
+    if books[0].shape[1] != dims[1] or idx.numel() % N or idx.numel() == 0:
         raise ValueError("shape mismatch between z_e, the codebooks and idx")
     Q = idx.numel() // N
     if nb is not None and nb != Q:
         raise ValueError(f"{Q} stages of indices for {nb} codebooks")
-    if grad_zq is not None:
-        F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = _lib.dense(grad_zq, 4)
-        if grad_zq.shape != z_e.shape:
-            raise ValueError("grad_zq must have z_e's shape")
-    if grad_loss is not None:
-        F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
     if not (need_z or need_codebooks):
         return None, None
-    dev = z_e.device
-    L = _lib.load()
-    with torch.cuda.device(dev):
-        gz = torch.empty_like(z_e) if need_z else None
-        ge = [torch.empty_like(c) for c in books] if need_codebooks else None
-        ws = None
-        if need_codebooks:
-            n = L.vqvae_vq_residual_backward_workspace_bytes(N, K, D, Q)
-            if n == 0:
-                raise _lib.VqvaeHipError(f"residual VQ backward: N={N}, K={K}, D={D}, Q={Q} not supported")
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        _lib.check(L.vqvae_vq_residual_backward_f32(
-            z_e.data_ptr(), F_hip._ptr_array(books), idx.data_ptr(),
-            grad_zq.data_ptr() if grad_zq is not None else None,
-            grad_loss.data_ptr() if grad_loss is not None else None,
-            B, D, H, W, K, Q, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_RESIDUAL_SHARED if shared else 0),
-            gz.data_ptr() if gz is not None else None, F_hip._ptr_array(ge) if ge is not None else None,
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
-    return gz, ge
+    flags = (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_RESIDUAL_SHARED if shared else 0)
+    return _bwd_launch("vq_residual_backward", "residual VQ backward", dims, z_e, books, idx, grad_zq, grad_loss, beta, flags,
+                       need_z, need_codebooks, Q=Q)
 
 
 class RVQStraightThrough(torch.autograd.Function):
@@ -301,46 +261,16 @@ def vq_grouped_backward(z_e, codebooks, idx, grad_zq, grad_loss, beta, *, rowmaj
     -> (grad_z or None, list of G codebook gradients or None)."""
     if commitment and need_codebooks:
         raise ValueError("the commitment-only gradient has no codebook term")
-    F_hip._check_dev("z_e", z_e)
-    F_hip._check_dev("idx", idx, torch.int64)
-    books = F_hip._grouped_books(codebooks)
+    dims, z_e, idx, grad_zq, grad_loss = _bwd_args(z_e, idx, grad_zq, grad_loss, rowmajor)
+    books = _lib.books(codebooks, 1, 16, 4)
     G = len(books)
-    z_e = _lib.dense(z_e, 4)
-    idx = _lib.dense(idx, 8)
-    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
-    K, d = books[0].shape
-    N = B * H * W
-    if d * G != D or idx.numel() != G * N:
+    if books[0].shape[1] * G != dims[1] or idx.numel() * dims[1] != G * z_e.numel():
         raise ValueError("shape mismatch between z_e, the codebooks and idx")
-    if grad_zq is not None:
-        F_hip._check_dev("grad_zq", grad_zq)
-        grad_zq = _lib.dense(grad_zq, 4)
-        if grad_zq.shape != z_e.shape:
-            raise ValueError("grad_zq must have z_e's shape")
-    if grad_loss is not None:
-        F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = _lib.dense(grad_loss.reshape(1), 4)
     if not (need_z or need_codebooks):
         return None, None
-    dev = z_e.device
-    L = _lib.load()
-    with torch.cuda.device(dev):
-        gz = torch.empty_like(z_e) if need_z else None
-        ge = [torch.empty_like(c) for c in books] if need_codebooks else None
-        ws = None
-        if need_codebooks:
-            n = L.vqvae_vq_grouped_backward_workspace_bytes(N, K, D, G)
-            if n == 0:
-                raise _lib.VqvaeHipError(f"grouped VQ backward: N={N}, K={K}, D={D}, G={G} not supported")
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        _lib.check(L.vqvae_vq_grouped_backward_f32(
-            z_e.data_ptr(), F_hip._ptr_array(books), idx.data_ptr(),
-            grad_zq.data_ptr() if grad_zq is not None else None,
-            grad_loss.data_ptr() if grad_loss is not None else None,
-            B, D, H, W, K, G, float(beta), (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0),
-            gz.data_ptr() if gz is not None else None, F_hip._ptr_array(ge) if ge is not None else None,
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
-    return gz, ge
+    flags = (F_hip.VQ_ROWMAJOR if rowmajor else 0) | (F_hip.VQ_BWD_COMMITMENT if commitment else 0)
+    return _bwd_launch("vq_grouped_backward", "grouped VQ backward", dims, z_e, books, idx, grad_zq, grad_loss, beta, flags,
+                       need_z, need_codebooks, G=G)
 
 
 class GroupedStraightThrough(torch.autograd.Function):
@@ -388,30 +318,33 @@ def fsq_backward(z_e, grad_zq, w_in, b_in, w_out, levels, *, rowmajor=False, nee
     are differentiated; t is recomputed from z_e.  z_e / grad_zq: (B,D,H,W), or (B,H,W,D) when rowmajor.
     -> (grad_z or None, (grad_w_in, grad_b_in, grad_w_out, grad_b_out) or None).  The parameter gradients are fp64 sums in a fixed
     order: the same bits in both layouts and in every run."""
-    F_hip._check_dev("z_e", z_e)
-    F_hip._check_dev("grad_zq", grad_zq)
-    if z_e.dim() != 4 or grad_zq.shape != z_e.shape:
-        raise ValueError("z_e must be 4-D and grad_zq must have its shape")
+    B, D, H, W = _lib.map_dims("z_e", z_e, rowmajor)
+    _lib.check_dev("grad_zq", grad_zq)
+    grad_zq = _lib.same_shape("grad_zq", grad_zq, z_e)
     if not (need_z or need_params):
         return None, None
-    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     lv, c_lv, _ = F_hip._fsq_levels(levels)
     d = len(lv)
     w_in, b_in, w_out = F_hip._fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out)
-    z_e, grad_zq = _lib.dense(z_e, 4), _lib.dense(grad_zq, 4)
+    z_e = _lib.dense(z_e, 4)
     dev = z_e.device
     with torch.cuda.device(dev):
         gz = torch.empty_like(z_e) if need_z else None
-        gp = ws = None
-        if need_params:
-            gp = (torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out), torch.empty((D,), dtype=torch.float32, device=dev))
-            ws = F_hip.fsq_backward_workspace(B * H * W, D, d, dev)
-        p = [t.data_ptr() for t in gp] if gp is not None else [None] * 4
+        gp, p = _param_grads(w_in, b_in, w_out, need_params)
+        ws = F_hip.fsq_backward_workspace(B * H * W, D, d, dev) if need_params else None
         _lib.check(_lib.load().vqvae_fsq_backward_f32(
             z_e.data_ptr(), grad_zq.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), c_lv, d, B, D, H, W,
-            F_hip.VQ_ROWMAJOR if rowmajor else 0, gz.data_ptr() if need_z else None, *p,
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _sp(z_e)))
+            F_hip.VQ_ROWMAJOR if rowmajor else 0, _lib.ptr(gz), *p, *_lib.ws_args(ws), _lib.stream_ptr(z_e)))
     return gz, gp
+
+
+def _param_grads(w_in, b_in, w_out, need_params):
+    """-> (the four empty parameter gradients of a projected-code quantizer -- like w_in, b_in, w_out and b_out (D,) -- or None,
+    their four pointers or Nones)"""
+    if not need_params:
+        return None, [None] * 4
+    gp = (torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out), w_out.new_empty(w_out.shape[0]))
+    return gp, [t.data_ptr() for t in gp]
 
 
 class FSQStraightThrough(torch.autograd.Function):
@@ -445,39 +378,28 @@ def lfq_backward(z_e, grad_zq, grad_loss, avg, w_in, b_in, w_out, n_e, *, beta=0
     entropy terms are differentiated through the factorised softmax.  grad_zq (z_e's shape) may be None (zero); grad_loss is a device
     scalar or None (one); avg is the forward's (K,) fp64, or None when the loss has no gradient.
     -> (grad_z or None, (grad_w_in, grad_b_in, grad_w_out, grad_b_out) or None), in fixed-order fp64 sums."""
-    F_hip._check_dev("z_e", z_e)
-    if grad_zq is not None:
-        F_hip._check_dev("grad_zq", grad_zq)
-    if z_e.dim() != 4 or (grad_zq is not None and grad_zq.shape != z_e.shape):
-        raise ValueError("z_e must be 4-D and grad_zq must have its shape")
+    B, D, H, W = _lib.map_dims("z_e", z_e, rowmajor)
+    grad_zq = _lib.same_shape("grad_zq", grad_zq, z_e)
     if not (need_z or need_params):
         return None, None
-    B, H, W, D = z_e.shape if rowmajor else (z_e.shape[0], z_e.shape[2], z_e.shape[3], z_e.shape[1])
     d = F_hip._lfq_bits(n_e)
     w_in, b_in, w_out = F_hip._fsq_params(D, d, w_in=w_in, b_in=b_in, w_out=w_out)
     if avg is not None:
-        F_hip._check_dev("avg", avg, torch.float64)
+        _lib.check_dev("avg", avg, torch.float64)
         if avg.numel() != n_e:
             raise ValueError("avg must hold n_e values")
         avg = _lib.dense(avg, 8)
-    if grad_loss is not None:
-        F_hip._check_dev("grad_loss", grad_loss)
-        grad_loss = _lib.dense(grad_loss, 4)
+    grad_loss = _lib.device_scalar("grad_loss", grad_loss)
     z_e = _lib.dense(z_e, 4)
-    grad_zq = _lib.dense(grad_zq, 4) if grad_zq is not None else None
     dev = z_e.device
     with torch.cuda.device(dev):
         gz = torch.empty_like(z_e) if need_z else None
-        gp = None
-        if need_params:
-            gp = (torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out), torch.empty((D,), dtype=torch.float32, device=dev))
+        gp, p = _param_grads(w_in, b_in, w_out, need_params)
         ws = workspace if workspace is not None else F_hip.lfq_workspace(B * H * W, D, d, dev)
-        p = [t.data_ptr() for t in gp] if gp is not None else [None] * 4
         _lib.check(_lib.load().vqvae_lfq_backward_f32(
-            z_e.data_ptr(), grad_zq.data_ptr() if grad_zq is not None else None, grad_loss.data_ptr() if grad_loss is not None else None,
-            avg.data_ptr() if avg is not None else None, w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), d, B, D, H, W,
-            F_hip.VQ_ROWMAJOR if rowmajor else 0, beta, entropy_weight, diversity_gamma, inv_temperature,
-            gz.data_ptr() if need_z else None, *p, ws.data_ptr(), ws.numel(), _sp(z_e)))
+            z_e.data_ptr(), _lib.ptr(grad_zq), _lib.ptr(grad_loss), _lib.ptr(avg), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(),
+            d, B, D, H, W, F_hip.VQ_ROWMAJOR if rowmajor else 0, beta, entropy_weight, diversity_gamma, inv_temperature,
+            _lib.ptr(gz), *p, *_lib.ws_args(ws), _lib.stream_ptr(z_e)))
     return gz, gp
 
 
